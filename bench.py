@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the RMHMC hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over the whole batch: every chain executes ONE generalised
 leapfrog step (rmhmc.py:96-163), including the transition bookkeeping (momentum draw, Hamiltonians,
@@ -16,11 +16,15 @@ Workloads (BASELINE.json configs):
   c5  4096 chains, D=256, M=50000 (large-D path)
 
 The timed region runs the product path exactly as a user gets it (the global step replayed from a
-hipGraph, no per-kernel events).  Right after it the SAME K steps are repeated once more with HIP events
-around every launch on the library's stream ("kernel_seconds", un-timed repetition: events disable the
-graph path); the "roofline" object is computed from that repetition.
+hipGraph, no per-kernel events).  A plain run sets up, runs the untimed burn-in and the warmup, times the
+K steps and prints the headline line; --dump-outputs DIR then writes what the timed path hands its caller
+after its last step (rmhmc_chains_state of every chain: theta, iters, accepted) as float64 .npy files.
 
-Extra objects in the JSON line: "roofline" (dominant kernel = metric assembly), "roofline_fp64" (the
+Everything else is measured with --full only.  Right after the timed region the SAME K steps are repeated
+once more with HIP events around every launch on the library's stream ("kernel_seconds", un-timed
+repetition: events disable the graph path); the "roofline" object is computed from that repetition.
+
+Extra objects in the --full JSON line: "roofline" (dominant kernel = metric assembly), "roofline_fp64" (the
 same workload and steps with the metric on the fp64 matrix cores: the same-arithmetic number and its
 fraction of the fp64 MFMA peak), "min_ess" (the second half of BASELINE.json's metric: min-ESS/sec over
 the TimeTaken window of rmhmc.py:194-198, ESS by tools.py:32-74) and "cpu_baseline" (the CPU oracle timed
@@ -45,6 +49,7 @@ INT8_FEED_FREE_REAL = 2.84e15  # op/s of the library's own tile on the REAL oper
                                # and no fragment is re-read (I8_ABLATE timing builds, profiles/r03_i8_real_ceiling.txt: 2.8-2.9e15 on the box that ran
                                # the product at 2.48e15)
 FP64_MFMA_PEAK = 78.6e12  # flop/s dense fp64 matrix (spec); tools/mfma_probe measures 75.1e12
+DUMP_CAP_BYTES = 60_000_000  # --dump-outputs stays under 64 MB: above this, a fixed, seeded sample of the chains
 
 WORKLOADS = {
     "c3": dict(chains=8192, D=64, M=10000, desc="BASELINE config 3/4: 8192 chains per GPU, D=64, M=10000 synthetic logistic regression"),
@@ -132,6 +137,20 @@ def cpu_baseline(XX, t, flags, L, eps, K, budget_s=12.0, literal_budget_s=10.0):
     return out
 
 
+def dump_outputs(d, w, iters, accepted):
+    """--dump-outputs: the chain state after the last timed step, the arrays rmhmc_chains_state returns (positions, completed and
+    accepted transitions per chain), as float64; above DUMP_CAP_BYTES a fixed, seeded sample of chains plus their indices."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {"theta": w, "iters": iters, "accepted": accepted}
+    n, D = w.shape
+    if n * (D + 2) * 8 > DUMP_CAP_BYTES:
+        idx = np.sort(np.random.RandomState(0).choice(n, DUMP_CAP_BYTES // ((D + 3) * 8), replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["chain_index"] = idx
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), np.asarray(v, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -142,6 +161,11 @@ def main():
     ap.add_argument("--i8-slices", type=int, default=-1, help="4..7: assemble the metric (and the leverages) on the int8 matrix cores from that "
                     "many exact byte slices per operand (RMHMC_FLAG_INT8_METRIC, 8 < D <= 256); 0: fp64 matrix cores; -1 (default): 6 slices "
                     "(error of G 2e-14, the level of fp64 summation) where the path applies and the batch fills its 128-chain tiles")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline: kernel_seconds and roofline (an extra "
+                    "repetition of the steps with events), min_ess, cpu_baseline, roofline_fp64 and alternates (the --no-* / --ess-iters "
+                    "options below tune these)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write the chain state the timed path "
+                    "computed (theta, iters, accepted of every chain) to DIR/<name>.npy as float64")
     ap.add_argument("--no-alternates", action="store_true", help="skip the short extra runs with the other metric-assembly variants")
     ap.add_argument("--compat", type=int, default=0, help="1: reference-compatible momentum (L'z) and guards; 0: corrected (default, see DESIGN.md)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -254,13 +278,6 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
 
-    KT_NAMES = ("assemble", "assemble_i8", "assemble_i8_inner", "assemble_i8_inner_delta", "assemble_i8_delta", "vsplit", "leverage", "leverage_i8", "qsplit", "trvec", "rowpass", "mompass", "factor", "small",
-                "fused", "medium", "total")
-    # un-timed repetition of the same K steps with HIP events around every launch (on the library's own stream)
-    ctx.kernel_time("enable"); ctx.kernel_time("reset")
-    tk0 = time.perf_counter(); ctx.chains_run(args.steps); tk1 = time.perf_counter()
-    kt = {k: ctx.kernel_time(k) for k in KT_NAMES}
-    ctx.kernel_time("disable")
     finite = True
     if world > 1 or force_dist:
         # the one exchange of the sharded path: the chain positions are gathered at write-out straight from HBM
@@ -273,18 +290,37 @@ def main():
         if rank == 0:
             finite = all(bool(torch.isfinite(g).all()) for g in gathered)
             gathered_chains = int(sum(g.shape[0] for g in gathered))
+        if args.dump_outputs:   # the counters of every rank as well
+            counters = []
+            for c in (it_t.to(ddev), acc_t.to(ddev)):
+                g = [torch.empty_like(c) for _ in range(world)] if rank == 0 else None
+                dist.gather(c, g, dst=0)
+                counters.append(torch.cat(g).cpu().numpy() if rank == 0 else None)
+            if rank == 0:
+                dump_outputs(args.dump_outputs, torch.cat(gathered).cpu().numpy(), *counters)
         iters, acc = it_t.cpu().numpy(), acc_t.cpu().numpy()
         finite = finite and bool(torch.isfinite(wt).all())
     else:
         w_end, iters, acc = ctx.chains_state()
         finite = bool(np.isfinite(w_end).all())
         gathered_chains = n
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, w_end, iters, acc)
     acc_rate = float(acc.sum()) / max(1.0, float(iters.sum()))
+
+    KT_NAMES = ("assemble", "assemble_i8", "assemble_i8_inner", "assemble_i8_inner_delta", "assemble_i8_delta", "vsplit", "leverage", "leverage_i8", "qsplit", "trvec", "rowpass", "mompass", "factor", "small",
+                "fused", "medium", "total")
+    if args.full:
+        # un-timed repetition of the same K steps with HIP events around every launch (on the library's own stream)
+        ctx.kernel_time("enable"); ctx.kernel_time("reset")
+        tk0 = time.perf_counter(); ctx.chains_run(args.steps); tk1 = time.perf_counter()
+        kt = {k: ctx.kernel_time(k) for k in KT_NAMES}
+        ctx.kernel_time("disable")
 
     ess = None
     if args.ess_iters < 0:
         args.ess_iters = 0 if args.workload == "c5" else 200
-    if args.ess_iters > 0:
+    if args.full and args.ess_iters > 0:
         # second half of the metric: sum over chains of (min over dims of the per-chain ESS) / seconds of the
         # post-burn-in phase (TimeTaken semantics, rmhmc.py:194-198).  ESS by tools.CalculateESS semantics with
         # the MATLAB FFT length (no wrap-around); estimated on a subset of chains to bound the host FFT work.
@@ -311,99 +347,100 @@ def main():
         value = total_steps / elapsed
         bytes_step = 80.0 * M * D          # (2K+2) passes over X per chain per leapfrog step, K=4
         flops_step = 6.0 * M * D * D + 40.0 * M * D + 2.0 * D ** 3
-        a_s, a_n = kt["assemble"]
-        pass_bytes = 8.0 * M * D * n       # one assembly launch = one pass over X for every chain on this GPU
         roof = None
-        f_s, f_n = kt["fused"]
-        if f_n > 0:
-            # small-problem path: one kernel does everything; a launch covers `steps` leapfrog steps of every chain
-            f_avg = f_s / f_n
-            units = n * args.steps / f_n
-            achieved = units * bytes_step / f_avg
-            roof = {"bound": "hbm", "kernel": "k_fused_small (whole leapfrog step, X resident in LDS, fp64 VALU)",
-                    "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": achieved / HBM_PEAK, "traffic": None,
-                    "avg_launch_ms": f_avg * 1e3, "launches": f_n,
-                    "fp64_tflops": units * flops_step / f_avg / 1e12, "fp64_frac": units * flops_step / f_avg / FP64_MFMA_PEAK,
-                    "note": "achieved = algorithmic bytes (80*M*D per chain per leapfrog step, SURVEY 8(d)) / measured launch time; "
-                            "X (64 KB at config 2) is loaded into LDS once per launch, so real HBM traffic is ~0 and the kernel is "
-                            "bound by fp64 VALU issue and exp/log latency, not by HBM"}
-        elif kt["medium"][1] > 0:
-            # small-batch path: one launch = one leapfrog step of every chain (one workgroup per chain)
-            m_s, m_n = kt["medium"]
-            m_avg = m_s / m_n
-            achieved = n * bytes_step / m_avg
-            roof = {"bound": "hbm", "kernel": "k_step_medium (whole leapfrog step in one launch, one 256-thread workgroup per chain)",
-                    "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": achieved / HBM_PEAK, "traffic": None,
-                    "avg_launch_ms": m_avg * 1e3, "launches": m_n,
-                    "fp64_tflops": n * flops_step / m_avg / 1e12,
-                    "note": "achieved = algorithmic bytes (80*M*D per chain per leapfrog step, SURVEY 8(d)) / measured launch time.  With one "
-                            "chain this path is bound by the serial dependency chain of the step (about 70 us of barriers, LDS round trips "
-                            "and the wave-0 factorisations) plus two bookkeeping launches, not by any throughput limit"}
-        elif kt["assemble_i8"][1] > 0:
-            # int8 metric path: the assembly is a sliced integer GEMM, S(S+1)/2 byte products per fp64 product
-            S = args.i8_slices
-            i_s, i_n = kt["assemble_i8"]
-            i_avg = i_s / i_n
-            NP = D * (D + 1) // 2
-            ops = 2.0 * n * M * NP * (S * (S + 1) // 2)
-            roof = {"bound": "mfma", "kernel": "k_assemble_i8 (sum_n v_n x_na x_nb as a sliced int8 GEMM, %d slices, v_mfma_i32_32x32x32_i8)" % S,
-                    "achieved": ops / i_avg / 1e12, "peak": INT8_MFMA_PEAK / 1e12, "unit": "TOP/s", "frac": ops / i_avg / INT8_MFMA_PEAK,
-                    "traffic": None, "avg_launch_ms": i_avg * 1e3, "launches": i_n,
-                    "measured_mfma_stream_peak": INT8_MFMA_STREAM / 1e12,
-                    "frac_of_measured_mfma_stream": ops / i_avg / INT8_MFMA_STREAM,
-                    "feed_free_rate_on_real_bytes": INT8_FEED_FREE_REAL / 1e12,
-                    "feed_free_note": "profiles/r03_i8_real_ceiling.txt: the same tile on the same bytes without LDS-DMA feed and fragment re-reads "
-                                      "sustains 2.8-2.9 POP/s (the chip gives the clock back under load); the product reached 0.83-0.87 of that on the same box",
-                    "fp64_equivalent_tflops": 2.0 * n * M * NP / i_avg / 1e12,
-                    "fp64_equivalent_frac_of_fp64_mfma_peak": 2.0 * n * M * NP / i_avg / FP64_MFMA_PEAK,
-                    "vsplit_avg_launch_ms": kt["vsplit"][0] / max(1, kt["vsplit"][1]) * 1e3,
-                    # the assemblies of the position fixed-point iterates before the last: the 5 most significant slices (15 products)
-                    "inner_iterate_assembly": ({"slices": S - 1, "launches": kt["assemble_i8_inner"][1],
-                                                "avg_launch_ms": kt["assemble_i8_inner"][0] / kt["assemble_i8_inner"][1] * 1e3,
-                                                "frac": 2.0 * n * M * NP * ((S - 1) * S // 2) / (kt["assemble_i8_inner"][0] / kt["assemble_i8_inner"][1]) / INT8_MFMA_PEAK}
-                                               if kt["assemble_i8_inner"][1] else None),
-                    # the assembly of the evaluation that ends a step: G(last iterate) + the GEMM of the v differences, from as many
-                    # slices as the largest difference needs (4 at stationarity: 10 slice products; 5 / 6 in the first steps from theta0)
-                    "delta_assembly": ({"launches": kt["assemble_i8_delta"][1],
-                                        "avg_launch_ms": kt["assemble_i8_delta"][0] / kt["assemble_i8_delta"][1] * 1e3}
-                                       if kt["assemble_i8_delta"][1] else None),
-                    "survey8d_streaming_model_frac_NOT_A_BOUND": (value / world) * bytes_step / HBM_PEAK,
-                    "step_fp64_frac": (value / world) * flops_step / FP64_MFMA_PEAK,
-                    "note": "survey8d_streaming_model_frac = steps/s x 80 M D bytes / 8 TB/s, the figure SURVEY 8(d) / north_star ask for; it can "
-                            "exceed 1 because X is shared by all chains (cache resident), so it is a model, not a physical bound.  "
-                            "achieved = int8 multiply-adds issued for the unpadded problem (chains x D(D+1)/2 pairs x M rows x S(S+1)/2 "
-                            "slice products) / measured launch time; fp64_equivalent = the fp64 flops of the same assembly"}
-        elif a_n > 0:
-            a_avg = a_s / a_n
-            achieved = pass_bytes / a_avg
-            if D > 64:  # large-D path: one launch = all block pairs; compute bound (AI above the ridge)
-                nbk = (D + 63) // 64
-                tiles = nbk * 10 + (nbk * (nbk + 1) // 2 - nbk) * 16
-                fl = n * (M / 4.0) * tiles * 2048.0
-                roof = {"bound": "mfma", "kernel": "k_assemble_pair (X' diag(v) X, one wave per (chain, 64-column block pair), fp64 MFMA)",
-                        "achieved": fl / a_avg / 1e12, "peak": FP64_MFMA_PEAK / 1e12, "unit": "TFLOP/s", "frac": fl / a_avg / FP64_MFMA_PEAK,
-                        "traffic": None, "avg_launch_ms": a_avg * 1e3, "launches": a_n,
-                        "alg_hbm_gbs": achieved / 1e9, "survey8d_streaming_model_frac_NOT_A_BOUND": (value / world) * bytes_step / HBM_PEAK,
-                        "step_fp64_frac": (value / world) * flops_step / FP64_MFMA_PEAK,
-                        "note": "achieved = MFMA flops issued by one assembly launch (all block pairs) / measured launch time"}
-            else:
-                nb16 = (D + 15) // 16
-                fl = n * (M / 4.0) * (nb16 * (nb16 + 1) // 2) * 2048.0
-                roof = {"bound": "hbm", "kernel": "k_assemble (X' diag(v) X on fp64 MFMA)", "achieved": achieved / 1e9,
-                        "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": achieved / HBM_PEAK, "traffic": None,
-                        "avg_launch_ms": a_avg * 1e3, "launches": a_n,
-                        "mfma_tflops": fl / a_avg / 1e12, "mfma_frac": fl / a_avg / FP64_MFMA_PEAK,
+        if args.full:
+            a_s, a_n = kt["assemble"]
+            pass_bytes = 8.0 * M * D * n       # one assembly launch = one pass over X for every chain on this GPU
+            f_s, f_n = kt["fused"]
+            if f_n > 0:
+                # small-problem path: one kernel does everything; a launch covers `steps` leapfrog steps of every chain
+                f_avg = f_s / f_n
+                units = n * args.steps / f_n
+                achieved = units * bytes_step / f_avg
+                roof = {"bound": "hbm", "kernel": "k_fused_small (whole leapfrog step, X resident in LDS, fp64 VALU)",
+                        "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": achieved / HBM_PEAK, "traffic": None,
+                        "avg_launch_ms": f_avg * 1e3, "launches": f_n,
+                        "fp64_tflops": units * flops_step / f_avg / 1e12, "fp64_frac": units * flops_step / f_avg / FP64_MFMA_PEAK,
+                        "note": "achieved = algorithmic bytes (80*M*D per chain per leapfrog step, SURVEY 8(d)) / measured launch time; "
+                                "X (64 KB at config 2) is loaded into LDS once per launch, so real HBM traffic is ~0 and the kernel is "
+                                "bound by fp64 VALU issue and exp/log latency, not by HBM"}
+            elif kt["medium"][1] > 0:
+                # small-batch path: one launch = one leapfrog step of every chain (one workgroup per chain)
+                m_s, m_n = kt["medium"]
+                m_avg = m_s / m_n
+                achieved = n * bytes_step / m_avg
+                roof = {"bound": "hbm", "kernel": "k_step_medium (whole leapfrog step in one launch, one 256-thread workgroup per chain)",
+                        "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": achieved / HBM_PEAK, "traffic": None,
+                        "avg_launch_ms": m_avg * 1e3, "launches": m_n,
+                        "fp64_tflops": n * flops_step / m_avg / 1e12,
+                        "note": "achieved = algorithmic bytes (80*M*D per chain per leapfrog step, SURVEY 8(d)) / measured launch time.  With one "
+                                "chain this path is bound by the serial dependency chain of the step (about 70 us of barriers, LDS round trips "
+                                "and the wave-0 factorisations) plus two bookkeeping launches, not by any throughput limit"}
+            elif kt["assemble_i8"][1] > 0:
+                # int8 metric path: the assembly is a sliced integer GEMM, S(S+1)/2 byte products per fp64 product
+                S = args.i8_slices
+                i_s, i_n = kt["assemble_i8"]
+                i_avg = i_s / i_n
+                NP = D * (D + 1) // 2
+                ops = 2.0 * n * M * NP * (S * (S + 1) // 2)
+                roof = {"bound": "mfma", "kernel": "k_assemble_i8 (sum_n v_n x_na x_nb as a sliced int8 GEMM, %d slices, v_mfma_i32_32x32x32_i8)" % S,
+                        "achieved": ops / i_avg / 1e12, "peak": INT8_MFMA_PEAK / 1e12, "unit": "TOP/s", "frac": ops / i_avg / INT8_MFMA_PEAK,
+                        "traffic": None, "avg_launch_ms": i_avg * 1e3, "launches": i_n,
+                        "measured_mfma_stream_peak": INT8_MFMA_STREAM / 1e12,
+                        "frac_of_measured_mfma_stream": ops / i_avg / INT8_MFMA_STREAM,
+                        "feed_free_rate_on_real_bytes": INT8_FEED_FREE_REAL / 1e12,
+                        "feed_free_note": "profiles/r03_i8_real_ceiling.txt: the same tile on the same bytes without LDS-DMA feed and fragment re-reads "
+                                          "sustains 2.8-2.9 POP/s (the chip gives the clock back under load); the product reached 0.83-0.87 of that on the same box",
+                        "fp64_equivalent_tflops": 2.0 * n * M * NP / i_avg / 1e12,
+                        "fp64_equivalent_frac_of_fp64_mfma_peak": 2.0 * n * M * NP / i_avg / FP64_MFMA_PEAK,
+                        "vsplit_avg_launch_ms": kt["vsplit"][0] / max(1, kt["vsplit"][1]) * 1e3,
+                        # the assemblies of the position fixed-point iterates before the last: the 5 most significant slices (15 products)
+                        "inner_iterate_assembly": ({"slices": S - 1, "launches": kt["assemble_i8_inner"][1],
+                                                    "avg_launch_ms": kt["assemble_i8_inner"][0] / kt["assemble_i8_inner"][1] * 1e3,
+                                                    "frac": 2.0 * n * M * NP * ((S - 1) * S // 2) / (kt["assemble_i8_inner"][0] / kt["assemble_i8_inner"][1]) / INT8_MFMA_PEAK}
+                                                   if kt["assemble_i8_inner"][1] else None),
+                        # the assembly of the evaluation that ends a step: G(last iterate) + the GEMM of the v differences, from as many
+                        # slices as the largest difference needs (4 at stationarity: 10 slice products; 5 / 6 in the first steps from theta0)
+                        "delta_assembly": ({"launches": kt["assemble_i8_delta"][1],
+                                            "avg_launch_ms": kt["assemble_i8_delta"][0] / kt["assemble_i8_delta"][1] * 1e3}
+                                           if kt["assemble_i8_delta"][1] else None),
                         "survey8d_streaming_model_frac_NOT_A_BOUND": (value / world) * bytes_step / HBM_PEAK,
                         "step_fp64_frac": (value / world) * flops_step / FP64_MFMA_PEAK,
-                        "note": "achieved = algorithmic bytes (8*M*D per chain per pass) / measured launch time; X is shared by all "
-                                "chains and cache resident, so DRAM traffic is far below the algorithmic bytes (see DESIGN.md)"}
-            pmc = os.path.join(ROOT, "profiles", "traffic_%s.json" % args.workload)
-            if os.path.exists(pmc):
-                roof["traffic"] = json.load(open(pmc)).get("assemble_bytes_per_launch")
-        if roof is not None and kt["assemble_i8"][1] > 0:
-            pmc = os.path.join(ROOT, "profiles", "traffic_%s.json" % args.workload)
-            if os.path.exists(pmc):
-                roof["traffic"] = json.load(open(pmc)).get("assemble_i8_x%d_bytes_per_launch" % args.i8_slices)
+                        "note": "survey8d_streaming_model_frac = steps/s x 80 M D bytes / 8 TB/s, the figure SURVEY 8(d) / north_star ask for; it can "
+                                "exceed 1 because X is shared by all chains (cache resident), so it is a model, not a physical bound.  "
+                                "achieved = int8 multiply-adds issued for the unpadded problem (chains x D(D+1)/2 pairs x M rows x S(S+1)/2 "
+                                "slice products) / measured launch time; fp64_equivalent = the fp64 flops of the same assembly"}
+            elif a_n > 0:
+                a_avg = a_s / a_n
+                achieved = pass_bytes / a_avg
+                if D > 64:  # large-D path: one launch = all block pairs; compute bound (AI above the ridge)
+                    nbk = (D + 63) // 64
+                    tiles = nbk * 10 + (nbk * (nbk + 1) // 2 - nbk) * 16
+                    fl = n * (M / 4.0) * tiles * 2048.0
+                    roof = {"bound": "mfma", "kernel": "k_assemble_pair (X' diag(v) X, one wave per (chain, 64-column block pair), fp64 MFMA)",
+                            "achieved": fl / a_avg / 1e12, "peak": FP64_MFMA_PEAK / 1e12, "unit": "TFLOP/s", "frac": fl / a_avg / FP64_MFMA_PEAK,
+                            "traffic": None, "avg_launch_ms": a_avg * 1e3, "launches": a_n,
+                            "alg_hbm_gbs": achieved / 1e9, "survey8d_streaming_model_frac_NOT_A_BOUND": (value / world) * bytes_step / HBM_PEAK,
+                            "step_fp64_frac": (value / world) * flops_step / FP64_MFMA_PEAK,
+                            "note": "achieved = MFMA flops issued by one assembly launch (all block pairs) / measured launch time"}
+                else:
+                    nb16 = (D + 15) // 16
+                    fl = n * (M / 4.0) * (nb16 * (nb16 + 1) // 2) * 2048.0
+                    roof = {"bound": "hbm", "kernel": "k_assemble (X' diag(v) X on fp64 MFMA)", "achieved": achieved / 1e9,
+                            "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": achieved / HBM_PEAK, "traffic": None,
+                            "avg_launch_ms": a_avg * 1e3, "launches": a_n,
+                            "mfma_tflops": fl / a_avg / 1e12, "mfma_frac": fl / a_avg / FP64_MFMA_PEAK,
+                            "survey8d_streaming_model_frac_NOT_A_BOUND": (value / world) * bytes_step / HBM_PEAK,
+                            "step_fp64_frac": (value / world) * flops_step / FP64_MFMA_PEAK,
+                            "note": "achieved = algorithmic bytes (8*M*D per chain per pass) / measured launch time; X is shared by all "
+                                    "chains and cache resident, so DRAM traffic is far below the algorithmic bytes (see DESIGN.md)"}
+                pmc = os.path.join(ROOT, "profiles", "traffic_%s.json" % args.workload)
+                if os.path.exists(pmc):
+                    roof["traffic"] = json.load(open(pmc)).get("assemble_bytes_per_launch")
+            if roof is not None and kt["assemble_i8"][1] > 0:
+                pmc = os.path.join(ROOT, "profiles", "traffic_%s.json" % args.workload)
+                if os.path.exists(pmc):
+                    roof["traffic"] = json.load(open(pmc)).get("assemble_i8_x%d_bytes_per_launch" % args.i8_slices)
         out = {
             "metric": "leapfrog-steps/sec (whole node)", "value": value, "unit": "leapfrog-steps/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
@@ -426,21 +463,22 @@ def main():
                                            "RMHMC_FLAG_INT8_INNER_FULL = 6 everywhere, see alternates.int8_x6_inner_full)" if args.i8_slices == 6 else ""))
                        if args.i8_slices else "fp64",
                        "int8_error_certificate": i8_bound if i8_bound > 0 else None, "parallelism": "chains sharded over %d GPU(s), no data-path collective" % world},
-            "roofline": roof,
-            "kernel_seconds": {k: {"seconds": v[0], "launches": v[1]} for k, v in kt.items()},
-            "kernel_seconds_from": "un-timed repetition of the same %d steps with HIP events around every launch (%.1f ms per step there; the "
-                                   "timed region itself runs the hipGraph path without events)" % (args.steps, (tk1 - tk0) / args.steps * 1e3),
             "all_finite": finite, "acceptance_rate": acc_rate, "gathered_chains": gathered_chains,
         }
+        if args.full:
+            out["roofline"] = roof
+            out["kernel_seconds"] = {k: {"seconds": v[0], "launches": v[1]} for k, v in kt.items()}
+            out["kernel_seconds_from"] = ("un-timed repetition of the same %d steps with HIP events around every launch (%.1f ms per step there; the "
+                                          "timed region itself runs the hipGraph path without events)" % (args.steps, (tk1 - tk0) / args.steps * 1e3))
         if roof is not None and roof.get("traffic") is not None:
             roof["traffic_source"] = "profiles/traffic_%s.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command (per launch)" % args.workload
         if ess is not None:
             out["min_ess"] = ess
             out["min_ess_per_sec"] = ess["min_ess_per_sec"]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(XX, t, flags, L, eps, K)
     ctx.close()
-    if rank == 0:
+    if rank == 0 and args.full:
         big = 8 < D <= 256 and n * float(M) * D * D >= 1e9
 
         def run_variant(sl, steps, timing, extra=0, burn=None):
@@ -491,6 +529,7 @@ def main():
             if "roofline_fp64" in out:
                 alts["fp64_mfma"] = {"value": out["roofline_fp64"]["value"], "ms_per_step": out["roofline_fp64"]["ms_per_step"]}
             out["alternates"] = alts
+    if rank == 0:
         print(json.dumps(out))
     if world > 1 or force_dist:
         dist.destroy_process_group()

@@ -34,7 +34,7 @@ def _run_bench(extra, nproc=1, env_extra=None, timeout=600):
 def test_bench_two_ranks_gloo():
     """`bench.py --gpus 2` under torch.distributed.run with BENCH_BACKEND=gloo: both ranks run their shard (global chain ids
     rank*n ...), the barrier / max-over-ranks timing and the write-out gather see 2 ranks, rank 0 reports the whole job."""
-    out = _run_bench(["--steps", "4", "--warmup", "1", "--workload", "c2", "--ess-iters", "20", "--no-cpu-baseline", "--no-alternates"],
+    out = _run_bench(["--full", "--steps", "4", "--warmup", "1", "--workload", "c2", "--ess-iters", "20", "--no-cpu-baseline", "--no-alternates"],
                      nproc=2, env_extra={"BENCH_BACKEND": "gloo"})
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["steps"] == 4
     assert out["config"]["chains_total"] == 2 * out["config"]["chains_per_gpu"] == 2048
@@ -47,7 +47,7 @@ def test_bench_two_ranks_gloo():
 def test_bench_four_ranks_gloo_small_shards():
     """The rank count rehearsed beyond two (the GPU box allows at most 6 processes on its card, so 4 ranks stand in for config 4's 8):
     `bench.py --gpus 4 --chains 128`, gloo collectives, every rank's shard on the one GPU; global chain ids rank*128.., one gather."""
-    out = _run_bench(["--steps", "3", "--warmup", "1", "--workload", "c2", "--chains", "128", "--ess-iters", "10", "--no-cpu-baseline",
+    out = _run_bench(["--full", "--steps", "3", "--warmup", "1", "--workload", "c2", "--chains", "128", "--ess-iters", "10", "--no-cpu-baseline",
                       "--no-alternates", "--option", "inflight=16"], nproc=4, env_extra={"BENCH_BACKEND": "gloo"})
     assert out["n_gpus"] == 4 and out["config"]["chains_total"] == 512 and out["gathered_chains"] == 512 and out["all_finite"]
     assert out["config"]["options"]["inflight"] == 16 and out["config"]["options"]["graph"] == 1
@@ -95,9 +95,28 @@ def test_sample_sharded_hip_library_under_gloo(hip, tmp_path, gather):
         assert np.allclose(g["mean"], smp.mean(1), rtol=1e-12, atol=1e-14) and g["min_ess"].shape == (7,)
 
 
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain run (no --full) prints the headline only; --dump-outputs writes the chain state of the timed path's last step, the
+    same for two runs with the same arguments."""
+    common = ["--steps", "3", "--warmup", "1", "--workload", "c2", "--chains", "256"]
+    a = _run_bench(common + ["--dump-outputs", str(tmp_path / "a")])
+    b = _run_bench(common + ["--dump-outputs", str(tmp_path / "b")])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in a, k
+    assert a["steps"] == 3 and abs(a["value"] - 256 * 3 / (a["ms_per_step"] * 3e-3)) < 1e-6 * a["value"]
+    for k in ("roofline", "kernel_seconds", "min_ess", "cpu_baseline", "alternates"):
+        assert k not in a, k
+    d = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in ("theta", "iters", "accepted")}
+    assert d["theta"].shape == (256, 8) and d["iters"].shape == d["accepted"].shape == (256,)
+    assert all(v.dtype == np.float64 for v in d.values()) and np.isfinite(d["theta"]).all()
+    assert abs(d["accepted"].sum() / d["iters"].sum() - a["acceptance_rate"]) < 1e-12
+    for k, v in d.items():
+        assert np.array_equal(v, np.load(str(tmp_path / "b" / (k + ".npy")))), k
+
+
 def test_bench_default_line_shape():
-    """The N = 1 line on a small workload: every object the measurement contract names is present and self-consistent."""
-    out = _run_bench(["--steps", "3", "--warmup", "1", "--workload", "c1", "--ess-iters", "30"])
+    """The N = 1 --full line on a small workload: every object the measurement contract names is present and self-consistent."""
+    out = _run_bench(["--full", "--steps", "3", "--warmup", "1", "--workload", "c1", "--ess-iters", "30"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline", "min_ess", "min_ess_per_sec"):
         assert k in out, k
@@ -235,7 +254,7 @@ def test_bench_one_rank_rccl():
     and rmhmc_sample_stats_dev."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", BENCH_FORCE_DIST="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", "29653", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--workload", "c2",
+           "--master-port", "29653", os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "4", "--warmup", "1", "--workload", "c2",
            "--ess-iters", "20", "--no-cpu-baseline", "--no-alternates"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
