@@ -228,11 +228,20 @@ int rmhmc_chains_state(rmhmc_ctx *ctx, double *w_out, int64_t *iters_out,
 /* Checkpoint / resume: (w, iters, accepted) from rmhmc_chains_state is a complete checkpoint.  To resume, call
  * rmhmc_chains_init with theta0 = the saved w (same seed, chain_offset, L, eps, K) and then this function with the
  * saved counters.  Randomness is keyed by (seed, chain, iteration), so a chain that was in mid-trajectory replays
- * that transition from its start and every chain continues bit for bit as if it had never stopped.          */
+ * that transition from its start and every chain continues bit for bit as if it had never stopped - except on the
+ * int8 path with its delta assembly (6 slices, option i8_delta, the default there): the uninterrupted run carries the
+ * metric at a chain's position forward as G(last position iterate) + the assembly of the difference, the resumed run
+ * assembles it in full from w, one fp64 rounding apart, so resumed transitions agree to the last bits only (3.8e-15
+ * relative at BASELINE config 3, tests/test_gpu_timed_path.py).  With i8_delta = 0 it is bit for bit there as well. */
 int rmhmc_chains_restore(rmhmc_ctx *ctx, const int64_t *iters, const int64_t *accepted);
 /* Device seconds (HIP events on the library's stream) of the kernel named
  * `which` accumulated since the last rmhmc_chains_init, and its launch
- * count; which = "assemble" | "factor" | "momentum" | "leverage" | "total". */
+ * count; which = "assemble" | "factor" | "momentum" | "leverage" | "total".
+ * The int8 path at 6 slices also counts its delta assemblies (option i8_delta: the metric as the previous iterate's G plus the assembly
+ * of the v differences, summed from as few slices S' as the batch's largest difference needs) by the S' the kernels picked on the
+ * device, whether timing is on or not: which = "i8_delta_end_s4" | "_s5" | "_s6" (the evaluation at the end of a leapfrog step) and
+ * "i8_delta_inner_s4" | "_s5" (the second position iterate, five-slice accuracy) give that count in launches_out and 0 seconds.  The
+ * results do not depend on S' (no digit is lost); the counts let a test see which arithmetic ran.                                 */
 int rmhmc_kernel_time(rmhmc_ctx *ctx, const char *which, double *seconds_out,
                       int64_t *launches_out);
 
@@ -303,6 +312,7 @@ int rmhmc_set_progress(rmhmc_ctx *ctx, rmhmc_progress_fn fn, int64_t first, int6
  * are in use, 0 when the path was not requested or RMHMC_FLAG_INT8_CERTIFY sent this data set to the fp64 kernels.  The oracle
  * reports (0, 0).                                                                                                          */
 int rmhmc_int8_certificate(rmhmc_ctx *ctx, double *bound_out, int32_t *active_out);
+
 
 /* ---- device-resident write-out ("one RCCL gather over xGMI at sample write-out") -----------------------
  * The same calls as rmhmc_chains_state / rmhmc_sample / rmhmc_sample_stats with every OUTPUT ARRAY in DEVICE memory of the

@@ -407,6 +407,12 @@ class Context:
         self._ck(self.lib.rmhmc_int8_certificate(self._h, C.cast(C.byref(b), _dp), C.cast(C.byref(a), _ip)))
         return b.value, bool(a.value)
 
+    def i8_delta_counts(self):
+        """delta assemblies of the int8 path since chains_init, by the slice count S' the device picked (rmhmc_kernel_time,
+        include/rmhmc.h): {"end": [S'=4, S'=5, S'=6], "inner": [S'=4, S'=5]}"""
+        return {"end": [self.kernel_time("i8_delta_end_s%d" % s)[1] for s in (4, 5, 6)],
+                "inner": [self.kernel_time("i8_delta_inner_s%d" % s)[1] for s in (4, 5)]}
+
     def kernel_time(self, which):
         s = C.c_double(0.0); k = C.c_int64(0)
         self._ck(self.lib.rmhmc_kernel_time(self._h, which.encode(), C.cast(C.byref(s), _dp), C.cast(C.byref(k), _lp)))

@@ -591,6 +591,7 @@ struct I8Delta {
   double cscale;
   int need_lo, need_hi;            // this launch does the work when the digits the maximum needs lie in [need_lo, need_hi]
   const double* Gbase;             // the matrix that is added to (null: Gq itself; the large-D path factors Gq in place and keeps a copy)
+  unsigned long long* count = nullptr;  // delta assemblies by the slice count they used (rmhmc_kernel_time); set on ONE launch of each
   __device__ __forceinline__ bool skip() const;
 };
 // S' balanced digits hold |N| <= 127 (256^S' - 1) / 255 = 0.498 256^S'
@@ -681,12 +682,17 @@ __device__ __forceinline__ int i8_delta_pick(const I8Delta& dl, int seff) {
   const int need = i8_delta_slices(*dl.dsel);
   return seff == 6 ? need : (need == 6 ? 5 : 4);
 }
+// one count per delta assembly: lane 0 of workgroup (0, 0) of the launch that carries dl.count adds 1 to count[3 (6 - seff) + S' - 4]
+__device__ __forceinline__ void i8_delta_count(const I8Delta& dl, int seff, int Sp) {
+  if (dl.count && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(dl.count + 3 * (6 - seff) + (Sp - 4), 1ull);
+}
 template <int WN, int TN>
 __global__ __launch_bounds__(128 * WN) __attribute__((amdgpu_waves_per_eu(WN / 2, WN / 2))) void k_assemble_i8_sel(const int8_t* __restrict__ Vs, size_t vplane, int seff, const int8_t* __restrict__ Zs, int nCp, int nks_total,
                                                           int ks0, int nk, int accumulate, I8Pairs pr, int n_chains, const int* __restrict__ phase,
                                                           const int* __restrict__ vbad, int DP, double inv_alpha, double* __restrict__ Gq,
                                                           size_t plane_stride, const int* __restrict__ vexp, int npb, I8Delta dl) {
   const int Sp = i8_delta_pick(dl, seff);
+  i8_delta_count(dl, seff, Sp);
   dl.cscale = __builtin_ldexp(1.0, -8 * (seff - Sp));
   Vs += (size_t)(seff - Sp) * vplane;
   if (Sp == 6) assemble_i8_body<6, WN, TN>(Vs, Zs, nCp, nks_total, ks0, nk, accumulate, pr, n_chains, phase, vbad, DP, inv_alpha, Gq, plane_stride, vexp, npb, dl);
@@ -734,6 +740,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     const int8_t* __restrict__ Vs, size_t vplane, int seff, const int8_t* __restrict__ Zs, int nCp, int NPp, int NP, int nks_total, int ks0, int nk,
     int n_chains, int pb32_0, int ntail, int* __restrict__ Tq, I8Delta dl) {
   const int Sp = i8_delta_pick(dl, seff);
+  i8_delta_count(dl, seff, Sp);
   Vs += (size_t)(seff - Sp) * vplane;
   if (Sp == 6) assemble_i8_tail_body<6>(Vs, Zs, nCp, NPp, NP, nks_total, ks0, nk, n_chains, pb32_0, ntail, Tq);
   else if (Sp == 5) assemble_i8_tail_body<5>(Vs, Zs, nCp, NPp, NP, nks_total, ks0, nk, n_chains, pb32_0, ntail, Tq);

@@ -52,6 +52,7 @@ struct Group {
   int* vbad = nullptr;
   int* vexp = nullptr;   // per-chain extra binary digits of the v grid (VSlice)
   int* vexp_d = nullptr; int* rebase = nullptr; unsigned long long* dmax = nullptr;  // delta assembly (VSlice / I8Delta)
+  unsigned long long* dcount = nullptr;  // [6] delta assemblies by slice count (I8Delta::count, rmhmc_kernel_time "i8_delta_*"; zeroed by chains_init)
   double* Gbase = nullptr;  // large-D path: copy of the G a delta assembly adds to (Gq is factored in place)
   d4* ctile = nullptr;   // c = v(1-2p) of trj.w in the tile layout of k_mompass, [ceil(n/16)][Mp/16][64] x 4 doubles
   int nCp = 0;
@@ -368,15 +369,19 @@ void launch_assemble_i8_delta(rmhmc_ctx* ctx, Group& g, hipStream_t st, int seff
   const int pb32_0 = nPBfull * TN * WN, ntail = (ctx->pairs.NP - pb32_0 * 32 + 31) / 32;
   constexpr int lds_t = i8_lds_bytes<6, 1, 1>() > i8_lds_bytes<4, 1, 1>() ? i8_lds_bytes<6, 1, 1>() : i8_lds_bytes<4, 1, 1>();
   static_assert(lds_t >= (i8_lds_bytes<5, 1, 1>()), "dynamic LDS of the widest tail instantiation");
+  // the assembly is counted once (g.dcount): by the first k piece's main launch, or by its tail launch when there are no main tiles
+  I8Delta dlc = dl;
+  dlc.count = g.dcount;
   for (int ks0 = 0; ks0 < ctx->i8_nks; ks0 += ctx->i8_chunk) {
     const int nk = std::min(ctx->i8_chunk, ctx->i8_nks - ks0);
     if (nblk_main)
       hipLaunchKernelGGL((k_assemble_i8_sel<WN, TN>), dim3(nblk_main), dim3(128 * WN), lds, st, g.Vs, vplane, seff, ctx->d_Zs, g.nCp, ctx->i8_nks, ks0, nk,
-                         (ks0 > 0 ? 1 : 0) | 2, ctx->pairs, g.n, g.ch.phase, g.vbad, ctx->DP, ctx->dd.inv_alpha, g.ch.Gq, (size_t)0, g.vexp_d, npb, dl);
+                         (ks0 > 0 ? 1 : 0) | 2, ctx->pairs, g.n, g.ch.phase, g.vbad, ctx->DP, ctx->dd.inv_alpha, g.ch.Gq, (size_t)0, g.vexp_d, npb,
+                         ks0 == 0 ? dlc : dl);
     if (tail) {
       const int pieces = std::max(1, std::min({g.tail_pieces, nk / 8, (int)(256 / std::max(1, nCB * ntail))}));
       hipLaunchKernelGGL(k_assemble_i8_tail_sel, dim3((unsigned)(nCB * ntail), (unsigned)pieces), dim3(128), lds_t, st, g.Vs, vplane, seff, ctx->d_Zs,
-                         g.nCp, ctx->pairs.NPp, ctx->pairs.NP, ctx->i8_nks, ks0, nk, g.n, pb32_0, ntail, g.Tq, dl);
+                         g.nCp, ctx->pairs.NPp, ctx->pairs.NP, ctx->i8_nks, ks0, nk, g.n, pb32_0, ntail, g.Tq, (ks0 == 0 && !nblk_main) ? dlc : dl);
       hipLaunchKernelGGL(k_assemble_i8_tailsum_sel, dim3((unsigned)(((size_t)g.n * 32 * ntail + 255) / 256)), dim3(256), 0, st, seff, g.Tq, pieces, g.nCp, ntail,
                          pb32_0, (ks0 > 0 ? 1 : 0) | 2, ctx->pairs, g.n, g.ch.phase, g.vbad, ctx->DP, ctx->dd.inv_alpha, g.ch.Gq, g.vexp_d, dl);
     }
@@ -1076,6 +1081,7 @@ int rmhmc_create_opts(rmhmc_ctx** out, int32_t device_id, int64_t M, int32_t D, 
         RC(dalloc(ctx, &g.vbad, (size_t)g.nCp));
         RC(dalloc(ctx, &g.vexp, (size_t)g.nCp));
         RC(dalloc(ctx, &g.vexp_d, (size_t)g.nCp)); RC(dalloc(ctx, &g.rebase, (size_t)g.nCp)); RC(dalloc(ctx, &g.dmax, (size_t)1));
+        RC(dalloc(ctx, &g.dcount, (size_t)6));  // (before any graph is captured: every delta launch carries the pointer)
         if (!ctx->big) { g.ch.i8_vbad = g.vbad; g.ch.i8_dmax = g.dmax; }
         if (ctx->big && ctx->opt.i8_delta && S == 6) RC(dalloc(ctx, &g.Gbase, (size_t)g.n * ctx->DP * ctx->DP));
         RC(dalloc(ctx, &g.Qs, (size_t)S * ctx->i8_nkp * g.nCp * 32));
@@ -2012,6 +2018,8 @@ int rmhmc_chains_init(rmhmc_ctx* ctx, const double* theta0, uint64_t seed, int64
   if (L < 1 || K < 1) return fail(ctx, RMHMC_ERR_INVALID, "chains_init: L >= 1 and K >= 1 required");
   ctx->L = L; ctx->eps = eps; ctx->K = K; ctx->seed = seed; ctx->chain_offset = chain_offset;
   RC(init_chains(ctx, theta0));
+  for (Group& g : ctx->groups)
+    if (g.dcount) HIPCK(hipMemsetAsync(g.dcount, 0, 6 * sizeof(unsigned long long), ctx->stream));
   ctx->chains_ready = true;
   return RMHMC_OK;
 }
@@ -2089,6 +2097,18 @@ int rmhmc_kernel_time(rmhmc_ctx* ctx, const char* which, double* seconds_out, in
     return RMHMC_OK;
   }
   RC(sync(ctx));
+  if (w.rfind("i8_delta_", 0) == 0) {  // delta assemblies by slice count (I8Delta::count): [3 (6 - seff) + S' - 4]
+    static const char* const names[5] = {"i8_delta_end_s4", "i8_delta_end_s5", "i8_delta_end_s6", "i8_delta_inner_s4", "i8_delta_inner_s5"};
+    const int slot = (int)(std::find_if(names, names + 5, [&](const char* s) { return w == s; }) - names);
+    if (slot == 5) return fail(ctx, RMHMC_ERR_INVALID, "kernel_time: unknown delta counter " + w);
+    for (const Group& g : ctx->groups) {
+      if (!g.dcount) continue;
+      unsigned long long h = 0;
+      HIPCK(hipMemcpy(&h, g.dcount + slot, sizeof(h), hipMemcpyDeviceToHost));
+      if (launches_out) *launches_out += (int64_t)h;
+    }
+    return RMHMC_OK;
+  }
   auto it = ctx->events.find(w);
   if (it == ctx->events.end()) return RMHMC_OK;
   double ms = 0.0;

@@ -6,7 +6,7 @@
 #   2. PMC passes, one counter group per run (separate runs, as MI355X_MICROARCH.md prescribes; never together with a trace), ONE
 #      timed step from the same checkpoint each:
 #      FETCH_SIZE | WRITE_SIZE | SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE | SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT
-# So every duration, cycle count and byte count is of a launch on chains at stationarity (resume is bit exact).  All profiled runs pass
+# So every duration, cycle count and byte count is of a launch on chains at stationarity (resume is exact to the last bits, include/rmhmc.h).  All profiled runs pass
 # --no-graph: hipGraph replay under rocprofv3's queue interceptor faults in librocprofiler-sdk 7.2 (tools/rocprof_queue_repro.hip, DESIGN
 # section 6); the kernels and their order are the same, the launches just reach the queue one by one.
 # Summaries are written by tools/summarize_profile.py into gpurun_out/prof_<tag>/ and copied to profiles/ (committed).
