@@ -108,6 +108,14 @@ SIGNATURES = {
                                    _lp, _lp, _dp]),
 }
 
+# include/rmhmc_amh.h: the adaptive Metropolis sampler, exported by the HIP library only (not by the CPU oracle), so bound apart from
+# SIGNATURES and only where the library has it
+_i8p = C.POINTER(C.c_int8)
+AMH_SIGNATURES = {
+    "rmhmc_amh_sample": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_int64, _dp, _dp, _lp, _dp, _dp]),
+    "rmhmc_amh_replay": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _i8p]),
+}
+
 
 class RmhmcError(RuntimeError):
     def __init__(self, code, msg):
@@ -138,6 +146,12 @@ class RmhmcLib:
             fn = getattr(self.lib, name)  # AttributeError if a declared symbol is missing
             fn.restype = res
             fn.argtypes = args
+        self.has_amh = all(hasattr(self.lib, name) for name in AMH_SIGNATURES)
+        if self.has_amh:
+            for name, (res, args) in AMH_SIGNATURES.items():
+                fn = getattr(self.lib, name)
+                fn.restype = res
+                fn.argtypes = args
         # the HIP library writes its _dev outputs through device pointers of its own GPU; the CPU oracle's "device" is the host
         self.on_gpu = "gfx950" in self.version()
 
@@ -372,6 +386,36 @@ class Context:
                                            int(chain_offset), _ptr(th), _ptr(samples), _ptr(acc, _lp), _ptr(steps, _lp),
                                            C.cast(C.byref(secs), _dp)))
         return samples, acc, steps, secs.value
+
+    # ---- adaptive Metropolis (code/metropolis.py, include/rmhmc_amh.h) -----------
+    def _need_amh(self):
+        if not self.rl.has_amh:
+            raise RmhmcError(-4, "%s does not export the AMH sampler (include/rmhmc_amh.h)" % self.rl.path)
+
+    def amh_sample(self, n_iter, burn_in, seed=0, chain_offset=0, theta0=None):
+        """returns (samples [n][n_iter-burn_in][D], accepted proposals [n], final ProposalSD [n][D], seconds after burn-in)"""
+        self._need_amh()
+        n, D = self.n, self.D
+        S = int(n_iter) - int(burn_in)
+        if S <= 0 or int(burn_in) < 0:
+            raise ValueError("need 0 <= BurnIn < NumOfIterations")
+        th = None if theta0 is None else _f64(np.broadcast_to(theta0, (n, D)))
+        samples = np.empty((n, S, D)); acc = np.zeros(n, dtype=np.int64); sd = np.empty((n, D)); secs = C.c_double(0.0)
+        self._ck(self.lib.rmhmc_amh_sample(self._h, int(n_iter), int(burn_in), int(seed), int(chain_offset), _ptr(th), _ptr(samples),
+                                           _ptr(acc, _lp), _ptr(sd), C.cast(C.byref(secs), _dp)))
+        return samples, acc, sd, secs.value
+
+    def amh_replay(self, n_iter, burn_in, z, u, theta0=None):
+        """z, u: [n][n_iter][D] recorded draws (u NaN where none was drawn).  Returns dict(w [n][n_iter][D], ljl [n][n_iter],
+        sd [n][D], accepted / u_read [n][n_iter][D] bool)"""
+        self._need_amh()
+        n, D, T = self.n, self.D, int(n_iter)
+        z = _f64(z, (n, T, D)); u = _f64(u, (n, T, D))
+        th = None if theta0 is None else _f64(np.broadcast_to(theta0, (n, D)))
+        w = np.empty((n, T, D)); ljl = np.empty((n, T)); sd = np.empty((n, D)); dec = np.zeros((n, T, D), dtype=np.int8)
+        self._ck(self.lib.rmhmc_amh_replay(self._h, T, int(burn_in), _ptr(z), _ptr(u), _ptr(th), _ptr(w), _ptr(ljl), _ptr(sd),
+                                           _ptr(dec, _i8p)))
+        return dict(w=w, ljl=ljl, sd=sd, accepted=(dec & 1) != 0, u_read=(dec & 2) != 0)
 
     def chains_init(self, theta0=None, seed=0, chain_offset=0, L=6, eps=0.5, K=4):
         th = None if theta0 is None else _f64(np.broadcast_to(theta0, (self.n, self.D)))

@@ -93,6 +93,8 @@ __device__ __forceinline__ double col4_sum(double x) {
 // Philox4x32-10 counter RNG — same stream specification as oracle/rmhmc_oracle.c:
 // key = seed, counter = (chain lo, chain hi, iteration, block); blocks 0..ceil(D/2)-1 -> momentum
 // normals (Box-Muller), block 0x40000000 -> (u_len, u_acc), block 0x40000001 -> g_dir.
+// Adaptive Metropolis (amh.hip.h; no oracle counterpart): blocks 0x50000000 + d/2 -> proposal normals z_d (Box-Muller, cos for even
+// d, sin for odd), blocks 0x50001000 + d/2 -> acceptance uniforms u_d (U0 for even d, U1 for odd); iteration = IterationNum.
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
 #pragma unroll

@@ -6,11 +6,13 @@
 // asynchronously (k_iter_begin / k_iter_end act only on chains whose trajectory ended) and every
 // chain executes one leapfrog step per "global step" whatever its RandomStep.
 #include "../../include/rmhmc.h"
+#include "../../include/rmhmc_amh.h"
 #include "kernels.hip.h"
 #include "fused_small.hip.h"
 #include "large_d.hip.h"
 #include "metric_i8.hip.h"
 #include "medium_step.hip.h"
+#include "amh.hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -2120,6 +2122,125 @@ int rmhmc_kernel_time(rmhmc_ctx* ctx, const char* which, double* seconds_out, in
   if (seconds_out) *seconds_out = ms * 1e-3;
   if (launches_out) *launches_out = (int64_t)it->second.size();
   return RMHMC_OK;
+}
+
+}  // extern "C"
+
+// ---- adaptive Metropolis (metropolis.py, amh.hip.h) --------------------------------------------------------------------------------
+namespace {
+
+// Block size and rows per thread of k_amh: one wavefront per chain when the batch fills the chip and f fits in 16 registers per lane,
+// a 256-thread workgroup otherwise (short latency per proposal for few chains, room for long data sets); R = 0: f is streamed.
+void amh_shape(const rmhmc_ctx* ctx, int* nt, int* rows) {
+  const long long M = ctx->M;
+  const int NT = (M <= 64 * 16 && ctx->n >= 1024) ? 64 : 256;
+  *nt = NT;
+  *rows = M > AMH_MAX_ONCHIP_ROWS ? 0 : (int)((M + NT - 1) / NT);
+}
+
+// Runs iterations 0..n_iter-1 of every chain in segments (metropolis.py:38-91), p carries the mode.  Progress reports and the timer
+// sit between segments.  A segment ends after at most 1000 iterations, after every reported iteration and after iteration burn_in,
+// the same cuts for any number of chains; its launches are cut by work (AMH_LAUNCH_ROWS), which leaves the results unchanged.
+int amh_run(rmhmc_ctx* ctx, AmhParams p, const double* theta0, double* seconds_out) {
+  const size_t n = ctx->n, D = ctx->D, DP = ctx->DP;
+  Chains& ch = ctx->ch;
+  std::vector<double> h((size_t)n * D, 0.0);
+  RC(upload_vec(ctx, ch.cur.w, theta0 ? theta0 : h.data()));
+  std::fill(h.begin(), h.end(), 1.0);
+  RC(upload_vec(ctx, ch.PM, h.data()));
+  HIPCK(hipMemsetAsync(ch.u0, 0, sizeof(double) * n * DP, ctx->stream));
+  fill_ll(ctx, ch.accepted, 0, n);
+  p.w = ch.cur.w; p.sd = ch.PM; p.accw = ch.u0; p.ljl = ch.cur.ljl; p.accepted = ch.accepted; p.fa = ch.rv0; p.fb = ch.rv2;
+  int NT = 256, R = 0;
+  amh_shape(ctx, &NT, &R);
+  const bool sampling = p.z_in == nullptr;
+  const long long N = p.n_iter, B = p.burn_in;
+  auto t0 = std::chrono::steady_clock::now();
+  for (long long start = 0; start < N;) {
+    long long end = std::min(N, start + 1000);
+    if (start <= B) {
+      end = std::min(end, B + 1);
+      const long long rep = (start + 999) / 1000 * 1000;  // next reported iteration >= start
+      if (rep < B) end = std::min(end, rep + 1);
+    }
+    // the segment [start, end) in launches of at most AMH_LAUNCH_ROWS evaluations each; f is recomputed at the segment's start only
+    const long long per_iter = (long long)n * (long long)D * ctx->M;
+    const long long step = std::max(1LL, AMH_LAUNCH_ROWS / std::max(1LL, per_iter));
+    for (long long a = start; a < end; a += step) {
+      p.it0 = a; p.it1 = std::min(end, a + step); p.carry = a > start ? 1 : 0;
+      AMH_SWITCH(NT, R, hipLaunchKernelGGL((k_amh<NT_, R_>), dim3((unsigned)n), dim3(NT_), 0, ctx->stream, ctx->dd, p));
+      HIPCK(hipGetLastError());
+    }
+    const long long last = end - 1;
+    if (sampling && last <= B) {
+      RC(sync(ctx));
+      if (ctx->progress_fn && last % 1000 == 0 && last < B) ctx->progress_fn(RMHMC_EV_PROGRESS, last, 0, 0, ctx->progress_user);
+      if (last == B) {
+        if (ctx->progress_fn) ctx->progress_fn(RMHMC_EV_BURNIN_DONE, B, 0, 0, ctx->progress_user);
+        t0 = std::chrono::steady_clock::now();
+      }
+    }
+    start = end;
+  }
+  RC(sync(ctx));
+  if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return RMHMC_OK;
+}
+
+bool amh_iters_ok(int64_t n_iter, int64_t burn_in) { return burn_in >= 0 && burn_in < n_iter && n_iter <= (int64_t)0xffffffffLL; }
+
+}  // namespace
+
+extern "C" {
+
+int rmhmc_amh_sample(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, uint64_t seed, int64_t chain_offset, const double* theta0,
+                     double* samples_out, int64_t* accepted_out, double* sd_out, double* seconds_out) {
+  NEED_DATA(ctx);
+  if (!samples_out || !amh_iters_ok(n_iter, burn_in) || chain_offset < 0)
+    return fail(ctx, RMHMC_ERR_INVALID, "amh_sample: need samples_out, 0 <= burn_in < n_iter < 2^32, chain_offset >= 0");
+  ctx->chains_ready = false;
+  const size_t n = ctx->n, D = ctx->D, S = (size_t)(n_iter - burn_in);
+  double* d_samples = nullptr;
+  HIPCK(hipMalloc((void**)&d_samples, sizeof(double) * n * S * D));
+  int rc = [&]() -> int {
+    AmhParams p{};
+    p.samples = d_samples; p.seed = seed; p.chain_offset = chain_offset; p.n_iter = n_iter; p.burn_in = burn_in;
+    RC(amh_run(ctx, p, theta0, seconds_out));
+    HIPCK(hipMemcpyAsync(samples_out, d_samples, sizeof(double) * n * S * D, hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<long long> a(n);
+    RC(download(ctx, a.data(), ctx->ch.accepted, n));
+    if (sd_out) RC(download_vec(ctx, sd_out, ctx->ch.PM));
+    RC(sync(ctx));
+    if (accepted_out) for (size_t c = 0; c < n; ++c) accepted_out[c] = a[c];
+    return RMHMC_OK;
+  }();
+  (void)hipFree(d_samples);
+  return rc;
+}
+
+int rmhmc_amh_replay(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, const double* z, const double* u, const double* theta0,
+                     double* w_out, double* ljl_out, double* sd_out, int8_t* decisions_out) {
+  NEED_DATA(ctx);
+  if (!z || !u || !w_out || !ljl_out || !decisions_out || !amh_iters_ok(n_iter, burn_in))
+    return fail(ctx, RMHMC_ERR_INVALID, "amh_replay: need z, u, w_out, ljl_out, decisions_out and 0 <= burn_in < n_iter < 2^32");
+  ctx->chains_ready = false;
+  const size_t n = ctx->n, D = ctx->D, T = (size_t)n_iter, vec = n * T * D;
+  double *d_z = nullptr, *d_u = nullptr, *d_w = nullptr, *d_l = nullptr;
+  int8_t* d_dec = nullptr;
+  int rc = [&]() -> int {
+    HIPCK(hipMalloc((void**)&d_z, sizeof(double) * vec)); HIPCK(hipMalloc((void**)&d_u, sizeof(double) * vec));
+    HIPCK(hipMalloc((void**)&d_w, sizeof(double) * vec)); HIPCK(hipMalloc((void**)&d_l, sizeof(double) * n * T));
+    HIPCK(hipMalloc((void**)&d_dec, vec));
+    RC(upload(ctx, d_z, z, vec)); RC(upload(ctx, d_u, u, vec));
+    AmhParams p{};
+    p.z_in = d_z; p.u_in = d_u; p.w_out = d_w; p.ljl_out = d_l; p.dec_out = d_dec; p.n_iter = n_iter; p.burn_in = burn_in;
+    RC(amh_run(ctx, p, theta0, nullptr));
+    RC(download(ctx, w_out, d_w, vec)); RC(download(ctx, ljl_out, d_l, n * T)); RC(download(ctx, decisions_out, d_dec, vec));
+    if (sd_out) RC(download_vec(ctx, sd_out, ctx->ch.PM));
+    return sync(ctx);
+  }();
+  for (void* q : {(void*)d_z, (void*)d_u, (void*)d_w, (void*)d_l, (void*)d_dec}) if (q) (void)hipFree(q);
+  return rc;
 }
 
 }  // extern "C"

@@ -18,10 +18,11 @@ import numpy as np
 
 from . import tools
 from .hmc import HMC
+from .metropolis import AMH
 from .mmala import mMALA
 from .rmhmc import RMHMC
 
-SAMPLERS = {"RMHMC": RMHMC, "HMC": HMC, "mMALA": mMALA}
+SAMPLERS = {"RMHMC": RMHMC, "HMC": HMC, "mMALA": mMALA, "AMH": AMH}
 
 
 def summarize(results_beta, results_time, nfft="python"):
