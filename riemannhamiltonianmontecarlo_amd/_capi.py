@@ -115,6 +115,11 @@ AMH_SIGNATURES = {
     "rmhmc_amh_sample": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_int64, _dp, _dp, _lp, _dp, _dp]),
     "rmhmc_amh_replay": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _i8p]),
 }
+# include/rmhmc_iwls.h: the IWLS Metropolis-Hastings sampler, HIP library only as well
+IWLS_SIGNATURES = {
+    "rmhmc_iwls_sample": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_uint64, C.c_int64, _dp, _dp, _lp, _lp, _dp]),
+    "rmhmc_iwls_replay": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _i8p]),
+}
 
 
 class RmhmcError(RuntimeError):
@@ -149,6 +154,12 @@ class RmhmcLib:
         self.has_amh = all(hasattr(self.lib, name) for name in AMH_SIGNATURES)
         if self.has_amh:
             for name, (res, args) in AMH_SIGNATURES.items():
+                fn = getattr(self.lib, name)
+                fn.restype = res
+                fn.argtypes = args
+        self.has_iwls = all(hasattr(self.lib, name) for name in IWLS_SIGNATURES)
+        if self.has_iwls:
+            for name, (res, args) in IWLS_SIGNATURES.items():
                 fn = getattr(self.lib, name)
                 fn.restype = res
                 fn.argtypes = args
@@ -416,6 +427,39 @@ class Context:
         self._ck(self.lib.rmhmc_amh_replay(self._h, T, int(burn_in), _ptr(z), _ptr(u), _ptr(th), _ptr(w), _ptr(ljl), _ptr(sd),
                                            _ptr(dec, _i8p)))
         return dict(w=w, ljl=ljl, sd=sd, accepted=(dec & 1) != 0, u_read=(dec & 2) != 0)
+
+    # ---- IWLS Metropolis-Hastings (code/iwls.py, include/rmhmc_iwls.h) ----------
+    def _need_iwls(self):
+        if not self.rl.has_iwls:
+            raise RmhmcError(-4, "%s does not export the IWLS sampler (include/rmhmc_iwls.h)" % self.rl.path)
+
+    def iwls_sample(self, n_iter, burn_in, compat=True, seed=0, chain_offset=0, theta0=None):
+        """returns (samples [n][n_iter-burn_in][D], accepted proposals [n], saturated proposals [n], seconds from iteration burn_in)"""
+        self._need_iwls()
+        n, D = self.n, self.D
+        S = int(n_iter) - int(burn_in)
+        if S <= 0 or int(burn_in) < 0:
+            raise ValueError("need 0 <= burn_in < max_iter")
+        th = None if theta0 is None else _f64(np.broadcast_to(theta0, (n, D)))
+        samples = np.empty((n, S, D)); acc = np.zeros(n, dtype=np.int64); sat = np.zeros(n, dtype=np.int64); secs = C.c_double(0.0)
+        self._ck(self.lib.rmhmc_iwls_sample(self._h, int(n_iter), int(burn_in), 1 if compat else 0, int(seed), int(chain_offset), _ptr(th),
+                                            _ptr(samples), _ptr(acc, _lp), _ptr(sat, _lp), C.cast(C.byref(secs), _dp)))
+        return samples, acc, sat, secs.value
+
+    def iwls_replay(self, w_prop, u, compat=True, theta0=None):
+        """w_prop [n][T][D] given proposals, u [n][T] uniforms (NaN where none was drawn).  Returns dict(w, mean [n][T][D], ljl,
+        ratio [n][T] after every iteration, accepted / u_read / saturated [n][T] bool)"""
+        self._need_iwls()
+        n, D = self.n, self.D
+        w_prop = _f64(w_prop)
+        T = w_prop.size // (n * D)
+        w_prop = w_prop.reshape(n, T, D); u = _f64(u, (n, T))
+        th = None if theta0 is None else _f64(np.broadcast_to(theta0, (n, D)))
+        w = np.empty((n, T, D)); mean = np.empty((n, T, D)); ljl = np.empty((n, T)); ratio = np.empty((n, T))
+        dec = np.zeros((n, T), dtype=np.int8)
+        self._ck(self.lib.rmhmc_iwls_replay(self._h, T, 1 if compat else 0, _ptr(w_prop), _ptr(u), _ptr(th), _ptr(w), _ptr(mean), _ptr(ljl),
+                                            _ptr(ratio), _ptr(dec, _i8p)))
+        return dict(w=w, mean=mean, ljl=ljl, ratio=ratio, accepted=(dec & 1) != 0, u_read=(dec & 2) != 0, saturated=(dec & 4) != 0)
 
     def chains_init(self, theta0=None, seed=0, chain_offset=0, L=6, eps=0.5, K=4):
         th = None if theta0 is None else _f64(np.broadcast_to(theta0, (self.n, self.D)))

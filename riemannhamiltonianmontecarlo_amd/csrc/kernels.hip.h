@@ -95,6 +95,8 @@ __device__ __forceinline__ double col4_sum(double x) {
 // normals (Box-Muller), block 0x40000000 -> (u_len, u_acc), block 0x40000001 -> g_dir.
 // Adaptive Metropolis (amh.hip.h; no oracle counterpart): blocks 0x50000000 + d/2 -> proposal normals z_d (Box-Muller, cos for even
 // d, sin for odd), blocks 0x50001000 + d/2 -> acceptance uniforms u_d (U0 for even d, U1 for odd); iteration = IterationNum.
+// IWLS Metropolis-Hastings (iwls.hip.h; no oracle counterpart) reuses the streams above: proposal normals z from draw_normals (blocks
+// d/2, Box-Muller), acceptance uniform U1 of block 0x40000000; iteration = i, key (seed, chain_offset + c).
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
 #pragma unroll

@@ -7,12 +7,14 @@
 // chain executes one leapfrog step per "global step" whatever its RandomStep.
 #include "../../include/rmhmc.h"
 #include "../../include/rmhmc_amh.h"
+#include "../../include/rmhmc_iwls.h"
 #include "kernels.hip.h"
 #include "fused_small.hip.h"
 #include "large_d.hip.h"
 #include "metric_i8.hip.h"
 #include "medium_step.hip.h"
 #include "amh.hip.h"
+#include "iwls.hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -2240,6 +2242,186 @@ int rmhmc_amh_replay(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, const doub
     return sync(ctx);
   }();
   for (void* q : {(void*)d_z, (void*)d_u, (void*)d_w, (void*)d_l, (void*)d_dec}) if (q) (void)hipFree(q);
+  return rc;
+}
+
+}  // extern "C"
+
+// ---- IWLS Metropolis-Hastings (iwls.py, iwls.hip.h) --------------------------------------------------------------------------------
+namespace {
+
+const char* const kIwlsDMsg = "iwls: D > 64 is not supported (64 < D <= 256 needs a blocked factorisation of G^-1 + 1e-6 I)";
+
+// device state of one IWLS call: l() of cur / trj ([2][n]), the saturated flag and count, m(cur.w)
+struct IwlsState {
+  double* lq = nullptr;
+  int* sat = nullptr;
+  long long* nsat = nullptr;
+  double* mcur = nullptr;
+};
+
+int iwls_alloc(rmhmc_ctx* ctx, IwlsState& s, IwlsParams& p, int32_t compat) {
+  const size_t n = ctx->n;
+  HIPCK(hipMalloc((void**)&s.lq, sizeof(double) * 2 * n));
+  HIPCK(hipMalloc((void**)&s.sat, sizeof(int) * n));
+  HIPCK(hipMalloc((void**)&s.nsat, sizeof(long long) * n));
+  HIPCK(hipMalloc((void**)&s.mcur, sizeof(double) * n * ctx->DP));
+  HIPCK(hipMemsetAsync(s.lq, 0, sizeof(double) * 2 * n, ctx->stream));
+  HIPCK(hipMemsetAsync(s.nsat, 0, sizeof(long long) * n, ctx->stream));
+  p.compat = compat ? 1 : 0;
+  p.lq_cur = s.lq; p.lq_trj = s.lq + n; p.sat = s.sat; p.nsat = s.nsat; p.mcur = s.mcur;
+  return RMHMC_OK;
+}
+void iwls_free(IwlsState& s) {
+  for (void* q : {(void*)s.lq, (void*)s.sat, (void*)s.nsat, (void*)s.mcur}) if (q) (void)hipFree(q);
+}
+
+// the parameters of chains [g.off, g.off + g.n)
+IwlsParams iwls_view(const rmhmc_ctx* ctx, const Group& g, IwlsParams p) {
+  const size_t off = (size_t)g.off, D = ctx->D;
+  p.chain_offset += g.off;
+  if (p.samples) p.samples += off * p.S * D;
+  if (p.w_prop) { p.w_prop += off * p.T * D; p.u_in += off * p.T; }
+  if (p.w_out) p.w_out += off * p.T * D;
+  if (p.mean_out) p.mean_out += off * p.T * D;
+  if (p.ljl_out) p.ljl_out += off * p.T;
+  if (p.ratio_out) p.ratio_out += off * p.T;
+  if (p.dec_out) p.dec_out += off * p.T;
+  p.lq_cur += off; p.lq_trj += off; p.sat += off; p.nsat += off; p.mcur += off * ctx->DP;
+  return p;
+}
+
+void launch_iwls_ljit(rmhmc_ctx* ctx, Group& g, const double* Ginv, double* out) {
+  launch(ctx, g, LIGHT, "iwls", [&](hipStream_t st) {
+    NB_SWITCH(ctx, hipLaunchKernelGGL((k_iwls_ljit<NB_>), dim3((unsigned)g.n), dim3(64), 0, st, ctx->D, ctx->DP, Ginv, out));
+  });
+}
+
+// one iteration of every chain: proposal, the point evaluation at w' (mode 1, the assembly path of the context's flags), compat terms,
+// decision
+void launch_iwls_iter(rmhmc_ctx* ctx, const IwlsParams& p) {
+  std::vector<Phase> ph;
+  ph.push_back([ctx, p](Group& g) { SMALL(ctx, g, "iwls", k_iwls_begin, ctx->D, ctx->DP, g.ch, iwls_view(ctx, g, p)); });
+  eval_point_phases(ctx, ph, false, 1);
+  if (p.compat) {
+    ph.push_back([ctx, p](Group& g) { launch_iwls_ljit(ctx, g, g.ch.trj.Ginv, iwls_view(ctx, g, p).lq_trj); });
+    ph.push_back([ctx, p](Group& g) {
+      int* sat = iwls_view(ctx, g, p).sat;
+      launch(ctx, g, HEAVY, "iwls_sat", [&](hipStream_t st) {
+        const dim3 grid((unsigned)((ctx->M + IWLS_SAT_ROWS - 1) / IWLS_SAT_ROWS), (unsigned)((g.n + IWLS_SAT_CH - 1) / IWLS_SAT_CH));
+        hipLaunchKernelGGL(k_iwls_sat, grid, dim3(IWLS_SAT_ROWS), 0, st, ctx->dd, g.n, (const double*)g.ch.trj.w, sat);
+      });
+    });
+  }
+  ph.push_back([ctx, p](Group& g) { SMALL(ctx, g, "iwls", k_iwls_end, ctx->D, ctx->DP, g.ch, iwls_view(ctx, g, p)); });
+  run_phases(ctx, ph);
+}
+
+// Iterations 0..n_iter-1 of every chain (iwls.py:38-85) from the record at theta0 (default 0, :18), evaluated by the generic kernels
+// (the arithmetic of the iterations' own evaluations).  Sampling: the reference's reports before iterations i % 1000 == 0 and burn_in
+// (:39-43), then the timer.
+int iwls_run(rmhmc_ctx* ctx, IwlsParams p, long long n_iter, bool sampling, const double* theta0, double* seconds_out) {
+  const bool medium = ctx->medium;
+  ctx->medium = false;
+  const int rc0 = mmala_init(ctx, theta0);
+  ctx->medium = medium;
+  RC(rc0);
+  if (p.compat)
+    for (Group& g : ctx->groups) launch_iwls_ljit(ctx, g, g.ch.cur.Ginv, p.lq_cur + g.off);
+  std::vector<long long> acc;
+  auto t0 = std::chrono::steady_clock::now();
+  for (long long i = 0; i < n_iter; ++i) {
+    if (sampling && (i % 1000 == 0 || i == p.burn_in)) {
+      if (ctx->progress_fn) {
+        acc.resize(ctx->n);
+        RC(download(ctx, acc.data(), ctx->ch.accepted, ctx->n));
+        RC(sync(ctx));
+        long long a = 0;
+        for (long long x : acc) a += x;
+        if (i % 1000 == 0) ctx->progress_fn(RMHMC_EV_PROGRESS, i, a, i * ctx->n, ctx->progress_user);
+        if (i == p.burn_in) ctx->progress_fn(RMHMC_EV_BURNIN_DONE, i, a, i * ctx->n, ctx->progress_user);
+      }
+      if (i == p.burn_in) {
+        RC(sync(ctx));
+        t0 = std::chrono::steady_clock::now();
+      }
+    }
+    p.it = i;
+    launch_iwls_iter(ctx, p);
+    HIPCK(hipGetLastError());
+    flow_tick(ctx);
+  }
+  RC(sync(ctx));
+  if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return RMHMC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rmhmc_iwls_sample(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t compat, uint64_t seed, int64_t chain_offset,
+                      const double* theta0, double* samples_out, int64_t* accepted_out, int64_t* saturated_out, double* seconds_out) {
+  NEED_DATA(ctx);
+  if (!samples_out || !amh_iters_ok(n_iter, burn_in) || chain_offset < 0)
+    return fail(ctx, RMHMC_ERR_INVALID, "iwls_sample: need samples_out, 0 <= burn_in < n_iter < 2^32, chain_offset >= 0");
+  if (ctx->D > 64) return fail(ctx, RMHMC_ERR_UNSUPPORTED, kIwlsDMsg);
+  ctx->chains_ready = false;
+  const size_t n = ctx->n, D = ctx->D, S = (size_t)(n_iter - burn_in);
+  double* d_samples = nullptr;
+  IwlsState s;
+  int rc = [&]() -> int {
+    HIPCK(hipMalloc((void**)&d_samples, sizeof(double) * n * S * D));
+    IwlsParams p{};
+    RC(iwls_alloc(ctx, s, p, compat));
+    p.seed = seed; p.chain_offset = chain_offset; p.burn_in = burn_in; p.S = (long long)S; p.samples = d_samples; p.T = n_iter;
+    RC(iwls_run(ctx, p, n_iter, true, theta0, seconds_out));
+    HIPCK(hipMemcpyAsync(samples_out, d_samples, sizeof(double) * n * S * D, hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<long long> a(n), b(n);
+    RC(download(ctx, a.data(), ctx->ch.accepted, n));
+    RC(download(ctx, b.data(), s.nsat, n));
+    RC(sync(ctx));
+    for (size_t c = 0; c < n; ++c) {
+      if (accepted_out) accepted_out[c] = a[c];
+      if (saturated_out) saturated_out[c] = b[c];
+    }
+    return RMHMC_OK;
+  }();
+  if (d_samples) (void)hipFree(d_samples);
+  iwls_free(s);
+  return rc;
+}
+
+int rmhmc_iwls_replay(rmhmc_ctx* ctx, int64_t n_iter, int32_t compat, const double* w_prop, const double* u, const double* theta0,
+                      double* w_out, double* mean_out, double* ljl_out, double* ratio_out, int8_t* decisions_out) {
+  NEED_DATA(ctx);
+  if (!w_prop || !u || !w_out || n_iter < 1 || n_iter > (int64_t)0xffffffffLL)
+    return fail(ctx, RMHMC_ERR_INVALID, "iwls_replay: need w_prop, u, w_out and 0 < n_iter < 2^32");
+  if (ctx->D > 64) return fail(ctx, RMHMC_ERR_UNSUPPORTED, kIwlsDMsg);
+  ctx->chains_ready = false;
+  const size_t n = ctx->n, D = ctx->D, T = (size_t)n_iter, vec = n * T * D;
+  double *d_wp = nullptr, *d_u = nullptr, *d_w = nullptr, *d_m = nullptr, *d_l = nullptr, *d_r = nullptr;
+  int8_t* d_dec = nullptr;
+  IwlsState s;
+  int rc = [&]() -> int {
+    HIPCK(hipMalloc((void**)&d_wp, sizeof(double) * vec)); HIPCK(hipMalloc((void**)&d_u, sizeof(double) * n * T));
+    HIPCK(hipMalloc((void**)&d_w, sizeof(double) * vec)); HIPCK(hipMalloc((void**)&d_m, sizeof(double) * vec));
+    HIPCK(hipMalloc((void**)&d_l, sizeof(double) * n * T)); HIPCK(hipMalloc((void**)&d_r, sizeof(double) * n * T));
+    HIPCK(hipMalloc((void**)&d_dec, n * T));
+    RC(upload(ctx, d_wp, w_prop, vec)); RC(upload(ctx, d_u, u, n * T));
+    IwlsParams p{};
+    RC(iwls_alloc(ctx, s, p, compat));
+    p.T = n_iter; p.w_prop = d_wp; p.u_in = d_u; p.w_out = d_w; p.mean_out = d_m; p.ljl_out = d_l; p.ratio_out = d_r; p.dec_out = d_dec;
+    RC(iwls_run(ctx, p, n_iter, false, theta0, nullptr));
+    RC(download(ctx, w_out, d_w, vec));
+    if (mean_out) RC(download(ctx, mean_out, d_m, vec));
+    if (ljl_out) RC(download(ctx, ljl_out, d_l, n * T));
+    if (ratio_out) RC(download(ctx, ratio_out, d_r, n * T));
+    if (decisions_out) RC(download(ctx, decisions_out, d_dec, n * T));
+    return sync(ctx);
+  }();
+  for (void* q : {(void*)d_wp, (void*)d_u, (void*)d_w, (void*)d_m, (void*)d_l, (void*)d_r, (void*)d_dec}) if (q) (void)hipFree(q);
+  iwls_free(s);
   return rc;
 }
 

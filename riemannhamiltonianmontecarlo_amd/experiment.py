@@ -18,11 +18,12 @@ import numpy as np
 
 from . import tools
 from .hmc import HMC
+from .iwls import iwls
 from .metropolis import AMH
 from .mmala import mMALA
 from .rmhmc import RMHMC
 
-SAMPLERS = {"RMHMC": RMHMC, "HMC": HMC, "mMALA": mMALA, "AMH": AMH}
+SAMPLERS = {"RMHMC": RMHMC, "HMC": HMC, "mMALA": mMALA, "AMH": AMH, "IWLS": iwls}
 
 
 def summarize(results_beta, results_time, nfft="python"):
