@@ -22,7 +22,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -36,14 +35,13 @@ constexpr int MAX_LDS = 160 * 1024;
 
 struct EvPair { hipEvent_t a, b; };
 
-// The batch of chains a launch works on, with its view of the per-chain arrays and the scratch sized for it.  There is one per context
+// The batch of chains a launch works on, with the per-chain arrays and the scratch sized for it.  There is one per context
 // (the whole batch); the work-sorted sampler narrows a copy of it to the prefix of chains still running (launch_global_step_prefix).
-// (Rounds 1-2 could cut the batch into 2-4 groups ping-ponged over two streams; measured twice without gain on MI355X - the co-running
-// light kernels are starved and the heavy ones slow down by the same total, profiles/r01_groups_sweep.txt - and removed.)
+// (Cutting the batch into 2-4 groups ping-ponged over two streams was measured twice without gain on MI355X - the co-running
+// light kernels are starved and the heavy ones slow down by the same total, profiles/r01_groups_sweep.txt.)
 struct Group {
   Chains ch{};
   int n = 0;
-  long long off = 0;
   int nsplit = 1;
   int8_t* Vs = nullptr;  // int8 metric path: slices of v, [S][nks][nCp][32]
   int8_t* Qs = nullptr;  // slices of the doubled G^-1 entries, [S][nkp][nCp][32]
@@ -61,8 +59,6 @@ struct Group {
   d4* ctile = nullptr;   // c = v(1-2p) of trj.w in the tile layout of k_mompass, [ceil(n/16)][Mp/16][64] x 4 doubles
   int nCp = 0;
 };
-
-enum Cls { HEAVY = 0, LIGHT = 1 };  // (documentation of a launch's kind: matrix-core pass over all rows / per-chain kernel)
 
 // Tuning options (include/rmhmc.h: rmhmc_create_opts / rmhmc_set_option).  The library reads no environment variables.
 struct Options {
@@ -110,8 +106,7 @@ struct rmhmc_ctx {
   long long flow_steps = 0, flow_ticks = 0;
   int* stale_list_alloc = nullptr;  // list of the chains that have just rejected a proposal (k_crestore; in use when cdyn and crestore are on)
   DevData dd{};
-  Chains ch{};  // whole-batch view (uploads / downloads)
-  std::vector<Group> groups;
+  Group batch;  // all n chains; batch.ch holds the per-chain arrays
   std::vector<void*> allocs;
   bool have_data = false, chains_ready = false;
   int sampler = 0;           // 0: RMHMC (rmhmc.py), 1: plain HMC (hmc.py) -- selects the global step
@@ -209,10 +204,9 @@ struct Timed {
   ~Timed() { if (on) (void)hipEventRecord(ev.b, st); }
 };
 
-// Launch one kernel (or a short run of them) on the batch g.  fn(stream) enqueues it; name keys the optional event timing.
+// Launch one kernel (or a short run of them).  fn(stream) enqueues it; name keys the optional event timing.
 template <typename F>
-void launch(rmhmc_ctx* ctx, Group& g, Cls, const char* name, F&& fn) {
-  (void)g;
+void launch(rmhmc_ctx* ctx, const char* name, F&& fn) {
   Timed t(ctx, name, ctx->stream);
   fn(ctx->stream);
 }
@@ -265,7 +259,7 @@ static bool use_delta_inner(const rmhmc_ctx* ctx, const Group& g, int it) {
 }
 template <int MODE>
 void launch_rowpass(rmhmc_ctx* ctx, Group& g, const double* w, double* out0, double* out2 = nullptr, bool delta = false) {
-  launch(ctx, g, HEAVY, "rowpass", [&](hipStream_t st) {
+  launch(ctx, "rowpass", [&](hipStream_t st) {
     if (ctx->big) {
       dim3 grid((unsigned)((g.n + 15) / 16), g.nsplit);
       hipLaunchKernelGGL((k_rowpass_big<MODE>), grid, dim3(256), 0, st, ctx->dd, g.n, g.nsplit, ctx->nbk, g.ch.phase, w, out0, out2,
@@ -422,27 +416,27 @@ void launch_leverage_i8_t(rmhmc_ctx* ctx, Group& g, hipStream_t st, int part) {
 // keep_base (large-D path): this G is the base of a delta assembly to come; Gq will be factored in place, so a copy is kept
 void launch_assemble(rmhmc_ctx* ctx, Group& g, const double* v, bool inner = false, bool delta = false, bool keep_base = false) {
   if (ctx->i8 && delta && ctx->big)
-    launch(ctx, g, HEAVY, "vsplit", [&](hipStream_t st) { launch_assemble_i8_t<6, 4, 1>(ctx, g, v, st, 0, true); });
+    launch(ctx, "vsplit", [&](hipStream_t st) { launch_assemble_i8_t<6, 4, 1>(ctx, g, v, st, 0, true); });
   if (ctx->i8 && delta && inner) {  // (use_delta_inner: five-slice accuracy)
-    launch(ctx, g, HEAVY, "assemble_i8_inner_delta", [&](hipStream_t st) { launch_assemble_i8_delta(ctx, g, st, 5); });
+    launch(ctx, "assemble_i8_inner_delta", [&](hipStream_t st) { launch_assemble_i8_delta(ctx, g, st, 5); });
     return;
   }
   if (ctx->i8 && delta) {  // (use_delta: S = 6, WN = 4)
-    launch(ctx, g, HEAVY, "assemble_i8_delta", [&](hipStream_t st) { launch_assemble_i8_delta(ctx, g, st, 6); });
+    launch(ctx, "assemble_i8_delta", [&](hipStream_t st) { launch_assemble_i8_delta(ctx, g, st, 6); });
     return;
   }
   if (ctx->i8) {
     if (ctx->big)  // (the generic row pass already wrote the slices)
-      launch(ctx, g, HEAVY, "vsplit", [&](hipStream_t st) { I8_SWITCH(ctx, (launch_assemble_i8_t<S_, WN_, TN_>(ctx, g, v, st, 0))); });
+      launch(ctx, "vsplit", [&](hipStream_t st) { I8_SWITCH(ctx, (launch_assemble_i8_t<S_, WN_, TN_>(ctx, g, v, st, 0))); });
     const int suse = (inner && ctx->i8_inner_drop && ctx->i8S == 6) ? 5 : ctx->i8S;  // (5 -> 4 costs parity: 2e-9 on theta at M = 97)
-    launch(ctx, g, HEAVY, suse == ctx->i8S ? "assemble_i8" : "assemble_i8_inner", [&](hipStream_t st) {
+    launch(ctx, suse == ctx->i8S ? "assemble_i8" : "assemble_i8_inner", [&](hipStream_t st) {
       I8_SWITCH_S(suse, (launch_assemble_i8_t<S_, WN_, TN_>(ctx, g, v, st, 1)));
       if (keep_base && ctx->big && g.Gbase)
         (void)hipMemcpyAsync(g.Gbase, g.ch.Gq, sizeof(double) * (size_t)g.n * ctx->DP * ctx->DP, hipMemcpyDeviceToDevice, st);
     });
     return;
   }
-  launch(ctx, g, HEAVY, "assemble", [&](hipStream_t st) {
+  launch(ctx, "assemble", [&](hipStream_t st) {
     if (ctx->flags & RMHMC_FLAG_FP32_METRIC) {  // precision experiment: fp32 matrix cores for the metric only
       if (ctx->big) {
         hipLaunchKernelGGL((k_assemble_f32<4>), dim3((unsigned)((g.n + 3) / 4), ctx->npairs), dim3(256), 0, st, ctx->dd, g.n, g.ch.phase, v,
@@ -475,7 +469,7 @@ void launch_assemble(rmhmc_ctx* ctx, Group& g, const double* v, bool inner = fal
 // q partials of u' dG/dw_d u for every chain (u = ch.uq, w as given); summed by k_mom_update / k_mom_final.
 // cmode (generic path): 1 = first pass at this w, c is computed and kept; 2 = c of this w is at hand (k_mompass in kernels.hip.h)
 void launch_mompass(rmhmc_ctx* ctx, Group& g, const double* w, int cmode) {
-  launch(ctx, g, HEAVY, "mompass", [&](hipStream_t st) {
+  launch(ctx, "mompass", [&](hipStream_t st) {
     if (!ctx->opt.ccache) cmode = 0;
     if (ctx->big) {
       dim3 grid((unsigned)((g.n + 15) / 16), g.nsplit);
@@ -505,20 +499,20 @@ static bool fused_trace(const rmhmc_ctx* ctx, const Group& g) { return ctx->i8 &
 // part: 0 everything; 1 the leverage GEMM alone (h -> rv0); 2 the reduction of the trace partials alone
 void launch_leverage(rmhmc_ctx* ctx, Group& g, int part = 0) {
   if (ctx->i8 && part == 2) {
-    launch(ctx, g, LIGHT, "small", [&](hipStream_t st) {
+    launch(ctx, "small", [&](hipStream_t st) {
       hipLaunchKernelGGL(k_reduce_tr, dim3((unsigned)g.n), dim3(64), 0, st, ctx->D, ctx->DP, g.ch, g.ch.gpart, g.nsplit);
     });
     return;
   }
   if (ctx->i8) {  // h_n as the transposed sliced GEMM, then tr = X' (c .* h) on the fp64 matrix cores
-    launch(ctx, g, HEAVY, "qsplit", [&](hipStream_t st) { I8_SWITCH(ctx, (launch_leverage_i8_t<S_, WN_, TN_>(ctx, g, st, 0))); });
+    launch(ctx, "qsplit", [&](hipStream_t st) { I8_SWITCH(ctx, (launch_leverage_i8_t<S_, WN_, TN_>(ctx, g, st, 0))); });
     // The leverages h_n = x_n' G^-1 x_n enter the trace term only, which steers the momentum and appears in no Hamiltonian: like the metric
     // of an inner position iterate they are summed from the S - 1 most significant slices of the same operands (15 slice products
     // instead of 21; h to ~3e-12 norm-wise, theta / p after a step move by < 1e-11; RMHMC_FLAG_INT8_INNER_FULL: all S)
     const int suse = (ctx->i8_inner_drop && ctx->i8S == 6) ? 5 : ctx->i8S;
-    launch(ctx, g, HEAVY, "leverage_i8", [&](hipStream_t st) { I8_SWITCH_S(suse, (launch_leverage_i8_t<S_, WN_, TN_>(ctx, g, st, 1))); });
+    launch(ctx, "leverage_i8", [&](hipStream_t st) { I8_SWITCH_S(suse, (launch_leverage_i8_t<S_, WN_, TN_>(ctx, g, st, 1))); });
     if (part == 1) return;
-    launch(ctx, g, HEAVY, "trvec", [&](hipStream_t st) {
+    launch(ctx, "trvec", [&](hipStream_t st) {
       if (ctx->big) {  // rv0 holds h (one "pair" plane), the large-D trace kernel multiplies by c itself
         dim3 grid((unsigned)((g.n + 15) / 16), g.nsplit);
         hipLaunchKernelGGL(k_trace_big, grid, dim3(256), 0, st, ctx->dd, g.n, g.nsplit, ctx->nbk, 1, g.ch.rv2, g.ch.rv0, g.ch.gpart);
@@ -527,101 +521,85 @@ void launch_leverage(rmhmc_ctx* ctx, Group& g, int part = 0) {
       dim3 grid((unsigned)((g.n + 63) / 64), g.nsplit);
       NB_SWITCH(ctx, hipLaunchKernelGGL((k_trvec<NB_>), grid, dim3(256), 0, st, ctx->dd, g.n, g.nsplit, g.ch.rv0, g.ch.gpart, (const d4*)g.ctile));
     });
-    launch(ctx, g, LIGHT, "small", [&](hipStream_t st) {
+    launch(ctx, "small", [&](hipStream_t st) {
       hipLaunchKernelGGL(k_reduce_tr, dim3((unsigned)g.n), dim3(64), 0, st, ctx->D, ctx->DP, g.ch, g.ch.gpart, g.nsplit);
     });
     return;
   }
   if (ctx->big) {  // per block pair leverage contributions, then the trace GEMM over 16 chains per workgroup
-    double* hpart = ctx->d_hpart + (size_t)g.off * ctx->Mp;  // [pair][n][Mp] of this group (single group: off = 0)
-    launch(ctx, g, HEAVY, "leverage", [&](hipStream_t st) {
+    double* hpart = ctx->d_hpart;  // [pair][n][Mp]
+    launch(ctx, "leverage", [&](hipStream_t st) {
       hipLaunchKernelGGL(k_leverage_pair<false>, dim3((unsigned)((g.n + 3) / 4), ctx->npairs - ctx->nbk), dim3(256), 0, st, ctx->dd, g.n,
                          ctx->nbk, g.ch.phase, g.ch.trj.Ginv, hpart);
       hipLaunchKernelGGL(k_leverage_pair<true>, dim3((unsigned)((g.n + 3) / 4), ctx->nbk), dim3(256), 0, st, ctx->dd, g.n, ctx->nbk,
                          g.ch.phase, g.ch.trj.Ginv, hpart);
     });
-    launch(ctx, g, HEAVY, "leverage", [&](hipStream_t st) {
+    launch(ctx, "leverage", [&](hipStream_t st) {
       dim3 grid((unsigned)((g.n + 15) / 16), g.nsplit);
       hipLaunchKernelGGL(k_trace_big, grid, dim3(256), 0, st, ctx->dd, g.n, g.nsplit, ctx->nbk, ctx->npairs, g.ch.rv2, hpart, g.ch.gpart);
     });
-    launch(ctx, g, LIGHT, "small", [&](hipStream_t st) {
+    launch(ctx, "small", [&](hipStream_t st) {
       hipLaunchKernelGGL(k_reduce_tr, dim3((unsigned)g.n), dim3(64), 0, st, ctx->D, ctx->DP, g.ch, g.ch.gpart, g.nsplit);
     });
     return;
   }
   const int fs = std::min(g.fsplit, g.nsplit);  // (the partials go to gpart, which holds nsplit planes)
-  launch(ctx, g, HEAVY, "leverage", [&](hipStream_t st) {
+  launch(ctx, "leverage", [&](hipStream_t st) {
     dim3 grid((unsigned)((g.n + 3) / 4), (unsigned)fs);
     NB_SWITCH(ctx, hipLaunchKernelGGL((k_leverage<NB_>), grid, dim3(256), 0, st, ctx->dd, g.n, g.ch.phase, g.ch.trj.Ginv, g.ch.rv2,
                                       g.ch.trj.tr, g.ch.gpart));
   });
   if (fs > 1)
-    launch(ctx, g, LIGHT, "small", [&](hipStream_t st) {
+    launch(ctx, "small", [&](hipStream_t st) {
       hipLaunchKernelGGL(k_reduce_tr, dim3((unsigned)g.n), dim3(64), 0, st, ctx->D, ctx->DP, g.ch, g.ch.gpart, fs);
     });
 }
 
 // one wavefront (64-thread block) per chain
 #define SMALL(ctx, g, name, kern, ...)                                                                     \
-  launch(ctx, g, LIGHT, name, [&](hipStream_t st_) { hipLaunchKernelGGL(kern, dim3((unsigned)(g).n), dim3(64), 0, st_, __VA_ARGS__); })
+  launch(ctx, name, [&](hipStream_t st_) { hipLaunchKernelGGL(kern, dim3((unsigned)(g).n), dim3(64), 0, st_, __VA_ARGS__); })
 
 // one 256-thread workgroup per chain (blocked dense algebra of the large-D path)
 #define BIG(ctx, g, name, kern, ...)                                                                       \
-  launch(ctx, g, LIGHT, name, [&](hipStream_t st_) { hipLaunchKernelGGL(kern, dim3((unsigned)(g).n), dim3(256), 0, st_, __VA_ARGS__); })
-
-// A phase is one launch per group; phases are issued group-alternating so that, with two groups, the main
-// stream sees heavy(A), heavy(B), heavy(A), ... and the light kernels of a group overlap the other's heavy one.
-using Phase = std::function<void(Group&)>;
-void run_phases(rmhmc_ctx* ctx, const std::vector<Phase>& phases) {
-  for (const Phase& ph : phases)
-    for (Group& g : ctx->groups) ph(g);
-}
+  launch(ctx, name, [&](hipStream_t st_) { hipLaunchKernelGGL(kern, dim3((unsigned)(g).n), dim3(256), 0, st_, __VA_ARGS__); })
 
 // Evaluate the point record at trj.w for every chain in phase 1 (rmhmc.py:134-161; with advance the
 // explicit momentum half step :163 too): v, r, c, log-joint partials -> G and gradient on the matrix cores
 // -> factor / inverse / u = G^-1 p -> quadratic term -> leverage pass (trace term) -> momentum update.
 // mode 0: everything; 1: metric, factor, inverse, gradient, log joint only (simplified mMALA); 2: mode 1 + the trace term (full mMALA)
-void eval_point_phases(rmhmc_ctx* ctx, std::vector<Phase>& ph, bool advance, int mode = 0) {
+void eval_point_phases(rmhmc_ctx* ctx, Group& g, bool advance, int mode = 0) {
   // (advance: the evaluation that ends a leapfrog step - the last position iterate's slices and G are at hand)
-  ph.push_back([ctx, advance](Group& g) { launch_rowpass<RP_F>(ctx, g, g.ch.trj.w, g.ch.rv0, g.ch.rv2, advance && use_delta(ctx, g)); });
-  if (ctx->big) ph.push_back([ctx](Group& g) { SMALL(ctx, g, "small", k_finish_big, ctx->dd, g.ch, g.nsplit); });
-  ph.push_back([ctx, advance](Group& g) { launch_assemble(ctx, g, g.ch.rv0, false, advance && use_delta(ctx, g)); });
+  const bool delta = advance && use_delta(ctx, g);
+  launch_rowpass<RP_F>(ctx, g, g.ch.trj.w, g.ch.rv0, g.ch.rv2, delta);
+  if (ctx->big) SMALL(ctx, g, "small", k_finish_big, ctx->dd, g.ch, g.nsplit);
+  launch_assemble(ctx, g, g.ch.rv0, false, delta);
   if (ctx->big) {
-    ph.push_back([ctx](Group& g) {
-      if (ctx->want_G)
-        (void)hipMemcpyAsync(ctx->d_Gcopy + (size_t)g.off * ctx->DP * ctx->DP, g.ch.Gq, sizeof(double) * (size_t)g.n * ctx->DP * ctx->DP,
-                             hipMemcpyDeviceToDevice, ctx->stream);
-      BIG(ctx, g, "factor", k_chol_big<1>, ctx->dd, g.ch, ctx->nbk, ctx->d_Wd + (size_t)g.off * ctx->nbk * 4096, ctx->eps);
-    });
-    ph.push_back([ctx](Group& g) { BIG(ctx, g, "factor", k_inverse_big, ctx->dd, g.ch, ctx->nbk, ctx->d_Wd + (size_t)g.off * ctx->nbk * 4096); });
-    ph.push_back([ctx](Group& g) { SMALL(ctx, g, "small", k_ginv_matvec, ctx->D, ctx->DP, g.ch, g.ch.p); });
+    if (ctx->want_G)
+      (void)hipMemcpyAsync(ctx->d_Gcopy, g.ch.Gq, sizeof(double) * (size_t)g.n * ctx->DP * ctx->DP, hipMemcpyDeviceToDevice, ctx->stream);
+    BIG(ctx, g, "factor", k_chol_big<1>, ctx->dd, g.ch, ctx->nbk, ctx->d_Wd, ctx->eps);
+    BIG(ctx, g, "factor", k_inverse_big, ctx->dd, g.ch, ctx->nbk, ctx->d_Wd);
+    SMALL(ctx, g, "small", k_ginv_matvec, ctx->D, ctx->DP, g.ch, g.ch.p);
   } else {
-    ph.push_back([ctx](Group& g) {
-      launch(ctx, g, LIGHT, "factor", [&](hipStream_t st) {
-        NB_SWITCH(ctx, hipLaunchKernelGGL((k_factor_full<NB_>), dim3((unsigned)g.n), dim3(64), 0, st, ctx->dd, g.ch, g.nsplit));
-      });
+    launch(ctx, "factor", [&](hipStream_t st) {
+      NB_SWITCH(ctx, hipLaunchKernelGGL((k_factor_full<NB_>), dim3((unsigned)g.n), dim3(64), 0, st, ctx->dd, g.ch, g.nsplit));
     });
   }
   if (mode == 1) return;  // simplified mMALA needs neither the quadratic nor the trace term
   if (mode == 2) {        // full mMALA: the trace term enters the drift, the quadratic term does not exist
-    ph.push_back([ctx](Group& g) { launch_leverage(ctx, g); });
+    launch_leverage(ctx, g);
     return;
   }
-  ph.push_back([ctx](Group& g) {
-    if (fused_trace(ctx, g)) {  // leverage GEMM first, then ONE pass for the quadratic term and the trace term
-      launch_leverage(ctx, g, 1);
-      launch(ctx, g, HEAVY, "mompass", [&](hipStream_t st) {
-        dim3 grid((unsigned)((g.n + 63) / 64), g.nsplit);
-        NB_SWITCH(ctx, hipLaunchKernelGGL((k_mompass_trv<NB_>), grid, dim3(256), 0, st, ctx->dd, g.n, g.nsplit, g.ch.uq, g.ch.qpart, g.ctile, g.ch.rv0, g.ch.gpart));
-      });  // (k_mom_final below sums the trace partials itself)
-    } else {
-      launch_mompass(ctx, g, g.ch.trj.w, 2);  // (the row pass above has just stored c for trj.w)
-      launch_leverage(ctx, g);
-    }
-  });
-  ph.push_back([ctx, advance](Group& g) {
-    SMALL(ctx, g, "small", k_mom_final, ctx->D, ctx->DP, g.ch, ctx->eps, advance ? 1 : 0, g.nsplit, fused_trace(ctx, g) ? g.ch.gpart : (const double*)nullptr);
-  });
+  if (fused_trace(ctx, g)) {  // leverage GEMM first, then ONE pass for the quadratic term and the trace term
+    launch_leverage(ctx, g, 1);
+    launch(ctx, "mompass", [&](hipStream_t st) {
+      dim3 grid((unsigned)((g.n + 63) / 64), g.nsplit);
+      NB_SWITCH(ctx, hipLaunchKernelGGL((k_mompass_trv<NB_>), grid, dim3(256), 0, st, ctx->dd, g.n, g.nsplit, g.ch.uq, g.ch.qpart, g.ctile, g.ch.rv0, g.ch.gpart));
+    });  // (k_mom_final below sums the trace partials itself)
+  } else {
+    launch_mompass(ctx, g, g.ch.trj.w, 2);  // (the row pass above has just stored c for trj.w)
+    launch_leverage(ctx, g);
+  }
+  SMALL(ctx, g, "small", k_mom_final, ctx->D, ctx->DP, g.ch, ctx->eps, advance ? 1 : 0, g.nsplit, fused_trace(ctx, g) ? g.ch.gpart : (const double*)nullptr);
 }
 
 // one-launch step / evaluation / folded global step for small batches (medium_step.hip.h).  Data rows per thread stay in registers
@@ -645,83 +623,60 @@ void launch_step_medium(rmhmc_ctx* ctx, Group& g, hipStream_t st, int guards, in
 }
 
 // One generalised leapfrog step for every chain in phase 1 (rmhmc.py:96-163).
-void step_phases(rmhmc_ctx* ctx, std::vector<Phase>& ph) {
+void step_phases(rmhmc_ctx* ctx, Group& g) {
   const int D = ctx->D, DP = ctx->DP, K = ctx->K;
   const double eps = ctx->eps;
+  const int guards = (ctx->flags & RMHMC_FLAG_GUARDS) ? 1 : 0;
   if (ctx->medium) {  // the whole step in one launch, one workgroup per chain
-    const int guards = (ctx->flags & RMHMC_FLAG_GUARDS) ? 1 : 0;
-    ph.push_back([=](Group& g) {
-      launch(ctx, g, HEAVY, "medium", [&](hipStream_t st) {
-        launch_step_medium(ctx, g, st, guards, 0, 0, IterParams{});
-      });
-    });
+    launch(ctx, "medium", [&](hipStream_t st) { launch_step_medium(ctx, g, st, guards, 0, 0, IterParams{}); });
     return;
   }
   // c tiles of the chains whose last proposal was rejected (their trj has fallen back to cur): recomputed for them alone, so that the
   // first momentum pass finds every chain's tiles at hand
-  if (!ctx->big && ctx->opt.cdyn)
-    ph.push_back([=](Group& g) {
-      if (!g.ctile || !g.ch.stale_list) return;
-      launch(ctx, g, HEAVY, "mompass", [&](hipStream_t st) {
-        // row pieces of this kernel's own, and a SMALL grid whose wavefronts walk the list (8 x 64 chains at a time): a wavefront alone on its
-        // SIMD takes ~4.3 us per 32-row block (load - product - exp latencies with nothing to hide them), and workgroups that only read the
-        // count and return are not free either.  Measured at config 3 (~300 listed chains = 19 wavefront groups per step, one box,
-        // tools/crs_sweep.sh): grid 32 x 16 (round 2: room for 2048 chains, the rest left to k_mompass<.., 3>) 75.6 us, 8 x 16 43, 8 x 32 29.3,
-        // 8 x 64 31.9, 4 x 64 28.6, 2 x 128 34.1.
-        const int rsplit = std::max(1, std::min(32, ctx->Mp / 32 / 4));
-        dim3 grid((unsigned)std::min((g.n + 63) / 64, 8), (unsigned)rsplit);
-        NB_SWITCH(ctx, hipLaunchKernelGGL((k_crestore<NB_>), grid, dim3(256), 0, st, ctx->dd, g.n, g.ch.phase, g.ch.trj.w, g.ctile, g.ch.cstale,
-                                          g.ch.stale_list, g.ch.stale_count));
-        // (the count is reset by k_pos_first, later in the step)
-      });
+  if (!ctx->big && ctx->opt.cdyn && g.ctile && g.ch.stale_list)
+    launch(ctx, "mompass", [&](hipStream_t st) {
+      // row pieces of this kernel's own, and a SMALL grid whose wavefronts walk the list (8 x 64 chains at a time): a wavefront alone on its
+      // SIMD takes ~4.3 us per 32-row block (load - product - exp latencies with nothing to hide them), and workgroups that only read the
+      // count and return are not free either.  Measured at config 3 (~300 listed chains = 19 wavefront groups per step, one box,
+      // tools/crs_sweep.sh): grid 32 x 16 (round 2: room for 2048 chains, the rest left to k_mompass<.., 3>) 75.6 us, 8 x 16 43, 8 x 32 29.3,
+      // 8 x 64 31.9, 4 x 64 28.6, 2 x 128 34.1.
+      const int rsplit = std::max(1, std::min(32, ctx->Mp / 32 / 4));
+      dim3 grid((unsigned)std::min((g.n + 63) / 64, 8), (unsigned)rsplit);
+      NB_SWITCH(ctx, hipLaunchKernelGGL((k_crestore<NB_>), grid, dim3(256), 0, st, ctx->dd, g.n, g.ch.phase, g.ch.trj.w, g.ctile, g.ch.cstale,
+                                        g.ch.stale_list, g.ch.stale_count));
+      // (the count is reset by k_pos_first, later in the step)
     });
   // implicit momentum half step: K fixed-point iterations (rmhmc.py:102-110).  D <= 64: the update that ends an iteration and the G^-1 PM
   // product that starts the next are one launch (k_mom_update_matvec), the last update is done by k_pos_first
   const bool fuse = !ctx->big;
   for (int it = 0; it < K; ++it) {
-    if (it == 0 || !fuse) ph.push_back([=](Group& g) { SMALL(ctx, g, "small", k_ginv_matvec, D, DP, g.ch, it == 0 ? g.ch.p : g.ch.PM); });
-    ph.push_back([=](Group& g) { launch_mompass(ctx, g, g.ch.trj.w, it == 0 ? 1 : 2); });
-    if (!fuse) ph.push_back([=](Group& g) { SMALL(ctx, g, "small", k_mom_update, D, DP, g.ch, eps, it == K - 1 ? 1 : 0, g.nsplit); });
-    else if (it < K - 1) ph.push_back([=](Group& g) { SMALL(ctx, g, "small", k_mom_update_matvec, D, DP, g.ch, eps, g.nsplit); });
+    if (it == 0 || !fuse) SMALL(ctx, g, "small", k_ginv_matvec, D, DP, g.ch, it == 0 ? g.ch.p : g.ch.PM);
+    launch_mompass(ctx, g, g.ch.trj.w, it == 0 ? 1 : 2);
+    if (!fuse) SMALL(ctx, g, "small", k_mom_update, D, DP, g.ch, eps, it == K - 1 ? 1 : 0, g.nsplit);
+    else if (it < K - 1) SMALL(ctx, g, "small", k_mom_update_matvec, D, DP, g.ch, eps, g.nsplit);
   }
   // implicit position step: K fixed-point iterations (rmhmc.py:113-123); the first one re-uses the
   // stored factor of G(w)
   if (ctx->big) {
-    ph.push_back([=](Group& g) { SMALL(ctx, g, "small", k_ginv_matvec, D, DP, g.ch, g.ch.p); });
-    ph.push_back([=](Group& g) { SMALL(ctx, g, "small", k_pos_first_big, D, DP, g.ch, eps); });
+    SMALL(ctx, g, "small", k_ginv_matvec, D, DP, g.ch, g.ch.p);
+    SMALL(ctx, g, "small", k_pos_first_big, D, DP, g.ch, eps);
   } else {
-    ph.push_back([=](Group& g) { SMALL(ctx, g, "factor", k_pos_first, D, DP, g.ch, eps, g.nsplit); });
+    SMALL(ctx, g, "factor", k_pos_first, D, DP, g.ch, eps, g.nsplit);
   }
-  const int guards = (ctx->flags & RMHMC_FLAG_GUARDS) ? 1 : 0;
   for (int it = 1; it < K; ++it) {
-    ph.push_back([=](Group& g) { launch_rowpass<RP_V>(ctx, g, g.ch.wq, g.ch.rv0, nullptr, use_delta_inner(ctx, g, it)); });
-    ph.push_back([=](Group& g) {
-      const bool base = (it == 1 && use_delta_inner(ctx, g, 2)) || (it == K - 1 && use_delta(ctx, g));
-      launch_assemble(ctx, g, g.ch.rv0, it < K - 1, use_delta_inner(ctx, g, it), base);
-    });
+    launch_rowpass<RP_V>(ctx, g, g.ch.wq, g.ch.rv0, nullptr, use_delta_inner(ctx, g, it));
+    const bool base = (it == 1 && use_delta_inner(ctx, g, 2)) || (it == K - 1 && use_delta(ctx, g));
+    launch_assemble(ctx, g, g.ch.rv0, it < K - 1, use_delta_inner(ctx, g, it), base);
     if (ctx->big)
-      ph.push_back([=](Group& g) { BIG(ctx, g, "factor", k_chol_big<0>, ctx->dd, g.ch, ctx->nbk, ctx->d_Wd + (size_t)g.off * ctx->nbk * 4096, eps); });
+      BIG(ctx, g, "factor", k_chol_big<0>, ctx->dd, g.ch, ctx->nbk, ctx->d_Wd, eps);
     else
-      ph.push_back([=](Group& g) {
-        launch(ctx, g, LIGHT, "factor", [&](hipStream_t st) {  // (the last iterate: accepted as the new w, position guard, in the same launch)
-          NB_SWITCH(ctx, hipLaunchKernelGGL((k_factor_solve<NB_>), dim3((unsigned)g.n), dim3(64), 0, st, D, DP, g.ch, eps, it == K - 1 ? guards : -1));
-        });
+      launch(ctx, "factor", [&](hipStream_t st) {  // (the last iterate: accepted as the new w, position guard, in the same launch)
+        NB_SWITCH(ctx, hipLaunchKernelGGL((k_factor_solve<NB_>), dim3((unsigned)g.n), dim3(64), 0, st, D, DP, g.ch, eps, it == K - 1 ? guards : -1));
       });
   }
-  if (ctx->big || K < 2) ph.push_back([=](Group& g) { SMALL(ctx, g, "small", k_pos_final, D, DP, g.ch, guards); });
+  if (ctx->big || K < 2) SMALL(ctx, g, "small", k_pos_final, D, DP, g.ch, guards);
   // explicit momentum half step at the new point (rmhmc.py:134-163)
-  eval_point_phases(ctx, ph, true);
-}
-
-void launch_eval_point(rmhmc_ctx* ctx) {
-  std::vector<Phase> ph;
-  eval_point_phases(ctx, ph, false);
-  run_phases(ctx, ph);
-}
-void launch_step(rmhmc_ctx* ctx) {
-  std::vector<Phase> ph;
-  step_phases(ctx, ph);
-  run_phases(ctx, ph);
+  eval_point_phases(ctx, g, true);
 }
 
 struct IterBase {
@@ -731,34 +686,32 @@ struct IterBase {
   bool count_done;
 };
 
-IterParams iter_params(rmhmc_ctx* ctx, const Group& g, const IterBase& b) {
+IterParams iter_params(rmhmc_ctx* ctx, const IterBase& b) {
   IterParams ip{};
   ip.flags = ctx->flags;
   ip.L = ctx->L;
   ip.seed = ctx->seed;
-  ip.chain_offset = ctx->chain_offset + g.off;
+  ip.chain_offset = ctx->chain_offset;
   ip.iter_limit = b.limit;
   ip.burn_in = b.burn_in;
   ip.S = b.S;
-  ip.samples = b.samples ? b.samples + (size_t)g.off * b.S * ctx->D : nullptr;
-  if (ctx->sorted) {  // (single group: g.off = 0) chain ids and sample blocks through the position -> chain map
-    ip.orig = ctx->d_orig;
-    ip.chain_offset = ctx->chain_offset;
-    ip.samples = b.samples;
-  }
+  ip.samples = b.samples;
+  if (ctx->sorted) ip.orig = ctx->d_orig;  // chain ids and sample blocks through the position -> chain map
   if (b.explicit_rng) {
-    ip.z_in = ctx->d_z + (size_t)g.off * ctx->D; ip.ulen_in = ctx->d_ulen + g.off; ip.gdir_in = ctx->d_gdir + g.off; ip.uacc_in = ctx->d_uacc + g.off;
+    ip.z_in = ctx->d_z; ip.ulen_in = ctx->d_ulen; ip.gdir_in = ctx->d_gdir; ip.uacc_in = ctx->d_uacc;
   }
   ip.done_count = b.count_done ? ctx->d_done : nullptr;
   ip.lower_L = (!ctx->big && !ctx->medium && !ctx->fused && ctx->sampler == 0) ? 1 : 0;  // (k_factor_full is the only writer of trj.L there)
   return ip;
 }
 
-void launch_iter_begin(rmhmc_ctx* ctx, const IterBase& b) {
-  for (Group& g : ctx->groups) { IterParams ip = iter_params(ctx, g, b); SMALL(ctx, g, "small", k_iter_begin, ctx->D, ctx->DP, g.ch, ip); }
+void launch_iter_begin(rmhmc_ctx* ctx, Group& g, const IterBase& b) {
+  const IterParams ip = iter_params(ctx, b);
+  SMALL(ctx, g, "small", k_iter_begin, ctx->D, ctx->DP, g.ch, ip);
 }
-void launch_iter_end(rmhmc_ctx* ctx, const IterBase& b) {
-  for (Group& g : ctx->groups) { IterParams ip = iter_params(ctx, g, b); SMALL(ctx, g, "small", k_iter_end, ctx->D, ctx->DP, g.ch, ip); }
+void launch_iter_end(rmhmc_ctx* ctx, Group& g, const IterBase& b) {
+  const IterParams ip = iter_params(ctx, b);
+  SMALL(ctx, g, "small", k_iter_end, ctx->D, ctx->DP, g.ch, ip);
 }
 
 // plain HMC (hmc.py:38-84): begin / half step + position / gradient pass / half step / end
@@ -775,67 +728,58 @@ void launch_hmc_traj_nb(rmhmc_ctx* ctx, Group& g, int eval_only, hipStream_t st)
   }
 }
 void launch_hmc_traj(rmhmc_ctx* ctx, Group& g, int eval_only) {
-  launch(ctx, g, HEAVY, "medium", [&](hipStream_t st) {
+  launch(ctx, "medium", [&](hipStream_t st) {
     if (ctx->NB == 1) launch_hmc_traj_nb<1>(ctx, g, eval_only, st);
     else launch_hmc_traj_nb<2>(ctx, g, eval_only, st);
   });
 }
 
-void launch_hmc_global_step(rmhmc_ctx* ctx, const IterBase& b) {
-  std::vector<Phase> ph;
+void launch_hmc_global_step(rmhmc_ctx* ctx, Group& g, const IterBase& b) {
   const double eps = ctx->eps;
-  ph.push_back([ctx, b](Group& g) { IterParams ip = iter_params(ctx, g, b); SMALL(ctx, g, "small", k_hmc_begin, ctx->D, ctx->DP, g.ch, ip); });
+  const IterParams ip = iter_params(ctx, b);
+  SMALL(ctx, g, "small", k_hmc_begin, ctx->D, ctx->DP, g.ch, ip);
   if (ctx->hmc_traj) {  // the whole trajectory of every chain in one launch
-    ph.push_back([ctx](Group& g) { launch_hmc_traj(ctx, g, 0); });
-    ph.push_back([ctx, b](Group& g) { IterParams ip = iter_params(ctx, g, b); SMALL(ctx, g, "small", k_hmc_end, ctx->D, ctx->DP, g.ch, ip); });
-    run_phases(ctx, ph);
-    return;
+    launch_hmc_traj(ctx, g, 0);
+  } else {
+    SMALL(ctx, g, "small", k_hmc_pre, ctx->D, ctx->DP, g.ch, eps);
+    launch_rowpass<RP_G>(ctx, g, g.ch.trj.w, nullptr);
+    SMALL(ctx, g, "small", k_hmc_post, ctx->dd, g.ch, eps, g.nsplit);
   }
-  ph.push_back([=](Group& g) { SMALL(ctx, g, "small", k_hmc_pre, ctx->D, ctx->DP, g.ch, eps); });
-  ph.push_back([ctx](Group& g) { launch_rowpass<RP_G>(ctx, g, g.ch.trj.w, nullptr); });
-  ph.push_back([=](Group& g) { SMALL(ctx, g, "small", k_hmc_post, ctx->dd, g.ch, eps, g.nsplit); });
-  ph.push_back([ctx, b](Group& g) { IterParams ip = iter_params(ctx, g, b); SMALL(ctx, g, "small", k_hmc_end, ctx->D, ctx->DP, g.ch, ip); });
-  run_phases(ctx, ph);
+  SMALL(ctx, g, "small", k_hmc_end, ctx->D, ctx->DP, g.ch, ip);
 }
 
-void launch_global_step(rmhmc_ctx* ctx, const IterBase& b) {
-  if (ctx->sampler == 1) { launch_hmc_global_step(ctx, b); return; }
-  if (ctx->medium) {  // transition start, one leapfrog step and transition end of every chain in ONE launch
+// One global step of the batch g: transition start, one leapfrog step and transition end of every chain
+void launch_global_step(rmhmc_ctx* ctx, Group& g, const IterBase& b) {
+  if (ctx->sampler == 1) { launch_hmc_global_step(ctx, g, b); return; }
+  if (ctx->medium) {  // ... in ONE launch
     const int guards = (ctx->flags & RMHMC_FLAG_GUARDS) ? 1 : 0;
-    for (Group& g : ctx->groups) {
-      const IterParams ip = iter_params(ctx, g, b);
-      launch(ctx, g, HEAVY, "medium", [&](hipStream_t st) {
-        launch_step_medium(ctx, g, st, guards, 0, 1, ip);
-      });
-    }
+    const IterParams ip = iter_params(ctx, b);
+    launch(ctx, "medium", [&](hipStream_t st) { launch_step_medium(ctx, g, st, guards, 0, 1, ip); });
     return;
   }
-  std::vector<Phase> ph;
-  ph.push_back([ctx, b](Group& g) { IterParams ip = iter_params(ctx, g, b); SMALL(ctx, g, "small", k_iter_begin, ctx->D, ctx->DP, g.ch, ip); });
-  step_phases(ctx, ph);
-  ph.push_back([ctx, b](Group& g) { IterParams ip = iter_params(ctx, g, b); SMALL(ctx, g, "small", k_iter_end, ctx->D, ctx->DP, g.ch, ip); });
-  run_phases(ctx, ph);
+  launch_iter_begin(ctx, g, b);
+  step_phases(ctx, g);
+  launch_iter_end(ctx, g, b);
 }
 
 // Small-problem path: one launch = `nsteps` global steps of every chain (fused_small.hip.h).
 void launch_fused(rmhmc_ctx* ctx, const IterBase& b, long long nsteps) {
+  Group& g = ctx->batch;
   while (nsteps > 0) {
     const int chunk = (int)std::min<long long>(nsteps, 4096);
-    for (Group& g : ctx->groups) {
-      FusedParams fp{};
-      fp.ip = iter_params(ctx, g, b);
-      fp.eps = ctx->eps; fp.K = ctx->K; fp.nsteps = chunk; fp.DPs = ctx->DP; fp.init_eval = 0;
-      launch(ctx, g, HEAVY, "fused", [&](hipStream_t st) {
-        hipLaunchKernelGGL(k_fused_small, dim3((unsigned)((g.n + FS_WAVES - 1) / FS_WAVES)), dim3(64 * FS_WAVES), ctx->fused_lds, st,
-                           ctx->dd, g.ch, fp);
-      });
-    }
+    FusedParams fp{};
+    fp.ip = iter_params(ctx, b);
+    fp.eps = ctx->eps; fp.K = ctx->K; fp.nsteps = chunk; fp.DPs = ctx->DP; fp.init_eval = 0;
+    launch(ctx, "fused", [&](hipStream_t st) {
+      hipLaunchKernelGGL(k_fused_small, dim3((unsigned)((g.n + FS_WAVES - 1) / FS_WAVES)), dim3(64 * FS_WAVES), ctx->fused_lds, st,
+                         ctx->dd, g.ch, fp);
+    });
     nsteps -= chunk;
     if (nsteps > 0) flow_tick(ctx, ctx->opt.inflight);  // (one launch = up to 4096 steps: at most four launches queued ahead)
   }
 }
 
-// whole-batch helpers on the main stream (callers fork/join around group work)
+// fill helpers on the context's stream
 void fill_int(rmhmc_ctx* ctx, int* p, int v, size_t n) {
   hipLaunchKernelGGL(k_fill_int, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, p, v, n);
 }
@@ -879,54 +823,30 @@ int sync(rmhmc_ctx* ctx) {
     HIPCK(hipSetDevice((ctx)->device));                                             \
   } while (0)
 
-// upload w into trj.w, zero (or upload) p, mark every chain active, evaluate the record.
-// Leaves the streams forked: callers join before downloading.
-int eval_at(rmhmc_ctx* ctx, const double* w, const double* p, bool sampler_init = false) {
-  Chains& ch = ctx->ch;
+// upload w into trj.w, zero (or upload) p, mark every chain active, evaluate the record (asynchronous: callers sync before they
+// read the downloads).  one_launch: by the one-launch step kernel where the context has it
+int eval_at(rmhmc_ctx* ctx, const double* w, const double* p, bool one_launch = false) {
+  Group& g = ctx->batch;
+  Chains& ch = g.ch;
   RC(upload_vec(ctx, ch.trj.w, w));
   if (p) RC(upload_vec(ctx, ch.p, p));
   else HIPCK(hipMemsetAsync(ch.p, 0, sizeof(double) * ctx->n * ctx->DP, ctx->stream));
   fill_int(ctx, ch.phase, 1, ctx->n);
   fill_int(ctx, ch.status, 0, ctx->n);
-  if (sampler_init && ctx->medium) {  // same arithmetic as inside the one-launch steps (bit-exact checkpoint / resume)
-    for (Group& g : ctx->groups)
-      launch(ctx, g, HEAVY, "medium", [&](hipStream_t st) {
-        launch_step_medium(ctx, g, st, 0, 1, 0, IterParams{});
-      });
+  if (one_launch && ctx->medium) {  // same arithmetic as inside the one-launch steps (bit-exact checkpoint / resume)
+    launch(ctx, "medium", [&](hipStream_t st) { launch_step_medium(ctx, g, st, 0, 1, 0, IterParams{}); });
     return RMHMC_OK;
   }
-  launch_eval_point(ctx);
+  eval_point_phases(ctx, g, false);
   return RMHMC_OK;
-}
-
-// view of the per-chain arrays for chains [off, off+n)
-Chains chains_view(const rmhmc_ctx* ctx, long long off, int n) {
-  const size_t DP = ctx->DP, Mp = ctx->Mp;
-  Chains v = ctx->ch;
-  auto vec = [&](double* p) { return p + off * DP; };
-  auto mat = [&](double* p) { return p + off * DP * DP; };
-  for (Rec* r : {&v.cur, &v.trj}) {
-    r->w = vec(r->w); r->grad = vec(r->grad); r->tr = vec(r->tr); r->L = mat(r->L); r->Ginv = mat(r->Ginv);
-    r->ljl += off; r->hld += off;
-  }
-  v.p = vec(v.p); v.p0 = vec(v.p0); v.Hcur += off; v.Hprop += off; v.tau += off;
-  v.steps_left += off; v.phase += off; v.status += off; v.nsteps_last += off; v.cstale += off; v.stale_list += off;
-  v.iter += off; v.accepted += off; v.steps_done += off;
-  v.wq = vec(v.wq); v.uq = vec(v.uq); v.PM = vec(v.PM); v.u0 = vec(v.u0); v.q = vec(v.q); v.last = vec(v.last);
-  v.Gq = mat(v.Gq); v.rv0 += off * Mp; v.rv2 += off * Mp;
-  v.n = n;
-  return v;
 }
 
 // Run-time options that live in device-visible state.  The list of the chains that have just rejected a proposal (k_iter_end appends,
 // k_crestore consumes) exists on the generic multi-launch path with c tiles when cdyn and crestore are on.
 void apply_runtime_options(rmhmc_ctx* ctx) {
-  for (Group& g : ctx->groups) {
-    const bool ok = !ctx->big && !ctx->medium && !ctx->fused && g.ctile && ctx->opt.cdyn && ctx->opt.crestore;
-    g.ch.stale_list = ok ? ctx->stale_list_alloc : nullptr;
-    g.ch.stale_count = ctx->ch.stale_count;
-  }
-  ctx->ch.stale_list = nullptr;
+  Group& g = ctx->batch;
+  const bool ok = !ctx->big && !ctx->medium && !ctx->fused && g.ctile && ctx->opt.cdyn && ctx->opt.crestore;
+  g.ch.stale_list = ok ? ctx->stale_list_alloc : nullptr;
 }
 
 }  // namespace
@@ -960,7 +880,7 @@ int rmhmc_create_opts(rmhmc_ctx** out, int32_t device_id, int64_t M, int32_t D, 
   if (D > 256) return fail(nullptr, RMHMC_ERR_UNSUPPORTED, "rmhmc_create: D > 256 is not supported (64 < D <= 256 uses the blocked large-D path)");
   if (flags & RMHMC_FLAG_ORACLE_LITERAL) return fail(nullptr, RMHMC_ERR_UNSUPPORTED, "rmhmc_create: the literal variant exists only in the CPU oracle");
   if (M > (int64_t)1 << 30 || n_chains > (int64_t)1 << 30) return fail(nullptr, RMHMC_ERR_UNSUPPORTED, "rmhmc_create: M or n_chains too large");
-  // (the row passes of the D <= 64 path address X, a chain group's c tiles and its leverages with 32-bit byte offsets from a buffer
+  // (the row passes of the D <= 64 path address X, the batch's c tiles and its leverages with 32-bit byte offsets from a buffer
   //  descriptor's base: buf_rsrc in kernels.hip.h)
   if (D <= 64 && (M + 63) / 64 * 64 * (int64_t)(16 * ((D + 15) / 16)) * 8 >= (int64_t)1 << 32)
     return fail(nullptr, RMHMC_ERR_UNSUPPORTED, "rmhmc_create: the data matrix of the D <= 64 path must stay below 4 GB");
@@ -996,7 +916,7 @@ int rmhmc_create_opts(rmhmc_ctx** out, int32_t device_id, int64_t M, int32_t D, 
     RC(dalloc(ctx, &Xr, Mp * DP)); RC(dalloc(ctx, &Xt, DP * Mp)); RC(dalloc(ctx, &t, Mp));
     ctx->dd.Xr = Xr; ctx->dd.Xt = Xt; ctx->dd.t = t;
     ctx->dd.M = (int)M; ctx->dd.Mp = ctx->Mp; ctx->dd.D = D; ctx->dd.DP = ctx->DP; ctx->dd.nblk = ctx->nblk;
-    Chains& ch = ctx->ch;
+    Chains& ch = ctx->batch.ch;
     ch.n = (int)n;
     for (Rec* r : {&ch.cur, &ch.trj}) {
       RC(dalloc(ctx, &r->w, n * DP)); RC(dalloc(ctx, &r->grad, n * DP)); RC(dalloc(ctx, &r->tr, n * DP));
@@ -1011,10 +931,8 @@ int rmhmc_create_opts(rmhmc_ctx** out, int32_t device_id, int64_t M, int32_t D, 
     RC(dalloc(ctx, &ch.wq, n * DP)); RC(dalloc(ctx, &ch.uq, n * DP)); RC(dalloc(ctx, &ch.PM, n * DP)); RC(dalloc(ctx, &ch.u0, n * DP));
     RC(dalloc(ctx, &ch.q, n * DP)); RC(dalloc(ctx, &ch.last, n * DP)); RC(dalloc(ctx, &ch.Gq, n * DP * DP));
     RC(dalloc(ctx, &ch.rv0, n * Mp)); RC(dalloc(ctx, &ch.rv2, n * Mp));
-    ctx->groups.resize(1);
-    {
-      Group& g = ctx->groups[0];
-      g.off = 0;
+    Group& g = ctx->batch;
+    {  // row splits and partial planes
       g.n = (int)n_chains;
       // row splits of the 16-chains-per-wave passes (option nsplit_waves).  D <= 64: ~2048 wavefronts per launch = ONE round of two
       // four-wave workgroups per CU - measured against the 6144 of rounds 1-2 (three rounds) on one box, interleaved: 14.73-14.92
@@ -1031,7 +949,6 @@ int rmhmc_create_opts(rmhmc_ctx** out, int32_t device_id, int64_t M, int32_t D, 
       // 1.99 ms per step, the int8 path at 128-512 chains 10-30 % less; profiles/r02_fp64_batch_sweep.txt)
       if (ns > ctx->opt.nsplit_max) ns = ctx->opt.nsplit_max;
       g.nsplit = (int)ns;
-      g.ch = chains_view(ctx, g.off, g.n);
       RC(dalloc(ctx, &g.ch.qpart, (size_t)g.nsplit * g.n * DP));
       RC(dalloc(ctx, &g.ch.gpart, (size_t)g.nsplit * g.n * DP));
       RC(dalloc(ctx, &g.ch.ljl_part, (size_t)g.n * g.nsplit));
@@ -1079,7 +996,7 @@ int rmhmc_create_opts(rmhmc_ctx** out, int32_t device_id, int64_t M, int32_t D, 
       ctx->i8_NRp = (ctx->Mp + ctx->i8_bn - 1) / ctx->i8_bn * ctx->i8_bn;
       RC(dalloc(ctx, &ctx->d_Zt, (size_t)S * ctx->i8_nkp * ctx->i8_NRp * 32));
       RC(dalloc(ctx, &ctx->d_zre, (size_t)ctx->i8_NRp)); RC(dalloc(ctx, &ctx->d_zscale, (size_t)ctx->i8_NRp));
-      for (Group& g : ctx->groups) {
+      {  // slice planes and accumulators of the batch
         g.nCp = (g.n + I8_BM - 1) / I8_BM * I8_BM;
         RC(dalloc(ctx, &g.Vs, (size_t)S * ctx->i8_nks * g.nCp * 32));
         RC(dalloc(ctx, &g.vbad, (size_t)g.nCp));
@@ -1136,7 +1053,7 @@ int rmhmc_create_opts(rmhmc_ctx** out, int32_t device_id, int64_t M, int32_t D, 
             HIPCK(hipFuncSetAttribute((const void*)kfn3, hipFuncAttributeMaxDynamicSharedMemorySize, (i8_lds_bytes<S_, 1, 1>())));
           });
     }
-    for (Group& g : ctx->groups) {  // planes of the fp64 small-batch assembly (shared with the int8 k-split planes, whichever is larger)
+    {  // planes of the fp64 small-batch assembly (shared with the int8 k-split planes, whichever is larger)
       const int need = std::max(g.fsplit, g.ksplit_a);
       if (g.fsplit > 1 && (!g.Gpart || g.fsplit > g.ksplit_a)) RC(dalloc(ctx, &g.Gpart, (size_t)need * g.n * ctx->DP * ctx->DP));
     }
@@ -1224,8 +1141,8 @@ int rmhmc_set_option(rmhmc_ctx* ctx, const char* key, int64_t value) {
   ctx->opt.*(d->slot) = value;
   apply_runtime_options(ctx);
   if (ctx->stale_list_alloc) {  // a list left over from a run with the other setting must not be consumed
-    HIPCK(hipMemsetAsync(ctx->ch.stale_count, 0, sizeof(int), ctx->stream));
-    fill_int(ctx, ctx->ch.cstale, 1, ctx->n);  // (every chain's tiles count as stale: the next first pass recomputes them)
+    HIPCK(hipMemsetAsync(ctx->batch.ch.stale_count, 0, sizeof(int), ctx->stream));
+    fill_int(ctx, ctx->batch.ch.cstale, 1, ctx->n);  // (every chain's tiles count as stale: the next first pass recomputes them)
     HIPCK(hipStreamSynchronize(ctx->stream));
   }
   return RMHMC_OK;
@@ -1345,7 +1262,7 @@ int rmhmc_log_posterior(rmhmc_ctx* ctx, const double* w, double* ljl_out) {
   if (!w || !ljl_out) return fail(ctx, RMHMC_ERR_INVALID, "log_posterior: null pointer");
   ctx->chains_ready = false;
   RC(eval_at(ctx, w, nullptr));
-  RC(download(ctx, ljl_out, ctx->ch.trj.ljl, ctx->n));
+  RC(download(ctx, ljl_out, ctx->batch.ch.trj.ljl, ctx->n));
   return sync(ctx);
 }
 
@@ -1360,10 +1277,10 @@ int rmhmc_metric(rmhmc_ctx* ctx, const double* w, double* G_out, double* half_lo
   RC(rc_eval);
   if (G_out)
     for (int64_t c = 0; c < ctx->n; ++c)  // strip the padding: [DP][DP] -> [D][D]
-      HIPCK(hipMemcpy2DAsync(G_out + c * ctx->D * ctx->D, ctx->D * 8, (ctx->big ? ctx->d_Gcopy : ctx->ch.Gq) + c * ctx->DP * ctx->DP, ctx->DP * 8, ctx->D * 8, ctx->D,
+      HIPCK(hipMemcpy2DAsync(G_out + c * ctx->D * ctx->D, ctx->D * 8, (ctx->big ? ctx->d_Gcopy : ctx->batch.ch.Gq) + c * ctx->DP * ctx->DP, ctx->DP * 8, ctx->D * 8, ctx->D,
                              hipMemcpyDeviceToHost, ctx->stream));
-  if (half_logdet_out) RC(download(ctx, half_logdet_out, ctx->ch.trj.hld, ctx->n));
-  if (grad_out) RC(download_vec(ctx, grad_out, ctx->ch.trj.grad));
+  if (half_logdet_out) RC(download(ctx, half_logdet_out, ctx->batch.ch.trj.hld, ctx->n));
+  if (grad_out) RC(download_vec(ctx, grad_out, ctx->batch.ch.trj.grad));
   RC(sync(ctx));
   if (G_out && ctx->i8) {  // the int8 assembly writes the lower triangle only
     const int64_t D = ctx->D;
@@ -1379,8 +1296,8 @@ int rmhmc_metric_terms(rmhmc_ctx* ctx, const double* w, const double* p, double*
   if (!w) return fail(ctx, RMHMC_ERR_INVALID, "metric_terms: null pointer");
   ctx->chains_ready = false;
   RC(eval_at(ctx, w, p));
-  if (trace_out) RC(download_vec(ctx, trace_out, ctx->ch.trj.tr));
-  if (quad_out && p) RC(download_vec(ctx, quad_out, ctx->ch.last));
+  if (trace_out) RC(download_vec(ctx, trace_out, ctx->batch.ch.trj.tr));
+  if (quad_out && p) RC(download_vec(ctx, quad_out, ctx->batch.ch.last));
   return sync(ctx);
 }
 
@@ -1398,53 +1315,52 @@ int rmhmc_leapfrog(rmhmc_ctx* ctx, double* w, double* p, double eps, const int32
   RC(upload(ctx, ctx->d_nsteps, nsteps, ctx->n));
   RC(upload(ctx, ctx->d_dir, dir, ctx->n));
   RC(eval_at(ctx, w, p));
-  for (Group& g : ctx->groups)
-    launch(ctx, g, LIGHT, "small", [&](hipStream_t st) {
-      hipLaunchKernelGGL(k_set_leapfrog, dim3((unsigned)((g.n + 255) / 256)), dim3(256), 0, st, g.n, ctx->d_nsteps + g.off, ctx->d_dir + g.off, g.ch);
-    });
+  Group& g = ctx->batch;
+  launch(ctx, "small", [&](hipStream_t st) {
+    hipLaunchKernelGGL(k_set_leapfrog, dim3((unsigned)((g.n + 255) / 256)), dim3(256), 0, st, g.n, ctx->d_nsteps, ctx->d_dir, g.ch);
+  });
   for (int s = 0; s < maxs; ++s) {
-    launch_step(ctx);
-    for (Group& g : ctx->groups)
-      launch(ctx, g, LIGHT, "small", [&](hipStream_t st) {
-        hipLaunchKernelGGL(k_park_finished, dim3((unsigned)((g.n + 255) / 256)), dim3(256), 0, st, g.n, g.ch);
-      });
+    step_phases(ctx, g);
+    launch(ctx, "small", [&](hipStream_t st) {
+      hipLaunchKernelGGL(k_park_finished, dim3((unsigned)((g.n + 255) / 256)), dim3(256), 0, st, g.n, g.ch);
+    });
   }
-  RC(download_vec(ctx, w, ctx->ch.trj.w));
-  RC(download_vec(ctx, p, ctx->ch.p));
-  if (half_logdet_out) RC(download(ctx, half_logdet_out, ctx->ch.trj.hld, ctx->n));
-  if (status_out) RC(download(ctx, status_out, ctx->ch.status, ctx->n));
+  RC(download_vec(ctx, w, ctx->batch.ch.trj.w));
+  RC(download_vec(ctx, p, ctx->batch.ch.p));
+  if (half_logdet_out) RC(download(ctx, half_logdet_out, ctx->batch.ch.trj.hld, ctx->n));
+  if (status_out) RC(download(ctx, status_out, ctx->batch.ch.status, ctx->n));
   return sync(ctx);
 }
 
 // shared by transition / sample / chains_init: evaluate the record at theta0 and commit it as the
-// current point of every chain
-static int init_chains(rmhmc_ctx* ctx, const double* theta0_host /* [n][D] or NULL */) {
+// current point of every chain.  By default the evaluation is that of the context's stepping path (same arithmetic as inside its
+// steps); the samplers that step with the generic kernels whatever the context say which one-launch evaluations they may not get.
+static int init_chains(rmhmc_ctx* ctx, const double* theta0_host /* [n][D] or NULL */, bool allow_fused = true, bool allow_medium = true) {
+  Group& g = ctx->batch;
   std::vector<double> th;
   if (!theta0_host) {
     th.assign((size_t)ctx->n * ctx->D, 1e-3);  // rmhmc.py:27
     theta0_host = th.data();
   }
-  if (ctx->fused) {  // the fused path evaluates its own initial record (same arithmetic as inside its steps)
-    RC(upload_vec(ctx, ctx->ch.cur.w, theta0_host));
-    for (Group& g : ctx->groups) {
-      FusedParams fp{};
-      fp.ip = iter_params(ctx, g, IterBase{0, 0, 0, nullptr, false, false});
-      fp.eps = ctx->eps; fp.K = ctx->K; fp.nsteps = 0; fp.DPs = ctx->DP; fp.init_eval = 1;
-      launch(ctx, g, HEAVY, "fused", [&](hipStream_t st) {
-        hipLaunchKernelGGL(k_fused_small, dim3((unsigned)((g.n + FS_WAVES - 1) / FS_WAVES)), dim3(64 * FS_WAVES), ctx->fused_lds, st,
-                           ctx->dd, g.ch, fp);
-      });
-    }
+  if (ctx->fused && allow_fused) {  // the fused path evaluates its own initial record (same arithmetic as inside its steps)
+    RC(upload_vec(ctx, g.ch.cur.w, theta0_host));
+    FusedParams fp{};
+    fp.ip = iter_params(ctx, IterBase{0, 0, 0, nullptr, false, false});
+    fp.eps = ctx->eps; fp.K = ctx->K; fp.nsteps = 0; fp.DPs = ctx->DP; fp.init_eval = 1;
+    launch(ctx, "fused", [&](hipStream_t st) {
+      hipLaunchKernelGGL(k_fused_small, dim3((unsigned)((g.n + FS_WAVES - 1) / FS_WAVES)), dim3(64 * FS_WAVES), ctx->fused_lds, st,
+                         ctx->dd, g.ch, fp);
+    });
   } else {
-    RC(eval_at(ctx, theta0_host, nullptr, true));
-    for (Group& g : ctx->groups) SMALL(ctx, g, "small", k_commit_all, ctx->D, ctx->DP, g.ch);
+    RC(eval_at(ctx, theta0_host, nullptr, allow_medium));
+    SMALL(ctx, g, "small", k_commit_all, ctx->D, ctx->DP, g.ch);
   }
-  fill_int(ctx, ctx->ch.phase, 0, ctx->n);
-  fill_int(ctx, ctx->ch.steps_left, 0, ctx->n);
-  fill_int(ctx, ctx->ch.status, 0, ctx->n);
-  fill_ll(ctx, ctx->ch.iter, 0, ctx->n);
-  fill_ll(ctx, ctx->ch.accepted, 0, ctx->n);
-  fill_ll(ctx, ctx->ch.steps_done, 0, ctx->n);
+  fill_int(ctx, ctx->batch.ch.phase, 0, ctx->n);
+  fill_int(ctx, ctx->batch.ch.steps_left, 0, ctx->n);
+  fill_int(ctx, ctx->batch.ch.status, 0, ctx->n);
+  fill_ll(ctx, ctx->batch.ch.iter, 0, ctx->n);
+  fill_ll(ctx, ctx->batch.ch.accepted, 0, ctx->n);
+  fill_ll(ctx, ctx->batch.ch.steps_done, 0, ctx->n);
   HIPCK(hipMemsetAsync(ctx->d_done, 0, sizeof(int), ctx->stream));
   return sync(ctx);  // theta0 staging vector goes out of scope
 }
@@ -1465,23 +1381,24 @@ int rmhmc_transition(rmhmc_ctx* ctx, double* w, const double* z, const double* u
   if (ctx->fused) {
     launch_fused(ctx, ib, L);
   } else {
-    launch_iter_begin(ctx, ib);
-    launch_iter_end(ctx, ib);  // trajectories of zero steps
+    Group& g = ctx->batch;
+    launch_iter_begin(ctx, g, ib);
+    launch_iter_end(ctx, g, ib);  // trajectories of zero steps
     for (int s = 0; s < L; ++s) {
-      launch_step(ctx);
-      launch_iter_end(ctx, ib);
+      step_phases(ctx, g);
+      launch_iter_end(ctx, g, ib);
     }
   }
   std::vector<long long> acc(ctx->n);
-  RC(download_vec(ctx, w, ctx->ch.cur.w));
-  RC(download(ctx, acc.data(), ctx->ch.accepted, ctx->n));
-  if (nsteps_out) RC(download(ctx, nsteps_out, ctx->ch.nsteps_last, ctx->n));
-  if (H_cur_out) RC(download(ctx, H_cur_out, ctx->ch.Hcur, ctx->n));
-  if (H_prop_out) RC(download(ctx, H_prop_out, ctx->ch.Hprop, ctx->n));
-  if (w_prop_out) RC(download_vec(ctx, w_prop_out, ctx->ch.trj.w));
-  if (p_prop_out) RC(download_vec(ctx, p_prop_out, ctx->ch.p));
-  if (half_logdet_prop_out) RC(download(ctx, half_logdet_prop_out, ctx->ch.trj.hld, ctx->n));
-  if (status_out) RC(download(ctx, status_out, ctx->ch.status, ctx->n));
+  RC(download_vec(ctx, w, ctx->batch.ch.cur.w));
+  RC(download(ctx, acc.data(), ctx->batch.ch.accepted, ctx->n));
+  if (nsteps_out) RC(download(ctx, nsteps_out, ctx->batch.ch.nsteps_last, ctx->n));
+  if (H_cur_out) RC(download(ctx, H_cur_out, ctx->batch.ch.Hcur, ctx->n));
+  if (H_prop_out) RC(download(ctx, H_prop_out, ctx->batch.ch.Hprop, ctx->n));
+  if (w_prop_out) RC(download_vec(ctx, w_prop_out, ctx->batch.ch.trj.w));
+  if (p_prop_out) RC(download_vec(ctx, p_prop_out, ctx->batch.ch.p));
+  if (half_logdet_prop_out) RC(download(ctx, half_logdet_prop_out, ctx->batch.ch.trj.hld, ctx->n));
+  if (status_out) RC(download(ctx, status_out, ctx->batch.ch.status, ctx->n));
   RC(sync(ctx));
   if (accepted_out) for (int64_t c = 0; c < ctx->n; ++c) accepted_out[c] = (int32_t)acc[c];
   return RMHMC_OK;
@@ -1499,14 +1416,14 @@ struct StepGraph {
   }
 };
 static bool step_graph_usable(const rmhmc_ctx* ctx, long long nsteps) {
-  if (ctx->groups.size() != 1 || ctx->timing || nsteps < 8) return false;
+  if (ctx->timing || nsteps < 8) return false;
   if (ctx->fused && ctx->sampler == 0) return false;
   if (ctx->medium && ctx->sampler == 0) return false;  // (the global step is ONE launch there: a one-node graph only costs its instantiation)
   return ctx->opt.graph != 0;
 }
 static bool build_step_graph(rmhmc_ctx* ctx, const IterBase& ib, StepGraph& sg) {
   if (hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return false;
-  launch_global_step(ctx, ib);
+  launch_global_step(ctx, ctx->batch, ib);
   if (hipStreamEndCapture(ctx->stream, &sg.graph) != hipSuccess || !sg.graph) { (void)hipGetLastError(); return false; }
   if (hipGraphInstantiate(&sg.exec, sg.graph, nullptr, nullptr, 0) != hipSuccess) { (void)hipGetLastError(); sg.exec = nullptr; return false; }
   return true;
@@ -1516,14 +1433,14 @@ static void run_generic_steps(rmhmc_ctx* ctx, const IterBase& ib, long long nste
   if (sg && sg->exec) {
     for (long long s = 0; s < nsteps; ++s) { (void)hipGraphLaunch(sg->exec, ctx->stream); flow_tick(ctx); }
   } else {
-    for (long long s = 0; s < nsteps; ++s) { launch_global_step(ctx, ib); flow_tick(ctx); }
+    for (long long s = 0; s < nsteps; ++s) { launch_global_step(ctx, ctx->batch, ib); flow_tick(ctx); }
   }
 }
 
 // number of chains that reached the iteration limit and the completed transitions of the slowest chain, in one round trip
 static int poll_progress(rmhmc_ctx* ctx, int* done, long long* min_iter) {
   HIPCK(hipMemsetAsync(ctx->d_miniter, 0xff, sizeof(unsigned long long), ctx->stream));
-  hipLaunchKernelGGL(k_min_iter, dim3((unsigned)((ctx->n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->ch.iter, (size_t)ctx->n, ctx->d_miniter);
+  hipLaunchKernelGGL(k_min_iter, dim3((unsigned)((ctx->n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->batch.ch.iter, (size_t)ctx->n, ctx->d_miniter);
   unsigned long long mi = 0;
   HIPCK(hipMemcpyAsync(done, ctx->d_done, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   HIPCK(hipMemcpyAsync(&mi, ctx->d_miniter, sizeof(mi), hipMemcpyDeviceToHost, ctx->stream));
@@ -1535,8 +1452,8 @@ static int poll_progress(rmhmc_ctx* ctx, int* done, long long* min_iter) {
 // rmhmc_set_progress: hand the caller the counters at a moment when every chain has completed at least `iters` transitions
 static int report_progress(rmhmc_ctx* ctx, int event, long long iters) {
   std::vector<long long> acc(ctx->n), it(ctx->n);
-  RC(download(ctx, acc.data(), ctx->ch.accepted, ctx->n));
-  RC(download(ctx, it.data(), ctx->ch.iter, ctx->n));
+  RC(download(ctx, acc.data(), ctx->batch.ch.accepted, ctx->n));
+  RC(download(ctx, it.data(), ctx->batch.ch.iter, ctx->n));
   RC(sync(ctx));
   long long tot = 0, tit = 0;
   for (long long a : acc) tot += a;
@@ -1622,17 +1539,15 @@ static int run_phase(rmhmc_ctx* ctx, const IterBase& ib, long long from, bool at
   return RMHMC_OK;
 }
 
-// One global step on the first na chains only (na a multiple of 128 or n).  The single group's view is narrowed for the launches of the
-// step: every kernel takes its chain count and its partial-plane strides from the group, so producers and consumers agree.
+// One global step on the first na chains only (na a multiple of 128 or n), on a narrowed copy of the batch: every kernel takes its
+// chain count and its partial-plane strides from the batch it is handed, so producers and consumers agree.
 static void launch_global_step_prefix(rmhmc_ctx* ctx, const IterBase& ib, int na) {
-  Group& g = ctx->groups[0];
-  const Group saved = g;
+  Group g = ctx->batch;
   g.n = na; g.ch.n = na;
   if (g.nCp) g.nCp = (na + I8_BM - 1) / I8_BM * I8_BM;
   // (row ranges, k-split planes and row splits stay as chosen for the whole batch: every chain's sums keep their order, so the
   // results are bit-identical to the unsorted run)
-  launch_global_step(ctx, ib);
-  g = saved;
+  launch_global_step(ctx, g, ib);
 }
 
 // Work-sorted phase B.  The trajectory lengths do not depend on the state (RandomStep = ceil(rand() L), rmhmc.py:89), so the number of
@@ -1663,7 +1578,7 @@ static int run_sorted_phase(rmhmc_ctx* ctx, const IterBase& ib, const std::vecto
   for (long long s = Tmin; s < Tmax; ++s) {
     while (na > 0 && T[na - 1] <= s) --na;  // chains with T > s are still running: positions [0, na)
     const int nar = std::min(n, (na + 127) / 128 * 128);
-    if (nar == n) launch_global_step(ctx, ib);
+    if (nar == n) launch_global_step(ctx, ctx->batch, ib);
     else launch_global_step_prefix(ctx, ib, nar);
     flow_tick(ctx);
     if (ticking && (s - Tmin) % chunk == chunk - 1) { RC(poll_progress(ctx, &done, &mi)); RC(progress_fire(ctx, mi)); }
@@ -1679,10 +1594,10 @@ static int run_sorted_phase(rmhmc_ctx* ctx, const IterBase& ib, const std::vecto
 static int sample_core(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, const double* theta0, double* d_samples, double* seconds_out) {
   const long long S = n_iter - burn_in;
   const int n = (int)ctx->n;
-  // work-sorted layout (see run_sorted_phase): generic and one-launch stepping paths of the RMHMC sampler, one chain group
+  // work-sorted layout (see run_sorted_phase): generic and one-launch stepping paths of the RMHMC sampler
   std::vector<long long> T;
   std::vector<double> th_perm;
-  bool sorted = ctx->sampler == 0 && ctx->groups.size() == 1 && !ctx->fused && n >= 2 && n_iter > burn_in + 1;
+  bool sorted = ctx->sampler == 0 && !ctx->fused && n >= 2 && n_iter > burn_in + 1;
   ctx->progress_next = ctx->progress_first;
   sorted = sorted && ctx->opt.sorted;
   if (sorted) {
@@ -1710,7 +1625,7 @@ static int sample_core(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, const do
     // the timed phase B covers exactly the post-burn-in transitions (TimeTaken, rmhmc.py:194-198)
     const IterBase ipA{burn_in + 1, burn_in, S, d_samples, false, true};
     RC(run_phase(ctx, ipA, 0));
-    HIPCK(hipMemcpyAsync(ctx->d_steps0, ctx->ch.steps_done, sizeof(long long) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCK(hipMemcpyAsync(ctx->d_steps0, ctx->batch.ch.steps_done, sizeof(long long) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
     HIPCK(hipMemsetAsync(ctx->d_done, 0, sizeof(int), ctx->stream));
     RC(sync(ctx));
     if (ctx->progress_fn) RC(report_progress(ctx, RMHMC_EV_BURNIN_DONE, burn_in + 1));  // rmhmc.py:194-196: banner, then the timer starts
@@ -1722,10 +1637,10 @@ static int sample_core(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, const do
     }
     RC(sync(ctx));
     if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    hipLaunchKernelGGL(k_sub_ll, dim3((unsigned)((ctx->n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_steps0, ctx->ch.steps_done, (size_t)ctx->n);
+    hipLaunchKernelGGL(k_sub_ll, dim3((unsigned)((ctx->n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_steps0, ctx->batch.ch.steps_done, (size_t)ctx->n);
     if (sorted) {  // counters back into the caller's order: d_T[0..n) accepted, d_T[n..2n) post-burn-in steps
       const dim3 grid((unsigned)((n + 255) / 256));
-      hipLaunchKernelGGL(k_scatter_ll, grid, dim3(256), 0, ctx->stream, ctx->d_T, ctx->ch.accepted, ctx->d_orig, (size_t)n);
+      hipLaunchKernelGGL(k_scatter_ll, grid, dim3(256), 0, ctx->stream, ctx->d_T, ctx->batch.ch.accepted, ctx->d_orig, (size_t)n);
       hipLaunchKernelGGL(k_scatter_ll, grid, dim3(256), 0, ctx->stream, ctx->d_T + n, ctx->d_steps0, ctx->d_orig, (size_t)n);
     }
     return RMHMC_OK;
@@ -1737,7 +1652,7 @@ static int sample_core(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, const do
 // the counters of sample_core to host or device int64 arrays (either may be NULL)
 static int sample_counters(rmhmc_ctx* ctx, int64_t* accept_out, int64_t* steps_out, hipMemcpyKind kind) {
   static_assert(sizeof(long long) == sizeof(int64_t), "int64");
-  const long long* acc = ctx->counters_sorted ? ctx->d_T : ctx->ch.accepted;
+  const long long* acc = ctx->counters_sorted ? ctx->d_T : ctx->batch.ch.accepted;
   const long long* stp = ctx->counters_sorted ? ctx->d_T + ctx->n : ctx->d_steps0;
   if (accept_out) HIPCK(hipMemcpyAsync(accept_out, acc, sizeof(int64_t) * ctx->n, kind, ctx->stream));
   if (steps_out) HIPCK(hipMemcpyAsync(steps_out, stp, sizeof(int64_t) * ctx->n, kind, ctx->stream));
@@ -1848,20 +1763,21 @@ int rmhmc_sample_stats_dev(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int3
 static int hmc_init_chains(rmhmc_ctx* ctx, const double* theta0_host /* [n][D] or NULL: zeros, hmc.py:27 */) {
   std::vector<double> th;
   if (!theta0_host) { th.assign((size_t)ctx->n * ctx->D, 0.0); theta0_host = th.data(); }
-  RC(upload_vec(ctx, ctx->ch.trj.w, theta0_host));
-  fill_int(ctx, ctx->ch.phase, 1, ctx->n);
+  RC(upload_vec(ctx, ctx->batch.ch.trj.w, theta0_host));
+  fill_int(ctx, ctx->batch.ch.phase, 1, ctx->n);
+  Group& g = ctx->batch;
   if (ctx->hmc_traj) {
-    for (Group& g : ctx->groups) launch_hmc_traj(ctx, g, 1);
+    launch_hmc_traj(ctx, g, 1);
   } else {
-    for (Group& g : ctx->groups) launch_rowpass<RP_G>(ctx, g, g.ch.trj.w, nullptr);
-    for (Group& g : ctx->groups) SMALL(ctx, g, "small", k_hmc_init, ctx->dd, g.ch, g.nsplit);
+    launch_rowpass<RP_G>(ctx, g, g.ch.trj.w, nullptr);
+    SMALL(ctx, g, "small", k_hmc_init, ctx->dd, g.ch, g.nsplit);
   }
-  fill_int(ctx, ctx->ch.phase, 0, ctx->n);
-  fill_int(ctx, ctx->ch.steps_left, 0, ctx->n);
-  fill_int(ctx, ctx->ch.status, 0, ctx->n);
-  fill_ll(ctx, ctx->ch.iter, 0, ctx->n);
-  fill_ll(ctx, ctx->ch.accepted, 0, ctx->n);
-  fill_ll(ctx, ctx->ch.steps_done, 0, ctx->n);
+  fill_int(ctx, ctx->batch.ch.phase, 0, ctx->n);
+  fill_int(ctx, ctx->batch.ch.steps_left, 0, ctx->n);
+  fill_int(ctx, ctx->batch.ch.status, 0, ctx->n);
+  fill_ll(ctx, ctx->batch.ch.iter, 0, ctx->n);
+  fill_ll(ctx, ctx->batch.ch.accepted, 0, ctx->n);
+  fill_ll(ctx, ctx->batch.ch.steps_done, 0, ctx->n);
   HIPCK(hipMemsetAsync(ctx->d_done, 0, sizeof(int), ctx->stream));
   return sync(ctx);
 }
@@ -1879,15 +1795,15 @@ int rmhmc_hmc_transition(rmhmc_ctx* ctx, double* w, const double* z, const doubl
     RC(upload(ctx, ctx->d_ulen, u_len, ctx->n));
     RC(upload(ctx, ctx->d_uacc, u_acc, ctx->n));
     const IterBase ib{1, 0, 0, nullptr, true, false};
-    for (int s = 0; s < L; ++s) launch_hmc_global_step(ctx, ib);
+    for (int s = 0; s < L; ++s) launch_hmc_global_step(ctx, ctx->batch, ib);
     std::vector<long long> acc(ctx->n);
-    RC(download_vec(ctx, w, ctx->ch.cur.w));
-    RC(download(ctx, acc.data(), ctx->ch.accepted, ctx->n));
-    if (nsteps_out) RC(download(ctx, nsteps_out, ctx->ch.nsteps_last, ctx->n));
-    if (H_cur_out) RC(download(ctx, H_cur_out, ctx->ch.Hcur, ctx->n));
-    if (H_prop_out) RC(download(ctx, H_prop_out, ctx->ch.Hprop, ctx->n));
-    if (w_prop_out) RC(download_vec(ctx, w_prop_out, ctx->ch.trj.w));
-    if (p_prop_out) RC(download_vec(ctx, p_prop_out, ctx->ch.p));
+    RC(download_vec(ctx, w, ctx->batch.ch.cur.w));
+    RC(download(ctx, acc.data(), ctx->batch.ch.accepted, ctx->n));
+    if (nsteps_out) RC(download(ctx, nsteps_out, ctx->batch.ch.nsteps_last, ctx->n));
+    if (H_cur_out) RC(download(ctx, H_cur_out, ctx->batch.ch.Hcur, ctx->n));
+    if (H_prop_out) RC(download(ctx, H_prop_out, ctx->batch.ch.Hprop, ctx->n));
+    if (w_prop_out) RC(download_vec(ctx, w_prop_out, ctx->batch.ch.trj.w));
+    if (p_prop_out) RC(download_vec(ctx, p_prop_out, ctx->batch.ch.p));
     RC(sync(ctx));
     if (accepted_out) for (int64_t c = 0; c < ctx->n; ++c) accepted_out[c] = (int32_t)acc[c];
     return RMHMC_OK;
@@ -1912,7 +1828,7 @@ int rmhmc_hmc_sample(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L,
     RC(hmc_init_chains(ctx, theta0));
     const IterBase ipA{burn_in + 1, burn_in, S, d_samples, false, true};
     RC(run_phase(ctx, ipA, 0, false, true));
-    HIPCK(hipMemcpyAsync(ctx->d_steps0, ctx->ch.steps_done, sizeof(long long) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCK(hipMemcpyAsync(ctx->d_steps0, ctx->batch.ch.steps_done, sizeof(long long) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
     HIPCK(hipMemsetAsync(ctx->d_done, 0, sizeof(int), ctx->stream));
     RC(sync(ctx));
     if (ctx->progress_fn) RC(report_progress(ctx, RMHMC_EV_BURNIN_DONE, burn_in + 1));  // hmc.py:92-94
@@ -1930,8 +1846,8 @@ int rmhmc_hmc_sample(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L,
     if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     HIPCK(hipMemcpyAsync(samples_out, d_samples, sizeof(double) * (size_t)ctx->n * S * ctx->D, hipMemcpyDeviceToHost, ctx->stream));
     std::vector<long long> a(ctx->n), s1(ctx->n), s0(ctx->n);
-    RC(download(ctx, a.data(), ctx->ch.accepted, ctx->n));
-    RC(download(ctx, s1.data(), ctx->ch.steps_done, ctx->n));
+    RC(download(ctx, a.data(), ctx->batch.ch.accepted, ctx->n));
+    RC(download(ctx, s1.data(), ctx->batch.ch.steps_done, ctx->n));
     RC(download(ctx, s0.data(), ctx->d_steps0, ctx->n));
     RC(sync(ctx));
     for (int64_t c = 0; c < ctx->n; ++c) {
@@ -1946,24 +1862,20 @@ int rmhmc_hmc_sample(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L,
 }
 
 // ---- simplified manifold MALA (BLR_mMALA_Simp.m) -------------------------------------------------------------
-static void launch_mmala_step(rmhmc_ctx* ctx, const IterBase& b) {
-  std::vector<Phase> ph;
+static void launch_mmala_step(rmhmc_ctx* ctx, Group& g, const IterBase& b) {
   const double eps = ctx->eps;
   const int full = (ctx->flags & RMHMC_FLAG_MMALA_FULL) ? 1 : 0;
-  ph.push_back([ctx, b, eps, full](Group& g) { IterParams ip = iter_params(ctx, g, b); SMALL(ctx, g, "small", k_mmala_begin, ctx->D, ctx->DP, g.ch, ip, eps, full); });
-  eval_point_phases(ctx, ph, false, full ? 2 : 1);
-  ph.push_back([ctx, b, eps, full](Group& g) { IterParams ip = iter_params(ctx, g, b); SMALL(ctx, g, "small", k_mmala_end, ctx->D, ctx->DP, g.ch, ip, eps, full); });
-  run_phases(ctx, ph);
+  const IterParams ip = iter_params(ctx, b);
+  SMALL(ctx, g, "small", k_mmala_begin, ctx->D, ctx->DP, g.ch, ip, eps, full);
+  eval_point_phases(ctx, g, false, full ? 2 : 1);
+  SMALL(ctx, g, "small", k_mmala_end, ctx->D, ctx->DP, g.ch, ip, eps, full);
 }
-// record at theta0 (generic kernels; mMALA never uses the fused stepping kernel)
-static int mmala_init(rmhmc_ctx* ctx, const double* theta0_host) {
+// record at theta0: mMALA never uses the fused stepping kernel, so not by its evaluation either; by the one-launch step kernel's where
+// the context has it, unless the caller (IWLS) wants the generic kernels throughout
+static int mmala_init(rmhmc_ctx* ctx, const double* theta0_host, bool allow_medium = true) {
   std::vector<double> th;
   if (!theta0_host) { th.assign((size_t)ctx->n * ctx->D, 0.0); theta0_host = th.data(); }  // BLR_mMALA_Simp.m:175
-  const bool fused = ctx->fused;
-  ctx->fused = false;
-  const int rc = init_chains(ctx, theta0_host);
-  ctx->fused = fused;
-  return rc;
+  return init_chains(ctx, theta0_host, false, allow_medium);
 }
 
 int rmhmc_mmala_transition(rmhmc_ctx* ctx, double* w, const double* z, const double* u_acc, double eps, int32_t* accepted_out,
@@ -1976,12 +1888,12 @@ int rmhmc_mmala_transition(rmhmc_ctx* ctx, double* w, const double* z, const dou
   RC(upload(ctx, ctx->d_z, z, (size_t)ctx->n * ctx->D));
   RC(upload(ctx, ctx->d_uacc, u_acc, ctx->n));
   const IterBase ib{1, 0, 0, nullptr, true, false};
-  launch_mmala_step(ctx, ib);
+  launch_mmala_step(ctx, ctx->batch, ib);
   std::vector<long long> acc(ctx->n);
-  RC(download_vec(ctx, w, ctx->ch.cur.w));
-  RC(download(ctx, acc.data(), ctx->ch.accepted, ctx->n));
-  if (ratio_out) RC(download(ctx, ratio_out, ctx->ch.Hprop, ctx->n));
-  if (w_prop_out) RC(download_vec(ctx, w_prop_out, ctx->ch.trj.w));
+  RC(download_vec(ctx, w, ctx->batch.ch.cur.w));
+  RC(download(ctx, acc.data(), ctx->batch.ch.accepted, ctx->n));
+  if (ratio_out) RC(download(ctx, ratio_out, ctx->batch.ch.Hprop, ctx->n));
+  if (w_prop_out) RC(download_vec(ctx, w_prop_out, ctx->batch.ch.trj.w));
   RC(sync(ctx));
   if (accepted_out) for (int64_t c = 0; c < ctx->n; ++c) accepted_out[c] = (int32_t)acc[c];
   return RMHMC_OK;
@@ -2000,16 +1912,16 @@ int rmhmc_mmala_sample(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, double e
   int rc = [&]() -> int {
     RC(mmala_init(ctx, theta0));
     const IterBase ib{n_iter, burn_in, S, d_samples, false, false};
-    for (int64_t it = 0; it <= burn_in; ++it) { launch_mmala_step(ctx, ib); flow_tick(ctx); }
+    for (int64_t it = 0; it <= burn_in; ++it) { launch_mmala_step(ctx, ctx->batch, ib); flow_tick(ctx); }
     RC(sync(ctx));
     const auto t0 = std::chrono::steady_clock::now();
-    for (int64_t it = burn_in + 1; it < n_iter; ++it) { launch_mmala_step(ctx, ib); flow_tick(ctx); }
+    for (int64_t it = burn_in + 1; it < n_iter; ++it) { launch_mmala_step(ctx, ctx->batch, ib); flow_tick(ctx); }
     RC(sync(ctx));
     if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     HIPCK(hipMemcpyAsync(samples_out, d_samples, sizeof(double) * (size_t)ctx->n * S * ctx->D, hipMemcpyDeviceToHost, ctx->stream));
     if (accept_out) {
       static_assert(sizeof(long long) == sizeof(int64_t), "int64");
-      RC(download(ctx, (long long*)accept_out, ctx->ch.accepted, ctx->n));
+      RC(download(ctx, (long long*)accept_out, ctx->batch.ch.accepted, ctx->n));
     }
     return sync(ctx);
   }();
@@ -2022,8 +1934,7 @@ int rmhmc_chains_init(rmhmc_ctx* ctx, const double* theta0, uint64_t seed, int64
   if (L < 1 || K < 1) return fail(ctx, RMHMC_ERR_INVALID, "chains_init: L >= 1 and K >= 1 required");
   ctx->L = L; ctx->eps = eps; ctx->K = K; ctx->seed = seed; ctx->chain_offset = chain_offset;
   RC(init_chains(ctx, theta0));
-  for (Group& g : ctx->groups)
-    if (g.dcount) HIPCK(hipMemsetAsync(g.dcount, 0, 6 * sizeof(unsigned long long), ctx->stream));
+  if (ctx->batch.dcount) HIPCK(hipMemsetAsync(ctx->batch.dcount, 0, 6 * sizeof(unsigned long long), ctx->stream));
   ctx->chains_ready = true;
   return RMHMC_OK;
 }
@@ -2051,10 +1962,10 @@ static int chains_state_impl(rmhmc_ctx* ctx, double* w_out, int64_t* iters_out, 
   if (!ctx->chains_ready) return fail(ctx, RMHMC_ERR_INVALID, "chains_state: rmhmc_chains_init has not been called");
   const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   if (w_out)  // strip the padding: [n][DP] -> [n][D]
-    HIPCK(hipMemcpy2DAsync(w_out, ctx->D * sizeof(double), ctx->ch.cur.w, ctx->DP * sizeof(double), ctx->D * sizeof(double), ctx->n, kind, ctx->stream));
+    HIPCK(hipMemcpy2DAsync(w_out, ctx->D * sizeof(double), ctx->batch.ch.cur.w, ctx->DP * sizeof(double), ctx->D * sizeof(double), ctx->n, kind, ctx->stream));
   static_assert(sizeof(long long) == sizeof(int64_t), "int64");
-  if (iters_out) HIPCK(hipMemcpyAsync(iters_out, ctx->ch.iter, sizeof(int64_t) * ctx->n, kind, ctx->stream));
-  if (accept_out) HIPCK(hipMemcpyAsync(accept_out, ctx->ch.accepted, sizeof(int64_t) * ctx->n, kind, ctx->stream));
+  if (iters_out) HIPCK(hipMemcpyAsync(iters_out, ctx->batch.ch.iter, sizeof(int64_t) * ctx->n, kind, ctx->stream));
+  if (accept_out) HIPCK(hipMemcpyAsync(accept_out, ctx->batch.ch.accepted, sizeof(int64_t) * ctx->n, kind, ctx->stream));
   return sync(ctx);
 }
 int rmhmc_chains_state(rmhmc_ctx* ctx, double* w_out, int64_t* iters_out, int64_t* accept_out) {
@@ -2069,8 +1980,8 @@ int rmhmc_chains_restore(rmhmc_ctx* ctx, const int64_t* iters, const int64_t* ac
   if (!ctx->chains_ready || !iters || !accepted) return fail(ctx, RMHMC_ERR_INVALID, "chains_restore: call rmhmc_chains_init first");
   for (int64_t c = 0; c < ctx->n; ++c)
     if (iters[c] < 0 || accepted[c] < 0) return fail(ctx, RMHMC_ERR_INVALID, "chains_restore: negative counter");
-  RC(upload(ctx, ctx->ch.iter, (const long long*)iters, ctx->n));
-  RC(upload(ctx, ctx->ch.accepted, (const long long*)accepted, ctx->n));
+  RC(upload(ctx, ctx->batch.ch.iter, (const long long*)iters, ctx->n));
+  RC(upload(ctx, ctx->batch.ch.accepted, (const long long*)accepted, ctx->n));
   return sync(ctx);
 }
 
@@ -2105,11 +2016,10 @@ int rmhmc_kernel_time(rmhmc_ctx* ctx, const char* which, double* seconds_out, in
     static const char* const names[5] = {"i8_delta_end_s4", "i8_delta_end_s5", "i8_delta_end_s6", "i8_delta_inner_s4", "i8_delta_inner_s5"};
     const int slot = (int)(std::find_if(names, names + 5, [&](const char* s) { return w == s; }) - names);
     if (slot == 5) return fail(ctx, RMHMC_ERR_INVALID, "kernel_time: unknown delta counter " + w);
-    for (const Group& g : ctx->groups) {
-      if (!g.dcount) continue;
+    if (ctx->batch.dcount) {
       unsigned long long h = 0;
-      HIPCK(hipMemcpy(&h, g.dcount + slot, sizeof(h), hipMemcpyDeviceToHost));
-      if (launches_out) *launches_out += (int64_t)h;
+      HIPCK(hipMemcpy(&h, ctx->batch.dcount + slot, sizeof(h), hipMemcpyDeviceToHost));
+      if (launches_out) *launches_out = (int64_t)h;
     }
     return RMHMC_OK;
   }
@@ -2145,7 +2055,7 @@ void amh_shape(const rmhmc_ctx* ctx, int* nt, int* rows) {
 // the same cuts for any number of chains; its launches are cut by work (AMH_LAUNCH_ROWS), which leaves the results unchanged.
 int amh_run(rmhmc_ctx* ctx, AmhParams p, const double* theta0, double* seconds_out) {
   const size_t n = ctx->n, D = ctx->D, DP = ctx->DP;
-  Chains& ch = ctx->ch;
+  Chains& ch = ctx->batch.ch;
   std::vector<double> h((size_t)n * D, 0.0);
   RC(upload_vec(ctx, ch.cur.w, theta0 ? theta0 : h.data()));
   std::fill(h.begin(), h.end(), 1.0);
@@ -2210,8 +2120,8 @@ int rmhmc_amh_sample(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, uint64_t s
     RC(amh_run(ctx, p, theta0, seconds_out));
     HIPCK(hipMemcpyAsync(samples_out, d_samples, sizeof(double) * n * S * D, hipMemcpyDeviceToHost, ctx->stream));
     std::vector<long long> a(n);
-    RC(download(ctx, a.data(), ctx->ch.accepted, n));
-    if (sd_out) RC(download_vec(ctx, sd_out, ctx->ch.PM));
+    RC(download(ctx, a.data(), ctx->batch.ch.accepted, n));
+    if (sd_out) RC(download_vec(ctx, sd_out, ctx->batch.ch.PM));
     RC(sync(ctx));
     if (accepted_out) for (size_t c = 0; c < n; ++c) accepted_out[c] = a[c];
     return RMHMC_OK;
@@ -2238,7 +2148,7 @@ int rmhmc_amh_replay(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, const doub
     p.z_in = d_z; p.u_in = d_u; p.w_out = d_w; p.ljl_out = d_l; p.dec_out = d_dec; p.n_iter = n_iter; p.burn_in = burn_in;
     RC(amh_run(ctx, p, theta0, nullptr));
     RC(download(ctx, w_out, d_w, vec)); RC(download(ctx, ljl_out, d_l, n * T)); RC(download(ctx, decisions_out, d_dec, vec));
-    if (sd_out) RC(download_vec(ctx, sd_out, ctx->ch.PM));
+    if (sd_out) RC(download_vec(ctx, sd_out, ctx->batch.ch.PM));
     return sync(ctx);
   }();
   for (void* q : {(void*)d_z, (void*)d_u, (void*)d_w, (void*)d_l, (void*)d_dec}) if (q) (void)hipFree(q);
@@ -2276,65 +2186,41 @@ void iwls_free(IwlsState& s) {
   for (void* q : {(void*)s.lq, (void*)s.sat, (void*)s.nsat, (void*)s.mcur}) if (q) (void)hipFree(q);
 }
 
-// the parameters of chains [g.off, g.off + g.n)
-IwlsParams iwls_view(const rmhmc_ctx* ctx, const Group& g, IwlsParams p) {
-  const size_t off = (size_t)g.off, D = ctx->D;
-  p.chain_offset += g.off;
-  if (p.samples) p.samples += off * p.S * D;
-  if (p.w_prop) { p.w_prop += off * p.T * D; p.u_in += off * p.T; }
-  if (p.w_out) p.w_out += off * p.T * D;
-  if (p.mean_out) p.mean_out += off * p.T * D;
-  if (p.ljl_out) p.ljl_out += off * p.T;
-  if (p.ratio_out) p.ratio_out += off * p.T;
-  if (p.dec_out) p.dec_out += off * p.T;
-  p.lq_cur += off; p.lq_trj += off; p.sat += off; p.nsat += off; p.mcur += off * ctx->DP;
-  return p;
-}
-
 void launch_iwls_ljit(rmhmc_ctx* ctx, Group& g, const double* Ginv, double* out) {
-  launch(ctx, g, LIGHT, "iwls", [&](hipStream_t st) {
+  launch(ctx, "iwls", [&](hipStream_t st) {
     NB_SWITCH(ctx, hipLaunchKernelGGL((k_iwls_ljit<NB_>), dim3((unsigned)g.n), dim3(64), 0, st, ctx->D, ctx->DP, Ginv, out));
   });
 }
 
 // one iteration of every chain: proposal, the point evaluation at w' (mode 1, the assembly path of the context's flags), compat terms,
 // decision
-void launch_iwls_iter(rmhmc_ctx* ctx, const IwlsParams& p) {
-  std::vector<Phase> ph;
-  ph.push_back([ctx, p](Group& g) { SMALL(ctx, g, "iwls", k_iwls_begin, ctx->D, ctx->DP, g.ch, iwls_view(ctx, g, p)); });
-  eval_point_phases(ctx, ph, false, 1);
+void launch_iwls_iter(rmhmc_ctx* ctx, Group& g, const IwlsParams& p) {
+  SMALL(ctx, g, "iwls", k_iwls_begin, ctx->D, ctx->DP, g.ch, p);
+  eval_point_phases(ctx, g, false, 1);
   if (p.compat) {
-    ph.push_back([ctx, p](Group& g) { launch_iwls_ljit(ctx, g, g.ch.trj.Ginv, iwls_view(ctx, g, p).lq_trj); });
-    ph.push_back([ctx, p](Group& g) {
-      int* sat = iwls_view(ctx, g, p).sat;
-      launch(ctx, g, HEAVY, "iwls_sat", [&](hipStream_t st) {
-        const dim3 grid((unsigned)((ctx->M + IWLS_SAT_ROWS - 1) / IWLS_SAT_ROWS), (unsigned)((g.n + IWLS_SAT_CH - 1) / IWLS_SAT_CH));
-        hipLaunchKernelGGL(k_iwls_sat, grid, dim3(IWLS_SAT_ROWS), 0, st, ctx->dd, g.n, (const double*)g.ch.trj.w, sat);
-      });
+    launch_iwls_ljit(ctx, g, g.ch.trj.Ginv, p.lq_trj);
+    launch(ctx, "iwls_sat", [&](hipStream_t st) {
+      const dim3 grid((unsigned)((ctx->M + IWLS_SAT_ROWS - 1) / IWLS_SAT_ROWS), (unsigned)((g.n + IWLS_SAT_CH - 1) / IWLS_SAT_CH));
+      hipLaunchKernelGGL(k_iwls_sat, grid, dim3(IWLS_SAT_ROWS), 0, st, ctx->dd, g.n, (const double*)g.ch.trj.w, p.sat);
     });
   }
-  ph.push_back([ctx, p](Group& g) { SMALL(ctx, g, "iwls", k_iwls_end, ctx->D, ctx->DP, g.ch, iwls_view(ctx, g, p)); });
-  run_phases(ctx, ph);
+  SMALL(ctx, g, "iwls", k_iwls_end, ctx->D, ctx->DP, g.ch, p);
 }
 
 // Iterations 0..n_iter-1 of every chain (iwls.py:38-85) from the record at theta0 (default 0, :18), evaluated by the generic kernels
 // (the arithmetic of the iterations' own evaluations).  Sampling: the reference's reports before iterations i % 1000 == 0 and burn_in
 // (:39-43), then the timer.
 int iwls_run(rmhmc_ctx* ctx, IwlsParams p, long long n_iter, bool sampling, const double* theta0, double* seconds_out) {
-  const bool medium = ctx->medium;
-  ctx->medium = false;
-  const int rc0 = mmala_init(ctx, theta0);
-  ctx->medium = medium;
-  RC(rc0);
-  if (p.compat)
-    for (Group& g : ctx->groups) launch_iwls_ljit(ctx, g, g.ch.cur.Ginv, p.lq_cur + g.off);
+  Group& g = ctx->batch;
+  RC(mmala_init(ctx, theta0, false));
+  if (p.compat) launch_iwls_ljit(ctx, g, g.ch.cur.Ginv, p.lq_cur);
   std::vector<long long> acc;
   auto t0 = std::chrono::steady_clock::now();
   for (long long i = 0; i < n_iter; ++i) {
     if (sampling && (i % 1000 == 0 || i == p.burn_in)) {
       if (ctx->progress_fn) {
         acc.resize(ctx->n);
-        RC(download(ctx, acc.data(), ctx->ch.accepted, ctx->n));
+        RC(download(ctx, acc.data(), ctx->batch.ch.accepted, ctx->n));
         RC(sync(ctx));
         long long a = 0;
         for (long long x : acc) a += x;
@@ -2347,7 +2233,7 @@ int iwls_run(rmhmc_ctx* ctx, IwlsParams p, long long n_iter, bool sampling, cons
       }
     }
     p.it = i;
-    launch_iwls_iter(ctx, p);
+    launch_iwls_iter(ctx, g, p);
     HIPCK(hipGetLastError());
     flow_tick(ctx);
   }
@@ -2378,7 +2264,7 @@ int rmhmc_iwls_sample(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t c
     RC(iwls_run(ctx, p, n_iter, true, theta0, seconds_out));
     HIPCK(hipMemcpyAsync(samples_out, d_samples, sizeof(double) * n * S * D, hipMemcpyDeviceToHost, ctx->stream));
     std::vector<long long> a(n), b(n);
-    RC(download(ctx, a.data(), ctx->ch.accepted, n));
+    RC(download(ctx, a.data(), ctx->batch.ch.accepted, n));
     RC(download(ctx, b.data(), s.nsat, n));
     RC(sync(ctx));
     for (size_t c = 0; c < n; ++c) {
