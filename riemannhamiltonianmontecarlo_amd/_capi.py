@@ -120,6 +120,11 @@ IWLS_SIGNATURES = {
     "rmhmc_iwls_sample": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_uint64, C.c_int64, _dp, _dp, _lp, _lp, _dp]),
     "rmhmc_iwls_replay": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _i8p]),
 }
+# include/rmhmc_gibbs.h: the auxiliary-variable Gibbs sampler, HIP library only as well
+GIBBS_SIGNATURES = {
+    "rmhmc_gibbs_sample": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_int64, _dp, _lp, _lp, _dp, _dp, _dp]),
+    "rmhmc_gibbs_replay": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp, _dp, _dp, _lp, C.c_int64, _dp, _dp, _ip, _dp, _dp, _lp, _ip]),
+}
 
 
 class RmhmcError(RuntimeError):
@@ -160,6 +165,12 @@ class RmhmcLib:
         self.has_iwls = all(hasattr(self.lib, name) for name in IWLS_SIGNATURES)
         if self.has_iwls:
             for name, (res, args) in IWLS_SIGNATURES.items():
+                fn = getattr(self.lib, name)
+                fn.restype = res
+                fn.argtypes = args
+        self.has_gibbs = all(hasattr(self.lib, name) for name in GIBBS_SIGNATURES)
+        if self.has_gibbs:
+            for name, (res, args) in GIBBS_SIGNATURES.items():
                 fn = getattr(self.lib, name)
                 fn.restype = res
                 fn.argtypes = args
@@ -460,6 +471,47 @@ class Context:
         self._ck(self.lib.rmhmc_iwls_replay(self._h, T, 1 if compat else 0, _ptr(w_prop), _ptr(u), _ptr(th), _ptr(w), _ptr(mean), _ptr(ljl),
                                             _ptr(ratio), _ptr(dec, _i8p)))
         return dict(w=w, mean=mean, ljl=ljl, ratio=ratio, accepted=(dec & 1) != 0, u_read=(dec & 2) != 0, saturated=(dec & 4) != 0)
+
+    # ---- auxiliary-variable Gibbs sampler (code/gibbs_sampler.py, include/rmhmc_gibbs.h) ----------
+    def _need_gibbs(self):
+        if not self.rl.has_gibbs:
+            raise RmhmcError(-4, "%s does not export the Gibbs sampler (include/rmhmc_gibbs.h)" % self.rl.path)
+
+    def gibbs_sample(self, n_iter, burn_in, seed=0, chain_offset=0, state=False):
+        """returns dict(samples [n][n_iter-burn_in][D], capped [n]: rows that reached a bound (expected 0), stopped [n]: -1, or the
+        iteration at which the chain stopped where the reference would have (include/rmhmc_gibbs.h; its later rows are NaN), seconds
+        from iteration burn_in; state=True adds Z and lam [n][N] after the last iteration)"""
+        self._need_gibbs()
+        n, D = self.n, self.D
+        S = int(n_iter) - int(burn_in)
+        if S <= 0 or int(burn_in) < 0:
+            raise ValueError("need 0 <= burn_in < max_iter")
+        samples = np.empty((n, S, D)); capped = np.zeros(n, dtype=np.int64); stopped = np.zeros(n, dtype=np.int64); secs = C.c_double(0.0)
+        Z = np.zeros((n, self.M)) if state else None
+        lam = np.zeros((n, self.M)) if state else None
+        self._ck(self.lib.rmhmc_gibbs_sample(self._h, int(n_iter), int(burn_in), int(seed), int(chain_offset), _ptr(samples),
+                                             _ptr(capped, _lp), _ptr(stopped, _lp), _ptr(Z), _ptr(lam), C.cast(C.byref(secs), _dp)))
+        out = dict(samples=samples, capped=capped, stopped=stopped, seconds=secs.value)
+        if state:
+            out.update(Z=Z, lam=lam)
+        return out
+
+    def gibbs_replay(self, u_init, u_sweep, T, ks_draws, ks_offset):
+        """Recorded draws per chain: u_init [n][N], u_sweep [n][T][N], T [n][T][D], ks_draws [n][total][3], ks_offset [n][T][N+1].
+        Returns dict(beta, B [n][T][D] after every iteration (B before the T term), attempts [n][T][N], Z, lam [n][N] after the last
+        one, capped [n], status [n]: 1 where the tape ran out of attempts, 2 where a lam_j was not positive and finite: the chain stopped)"""
+        self._need_gibbs()
+        n, D, N = self.n, self.D, self.M
+        u_init = _f64(u_init, (n, N))
+        u_sweep = _f64(u_sweep); Tn = u_sweep.size // (n * N)
+        u_sweep = u_sweep.reshape(n, Tn, N); T = _f64(T, (n, Tn, D))
+        ks_draws = _f64(ks_draws).reshape(n, -1, 3); total = ks_draws.shape[1]
+        ks_offset = np.ascontiguousarray(ks_offset, dtype=np.int64).reshape(n, Tn, N + 1)
+        beta = np.zeros((n, Tn, D)); B = np.zeros((n, Tn, D)); att = np.zeros((n, Tn, N), dtype=np.int32)
+        Z = np.zeros((n, N)); lam = np.zeros((n, N)); capped = np.zeros(n, dtype=np.int64); status = np.zeros(n, dtype=np.int32)
+        self._ck(self.lib.rmhmc_gibbs_replay(self._h, Tn, _ptr(u_init), _ptr(u_sweep), _ptr(T), _ptr(ks_draws), _ptr(ks_offset, _lp), total,
+                                             _ptr(beta), _ptr(B), _ptr(att, _ip), _ptr(Z), _ptr(lam), _ptr(capped, _lp), _ptr(status, _ip)))
+        return dict(beta=beta, B=B, attempts=att, Z=Z, lam=lam, capped=capped, status=status)
 
     def chains_init(self, theta0=None, seed=0, chain_offset=0, L=6, eps=0.5, K=4):
         th = None if theta0 is None else _f64(np.broadcast_to(theta0, (self.n, self.D)))

@@ -8,6 +8,7 @@
 #include "../../include/rmhmc.h"
 #include "../../include/rmhmc_amh.h"
 #include "../../include/rmhmc_iwls.h"
+#include "../../include/rmhmc_gibbs.h"
 #include "kernels.hip.h"
 #include "fused_small.hip.h"
 #include "large_d.hip.h"
@@ -15,6 +16,7 @@
 #include "medium_step.hip.h"
 #include "amh.hip.h"
 #include "iwls.hip.h"
+#include "gibbs.hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -2308,6 +2310,189 @@ int rmhmc_iwls_replay(rmhmc_ctx* ctx, int64_t n_iter, int32_t compat, const doub
   }();
   for (void* q : {(void*)d_wp, (void*)d_u, (void*)d_w, (void*)d_m, (void*)d_l, (void*)d_r, (void*)d_dec}) if (q) (void)hipFree(q);
   iwls_free(s);
+  return rc;
+}
+
+}  // extern "C"
+
+// ---- auxiliary-variable Gibbs sampler (gibbs_sampler.py, gibbs.hip.h) --------------------------------------------------------------
+namespace {
+
+const char* const kGibbsDMsg = "gibbs: D > 64 is not supported (64 < D <= 256 needs a blocked inverse and sweep)";
+
+// device state of one Gibbs call (GibbsParams); G, V and Lt are the context's Gq, trj.Ginv and trj.L
+struct GibbsState {
+  double *Z = nullptr, *lam = nullptr, *ilam = nullptr, *B = nullptr, *beta = nullptr;
+  long long *capped = nullptr, *dead = nullptr;
+  int* stop = nullptr;
+};
+
+int gibbs_alloc(rmhmc_ctx* ctx, GibbsState& s, GibbsParams& p) {
+  const size_t n = ctx->n, Mp = ctx->Mp, DP = ctx->DP;
+  HIPCK(hipMalloc((void**)&s.Z, sizeof(double) * n * Mp)); HIPCK(hipMalloc((void**)&s.lam, sizeof(double) * n * Mp));
+  HIPCK(hipMalloc((void**)&s.ilam, sizeof(double) * n * Mp));
+  HIPCK(hipMalloc((void**)&s.B, sizeof(double) * n * DP)); HIPCK(hipMalloc((void**)&s.beta, sizeof(double) * n * DP));
+  HIPCK(hipMalloc((void**)&s.capped, sizeof(long long) * n)); HIPCK(hipMalloc((void**)&s.stop, sizeof(int) * n));
+  HIPCK(hipMalloc((void**)&s.dead, sizeof(long long) * n));
+  HIPCK(hipMemsetAsync(s.B, 0, sizeof(double) * n * DP, ctx->stream));
+  HIPCK(hipMemsetAsync(s.beta, 0, sizeof(double) * n * DP, ctx->stream));
+  p.Z = s.Z; p.lam = s.lam; p.ilam = s.ilam; p.B = s.B; p.beta = s.beta; p.capped = s.capped; p.stop = s.stop; p.dead = s.dead;
+  p.G = ctx->batch.ch.Gq; p.V = ctx->batch.ch.trj.Ginv; p.Lt = ctx->batch.ch.trj.L;
+  return RMHMC_OK;
+}
+void gibbs_free(GibbsState& s) {
+  for (void* q : {(void*)s.Z, (void*)s.lam, (void*)s.ilam, (void*)s.B, (void*)s.beta, (void*)s.capped, (void*)s.stop, (void*)s.dead}) if (q) (void)hipFree(q);
+}
+
+// one iteration of every chain
+void launch_gibbs_iter(rmhmc_ctx* ctx, const GibbsParams& p) {
+  const unsigned n = (unsigned)ctx->n;
+  const int D = (int)ctx->D, DP = (int)ctx->DP;
+  launch(ctx, "gibbs_assemble", [&](hipStream_t st) {  // (one row range per chain whatever the batch: see gibbs.hip.h)
+    NB_SWITCH(ctx, hipLaunchKernelGGL((k_assemble<NB_>), dim3((n + 3) / 4), dim3(256), 0, st, ctx->dd, (int)n, ctx->batch.ch.phase,
+                                      (const double*)p.ilam, p.G, (size_t)0));
+  });
+  launch(ctx, "gibbs_factor", [&](hipStream_t st) {
+    NB_SWITCH(ctx, hipLaunchKernelGGL((k_gibbs_factor<NB_>), dim3(n), dim3(64), 0, st, D, DP, p));
+  });
+  launch(ctx, "gibbs_b", [&](hipStream_t st) { hipLaunchKernelGGL(k_gibbs_b, dim3(n), dim3(256), 0, st, ctx->dd, p); });
+  launch(ctx, "gibbs_sweep", [&](hipStream_t st) {
+    NB_SWITCH(ctx, hipLaunchKernelGGL((k_gibbs_sweep<NB_>), dim3(n), dim3(64), 0, st, ctx->dd, p));
+  });
+  launch(ctx, "gibbs_beta", [&](hipStream_t st) { hipLaunchKernelGGL(k_gibbs_beta, dim3(n), dim3(64), 0, st, D, DP, p); });
+  launch(ctx, "gibbs_mix", [&](hipStream_t st) {
+    hipLaunchKernelGGL(k_gibbs_mix, dim3(n, (unsigned)((ctx->M + GIBBS_MIX_ROWS - 1) / GIBBS_MIX_ROWS)), dim3(GIBBS_MIX_ROWS), 0, st, ctx->dd, p);
+  });
+}
+
+// Initialisation and iterations 0..n_iter-1 of every chain.  Sampling: the host synchronises only before the iterations the reference
+// prints on (i % 100 == 0, gibbs_sampler.py:97-98) and before iteration burn_in, where the timer starts (:100-101).
+int gibbs_run_body(rmhmc_ctx* ctx, GibbsParams p, long long n_iter, bool sampling, double* seconds_out) {
+  fill_int(ctx, ctx->batch.ch.phase, 1, ctx->n);
+  hipLaunchKernelGGL(k_gibbs_init, dim3((unsigned)ctx->n, (unsigned)((ctx->Mp + 255) / 256)), dim3(256), 0, ctx->stream, ctx->dd, p);
+  HIPCK(hipGetLastError());
+  auto t0 = std::chrono::steady_clock::now();
+  for (long long i = 0; i < n_iter; ++i) {
+    if (sampling && (i % 100 == 0 || i == p.burn_in)) {
+      if (i % 100 == 0 && ctx->progress_fn) {
+        RC(sync(ctx));
+        ctx->progress_fn(RMHMC_EV_PROGRESS, i, 0, i * ctx->n, ctx->progress_user);
+      }
+      if (i == p.burn_in) {
+        RC(sync(ctx));
+        t0 = std::chrono::steady_clock::now();
+      }
+    }
+    p.it = i;
+    launch_gibbs_iter(ctx, p);
+    HIPCK(hipGetLastError());
+    flow_tick(ctx);
+  }
+  RC(sync(ctx));
+  if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return RMHMC_OK;
+}
+int gibbs_run(rmhmc_ctx* ctx, const GibbsParams& p, long long n_iter, bool sampling, double* seconds_out) {
+  const int rc = gibbs_run_body(ctx, p, n_iter, sampling, seconds_out);
+  fill_int(ctx, ctx->batch.ch.phase, 0, ctx->n);  // on every path: the next user of the context finds the phases as gibbs_run found them
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rmhmc_gibbs_sample(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, uint64_t seed, int64_t chain_offset, double* samples_out,
+                       int64_t* capped_out, int64_t* stopped_out, double* Z_out, double* lam_out, double* seconds_out) {
+  NEED_DATA(ctx);
+  if (!samples_out || !amh_iters_ok(n_iter, burn_in) || chain_offset < 0 || chain_offset + ctx->n > (int64_t)1 << 32)
+    return fail(ctx, RMHMC_ERR_INVALID, "gibbs_sample: need samples_out, 0 <= burn_in < n_iter < 2^32, 0 <= chain_offset, chain_offset + n <= 2^32");
+  if (ctx->D > 64) return fail(ctx, RMHMC_ERR_UNSUPPORTED, kGibbsDMsg);
+  HIPCK(hipSetDevice(ctx->device));
+  ctx->chains_ready = false;
+  const size_t n = ctx->n, D = ctx->D, S = (size_t)(n_iter - burn_in);
+  double* d_samples = nullptr;
+  GibbsState s;
+  int rc = [&]() -> int {
+    HIPCK(hipMalloc((void**)&d_samples, sizeof(double) * n * S * D));
+    HIPCK(hipMemsetAsync(d_samples, 0xff, sizeof(double) * n * S * D, ctx->stream));  // NaN: the rows a stopped chain never writes
+    GibbsParams p{};
+    RC(gibbs_alloc(ctx, s, p));
+    p.seed = seed; p.chain_offset = chain_offset; p.burn_in = burn_in; p.S = (long long)S; p.samples = d_samples; p.T = n_iter;
+    RC(gibbs_run(ctx, p, n_iter, true, seconds_out));
+    HIPCK(hipMemcpyAsync(samples_out, d_samples, sizeof(double) * n * S * D, hipMemcpyDeviceToHost, ctx->stream));
+    const size_t N = ctx->M, Mp = ctx->Mp;
+    if (Z_out) HIPCK(hipMemcpy2DAsync(Z_out, N * sizeof(double), s.Z, Mp * sizeof(double), N * sizeof(double), n, hipMemcpyDeviceToHost, ctx->stream));
+    if (lam_out) HIPCK(hipMemcpy2DAsync(lam_out, N * sizeof(double), s.lam, Mp * sizeof(double), N * sizeof(double), n, hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<long long> cp(n), dd(n);
+    RC(download(ctx, cp.data(), s.capped, n)); RC(download(ctx, dd.data(), s.dead, n));
+    RC(sync(ctx));
+    for (size_t c = 0; c < n; ++c) {
+      if (capped_out) capped_out[c] = cp[c];
+      if (stopped_out) stopped_out[c] = dd[c];
+    }
+    return RMHMC_OK;
+  }();
+  if (d_samples) (void)hipFree(d_samples);
+  gibbs_free(s);
+  return rc;
+}
+
+int rmhmc_gibbs_replay(rmhmc_ctx* ctx, int64_t n_iter, const double* u_init, const double* u_sweep, const double* T, const double* ks_draws,
+                       const int64_t* ks_offset, int64_t ks_total, double* beta_out, double* B_out, int32_t* attempts_out, double* Z_out,
+                       double* lam_out, int64_t* capped_out, int32_t* status_out) {
+  NEED_DATA(ctx);
+  if (!u_init || !u_sweep || !T || !ks_draws || !ks_offset || !beta_out || !B_out || !attempts_out || ks_total < 0 || n_iter < 1 ||
+      n_iter > (int64_t)0xffffffffLL)
+    return fail(ctx, RMHMC_ERR_INVALID, "gibbs_replay: need the five tapes, beta_out, B_out, attempts_out, ks_total >= 0 and 0 < n_iter < 2^32");
+  if (ctx->D > 64) return fail(ctx, RMHMC_ERR_UNSUPPORTED, kGibbsDMsg);
+  const size_t n = ctx->n, D = ctx->D, N = ctx->M, Tn = (size_t)n_iter, Mp = ctx->Mp;
+  for (size_t r = 0; r < n * Tn; ++r)  // every row's range lies inside its chain's draws
+    for (size_t j = 0; j <= N; ++j) {
+      const int64_t o = ks_offset[r * (N + 1) + j];
+      if (o < 0 || o > ks_total || (j && o < ks_offset[r * (N + 1) + j - 1]))
+        return fail(ctx, RMHMC_ERR_INVALID, "gibbs_replay: ks_offset must be non-decreasing within 0..ks_total");
+    }
+  HIPCK(hipSetDevice(ctx->device));
+  ctx->chains_ready = false;
+  double *d_ui = nullptr, *d_us = nullptr, *d_T = nullptr, *d_ks = nullptr, *d_beta = nullptr, *d_B = nullptr;
+  long long* d_off = nullptr;
+  int* d_att = nullptr;
+  GibbsState s;
+  int rc = [&]() -> int {
+    const size_t nks = n * (size_t)std::max<int64_t>(ks_total, 1) * 3;
+    HIPCK(hipMalloc((void**)&d_ui, sizeof(double) * n * N)); HIPCK(hipMalloc((void**)&d_us, sizeof(double) * n * Tn * N));
+    HIPCK(hipMalloc((void**)&d_T, sizeof(double) * n * Tn * D)); HIPCK(hipMalloc((void**)&d_ks, sizeof(double) * nks));
+    HIPCK(hipMalloc((void**)&d_off, sizeof(long long) * n * Tn * (N + 1)));
+    HIPCK(hipMalloc((void**)&d_beta, sizeof(double) * n * Tn * D)); HIPCK(hipMalloc((void**)&d_B, sizeof(double) * n * Tn * D));
+    HIPCK(hipMalloc((void**)&d_att, sizeof(int) * n * Tn * N));
+    HIPCK(hipMemsetAsync(d_beta, 0, sizeof(double) * n * Tn * D, ctx->stream)); HIPCK(hipMemsetAsync(d_B, 0, sizeof(double) * n * Tn * D, ctx->stream));
+    HIPCK(hipMemsetAsync(d_att, 0, sizeof(int) * n * Tn * N, ctx->stream));
+    RC(upload(ctx, d_ui, u_init, n * N)); RC(upload(ctx, d_us, u_sweep, n * Tn * N)); RC(upload(ctx, d_T, T, n * Tn * D));
+    if (ks_total) RC(upload(ctx, d_ks, ks_draws, n * (size_t)ks_total * 3));
+    static_assert(sizeof(long long) == sizeof(int64_t), "int64");
+    RC(upload(ctx, d_off, (const long long*)ks_offset, n * Tn * (N + 1)));
+    GibbsParams p{};
+    RC(gibbs_alloc(ctx, s, p));
+    p.T = n_iter; p.u_init = d_ui; p.u_sweep = d_us; p.T_in = d_T; p.ks = d_ks; p.ks_off = d_off; p.ks_total = ks_total;
+    p.beta_out = d_beta; p.B_out = d_B; p.att_out = d_att; p.burn_in = n_iter;
+    RC(gibbs_run(ctx, p, n_iter, false, nullptr));
+    RC(download(ctx, beta_out, d_beta, n * Tn * D)); RC(download(ctx, B_out, d_B, n * Tn * D));
+    RC(download(ctx, (int*)attempts_out, d_att, n * Tn * N));
+    if (Z_out) HIPCK(hipMemcpy2DAsync(Z_out, N * sizeof(double), s.Z, Mp * sizeof(double), N * sizeof(double), n, hipMemcpyDeviceToHost, ctx->stream));
+    if (lam_out) HIPCK(hipMemcpy2DAsync(lam_out, N * sizeof(double), s.lam, Mp * sizeof(double), N * sizeof(double), n, hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<long long> cp(n);
+    std::vector<int> sp(n);
+    RC(download(ctx, cp.data(), s.capped, n)); RC(download(ctx, sp.data(), s.stop, n));
+    RC(sync(ctx));
+    for (size_t c = 0; c < n; ++c) {
+      if (capped_out) capped_out[c] = cp[c];
+      if (status_out) status_out[c] = sp[c];
+    }
+    return RMHMC_OK;
+  }();
+  for (void* q : {(void*)d_ui, (void*)d_us, (void*)d_T, (void*)d_ks, (void*)d_off, (void*)d_beta, (void*)d_B, (void*)d_att}) if (q) (void)hipFree(q);
+  gibbs_free(s);
   return rc;
 }
 

@@ -17,13 +17,14 @@ Two ways to execute the runs:
 import numpy as np
 
 from . import tools
+from .gibbs_sampler import auxiliary_gibbs
 from .hmc import HMC
 from .iwls import iwls
 from .metropolis import AMH
 from .mmala import mMALA
 from .rmhmc import RMHMC
 
-SAMPLERS = {"RMHMC": RMHMC, "HMC": HMC, "mMALA": mMALA, "AMH": AMH, "IWLS": iwls}
+SAMPLERS = {"RMHMC": RMHMC, "HMC": HMC, "mMALA": mMALA, "AMH": AMH, "IWLS": iwls, "Gibbs": auxiliary_gibbs}
 
 
 def summarize(results_beta, results_time, nfft="python"):
