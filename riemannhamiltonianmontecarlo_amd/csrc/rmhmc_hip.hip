@@ -1144,7 +1144,9 @@ int rmhmc_set_option(rmhmc_ctx* ctx, const char* key, int64_t value) {
   apply_runtime_options(ctx);
   if (ctx->stale_list_alloc) {  // a list left over from a run with the other setting must not be consumed
     HIPCK(hipMemsetAsync(ctx->batch.ch.stale_count, 0, sizeof(int), ctx->stream));
-    fill_int(ctx, ctx->batch.ch.cstale, 1, ctx->n);  // (every chain's tiles count as stale: the next first pass recomputes them)
+    // (every chain's tiles count as stale: the next first pass recomputes them.  A second line of defence: k_iter_end sets the flag on
+    //  every rejection and the RP_F row pass clears it whatever the options are, so the flags are exact without this fill too)
+    fill_int(ctx, ctx->batch.ch.cstale, 1, ctx->n);
     HIPCK(hipStreamSynchronize(ctx->stream));
   }
   return RMHMC_OK;
