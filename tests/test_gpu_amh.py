@@ -2,6 +2,7 @@
 against the NumPy restatement of tests/test_amh_cpu.py, chain independence, agreement in distribution with the RMHMC sampler, and the
 Python surface."""
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -10,6 +11,9 @@ from conftest import GOLDEN
 from riemannhamiltonianmontecarlo_amd import AMH, RMHMC, experiment
 from riemannhamiltonianmontecarlo_amd.data import synthetic_logreg
 from test_amh_cpu import AMH_TAPES, amh_numpy, load_amh_tape, philox_draws
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import sampler_edges as E  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -35,15 +39,19 @@ def test_replay_matches_reference_tape(hip, name):
         np.testing.assert_allclose(r["ljl"][c], g["ljl"], rtol=1e-11)
 
 
-def _sample_vs_numpy(hip, XX, t, n, T, B, seed):
+def _sample_vs_numpy(hip, XX, t, n, T, B, seed, follow=None, ref=None):
+    """follow: the chain ids the restatement follows (default: all); ref: its run on them, where the caller shares it"""
     M, D = XX.shape
     with hip.context(M, D, n, flags=0) as ctx:
         ctx.set_data(XX, t)
         smp, acc, sd, _ = ctx.amh_sample(T, B, seed=seed)
-    ref = amh_numpy(XX, t, T, B, philox_draws(seed, np.arange(n), D), n=n)
-    np.testing.assert_array_equal(acc, ref["accepted"].sum(axis=(1, 2)))
-    assert _rel(smp, ref["w"][:, B:]) <= 1e-10
-    np.testing.assert_array_equal(sd, ref["sd"])
+    ids = np.arange(n) if follow is None else np.asarray(follow)
+    if ref is None:
+        ref = amh_numpy(XX, t, T, B, philox_draws(seed, ids, D), n=len(ids))
+    assert np.all(np.isfinite(smp))
+    np.testing.assert_array_equal(acc[ids], ref["accepted"].sum(axis=(1, 2)))
+    assert _rel(smp[ids], ref["w"][:, B:]) <= 1e-10
+    np.testing.assert_array_equal(sd[ids], ref["sd"])
 
 
 def test_sample_matches_numpy_philox_australian(hip):
@@ -74,6 +82,18 @@ def test_sample_matches_numpy_philox_one_wave_per_chain(hip, case):
         XX, t = d["XX"], d["t"]
         T, B = 30, 20
     _sample_vs_numpy(hip, XX, t, 1024, T, B, 31)
+
+
+@pytest.mark.parametrize("name", list(E.AMH_EDGE_CASES))
+def test_sample_matches_numpy_philox_wide_d_and_tile_edges(hip, name):
+    """the variants and edges no other case runs (tests/helpers/sampler_edges.py; the variant each shape selects is asserted in
+    tests/test_sampler_edges_cpu.py): one wavefront per chain with D = 256 (KW = 4, every lane owns four coordinates) and D = 129
+    (lane 0 owns three, the last Box-Muller pair is half used); 256 threads per chain with D = 200 and 65 (threads 64..255 own
+    coordinates and draw); M = 1024 (R = 16 full at NT = 64), 1025 (falls to NT = 256), 12 288 = AMH_MAX_ONCHIP_ROWS (R = 48 full) and
+    12 289 (the first streamed size).  Of a 1024-chain batch the restatement follows the first chain, the last and 16 in between."""
+    n, M, D, T, B, seed, _ = E.AMH_EDGE_CASES[name]
+    k = E.amh_edge_case(name)
+    _sample_vs_numpy(hip, k["XX"], k["t"], n, T, B, seed, follow=k["ids"], ref=k["ref"])
 
 
 @pytest.mark.parametrize("M", [500, 1500, 4000, 8000, 12000])

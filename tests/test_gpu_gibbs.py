@@ -5,6 +5,7 @@ surface."""
 import contextlib
 import io
 import os
+import sys
 import time
 
 import numpy as np
@@ -15,6 +16,10 @@ from riemannhamiltonianmontecarlo_amd import RMHMC, _capi, auxiliary_gibbs, expe
 from riemannhamiltonianmontecarlo_amd.data import synthetic_logreg
 from test_gibbs_cpu import GIBBS_TAPES, PhiloxDraws, flip_labels, gibbs_numpy, load_gibbs_tape
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import sampler_edges as E  # noqa: E402
+from sampler_edges import OneUlpOff as _OneUlpOff, philox_tapes  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 
@@ -22,21 +27,6 @@ def _tapes(g, n):
     T, N = g["u_sweep"].shape
     b = lambda a: np.ascontiguousarray(np.broadcast_to(a, (n,) + a.shape))
     return b(g["u_init"]), b(g["u_sweep"]), b(g["T"]), b(g["ks_draws"]), b(g["ks_offset"])
-
-
-def philox_tapes(dr, attempts):
-    """the replay entry point's five tapes from the sampler's own Philox streams, given the attempts (n, T, N) every row consumes"""
-    n, T, N = attempts.shape
-    off = np.concatenate([np.zeros((n, T, 1), np.int64), np.cumsum(attempts, axis=2)], axis=2)
-    tot = attempts.sum(axis=2)                                          # (n, T) attempts per iteration
-    off = off + np.concatenate([np.zeros((n, 1), np.int64), np.cumsum(tot, axis=1)[:, :-1]], axis=1)[:, :, None]
-    ks = np.zeros((n, int(tot.sum(axis=1).max()), 3))
-    for it in range(T):
-        for a in range(int(attempts[:, it].max())):
-            Y, Ua, Ub = dr.ks(it, a, None)
-            c, j = np.nonzero(attempts[:, it] > a)
-            ks[c, off[c, it, j] + a] = np.stack([Y[c, j], Ua[c, j], Ub[c, j]], axis=1)
-    return (dr.u_init(), np.stack([dr.u_sweep(i) for i in range(T)], axis=1), np.stack([dr.T(i) for i in range(T)], axis=1), ks, off)
 
 
 @pytest.mark.parametrize("name", GIBBS_TAPES)
@@ -82,23 +72,21 @@ def test_replay_stops_a_chain_whose_tape_is_short(hip):
             ctx.gibbs_replay(u_init, u_sweep, T, ks, bad)
 
 
-class _OneUlpOff(PhiloxDraws):
-    def u_init(self):
-        return super().u_init() * (1 + 2.0 ** -52)
-
-
-def _sample_vs_numpy(hip, XX, t, n, T, B, seed, follow=None, v=100.0):
+def _sample_vs_numpy(hip, XX, t, n, T, B, seed, follow=None, v=100.0, known=None):
     """gibbs_sample against gibbs_numpy on the same Philox streams; follow: the chain ids the restatement follows (default: all).
     The reference's proposal Y = 1 + (Y - sqrt(Y (4 r + Y))) / (2 r) (gibbs_sampler.py:59) cancels twice for a small residual r, so one
     rounding error in r comes back as ~ eps (Y / r)^2 in lam_j and, an iteration later, in beta: two correct evaluations of the file differ
     by 1e-10 .. 1e-5 after two or three iterations, depending on the smallest residual the case happens to meet.
     A case can carry the 1e-9 bound only where the restatement itself is stable to that level, so that is checked first, on the
     restatement alone: its samples move by <= 1e-10 when the initial uniforms move by one ulp.  Data, seeds and lengths below were
-    chosen by that criterion, before any run on the device."""
+    chosen by that criterion, before any run on the device.  known: dict(ref, own) where the caller shares them with other tests."""
     M, D = XX.shape
     ids = np.arange(n) if follow is None else np.asarray(follow)
-    ref = gibbs_numpy(XX, t, T, PhiloxDraws(seed, ids, M, D), n=len(ids), v=v)
-    own = rel_err(gibbs_numpy(XX, t, T, _OneUlpOff(seed, ids, M, D), n=len(ids), v=v)["beta"], ref["beta"])
+    if known is None:
+        ref = gibbs_numpy(XX, t, T, PhiloxDraws(seed, ids, M, D), n=len(ids), v=v)
+        own = rel_err(gibbs_numpy(XX, t, T, _OneUlpOff(seed, ids, M, D), n=len(ids), v=v)["beta"], ref["beta"])
+    else:
+        ref, own = known["ref"], known["own"]
     assert own <= 1e-10, own
     with hip.context(M, D, n, flags=0) as ctx:
         ctx.set_data(XX, t, v)
@@ -131,6 +119,59 @@ def test_sample_matches_numpy_philox_large_batch_ragged_m(hip):
     follow = np.unique(np.concatenate([[0, n - 1], np.linspace(1, n - 2, 16).astype(int)]))
     assert len(follow) >= 18
     _sample_vs_numpy(hip, XX, t, n, 3, 1, 109, follow=follow)
+
+
+@pytest.mark.parametrize("M,D,T", E.GIBBS_EDGE_CASES)
+def test_sample_matches_numpy_philox_block_counts_and_edges(hip, M, D, T):
+    """every block count of k_gibbs_sweep / k_gibbs_factor and the row-count edges (tests/helpers/sampler_edges.py): NB = 2 (D 17, 24,
+    31, 32), NB = 3 with D == DP (48), D == DP (16, 32), D = 1; M = 3, 15, 16, 17 (the sweep's 16-row blocks, the 8-row stride of
+    k_gibbs_b's four waves), 256 / 257 (a block of k_gibbs_mix / k_gibbs_init).  Four chains, no burn-in, same bounds as every case
+    here; the stability of each case on the restatement is asserted in tests/test_sampler_edges_cpu.py too."""
+    k = E.gibbs_edge_case(M, D, T)
+    _sample_vs_numpy(hip, k["XX"], k["t"], E.GIBBS_EDGE_CHAINS, T, 0, E.GIBBS_EDGE_SEED, known=k)
+
+
+@pytest.mark.parametrize("M,D,T", E.GIBBS_EDGE_CASES)
+def test_replay_matches_numpy_block_counts_and_edges(hip, M, D, T):
+    """the same cases through the replay entry point fed with the restatement's attempts: attempts array-equal, B, beta <= 1e-9, Z, lam
+    <= 1e-8 (the state and the attempts, which the sampler's samples do not show)"""
+    k = E.gibbs_edge_case(M, D, T)
+    ref = k["ref"]
+    with hip.context(M, D, E.GIBBS_EDGE_CHAINS, flags=0) as ctx:
+        ctx.set_data(k["XX"], k["t"])
+        r = ctx.gibbs_replay(*philox_tapes(k["draws"], ref["attempts"]))
+    assert np.all(r["status"] == 0) and np.all(r["capped"] == 0)
+    np.testing.assert_array_equal(r["attempts"], ref["attempts"])
+    errs = {key: rel_err(r[key], ref[key]) for key in ("beta", "B", "Z", "lam")}
+    print("replay vs gibbs_numpy: M %d D %d:" % (M, D), errs)
+    assert errs["beta"] <= 1e-9 and errs["B"] <= 1e-9 and errs["Z"] <= 1e-8 and errs["lam"] <= 1e-8, errs
+
+
+def test_replay_row_that_reaches_the_attempt_bound(hip):
+    """Row 7 of chain 1 has the second uniform of every attempt of iteration 1 at 1 - 2^-53: every attempt is rejected, the row runs
+    into GIBBS_MAX_ATTEMPTS, keeps its last proposal and is counted in capped (the path of k_gibbs_mix that no other test reaches:
+    they all assert capped == 0).  capped and attempts array-equal to the restatement, no chain stopped, beta, B <= 1e-9 and Z, lam
+    <= 1e-8 through the iteration after it, which runs on the kept proposal; chains 0 and 2 bit for bit as without the override."""
+    k = E.capped_case()
+    ref = k["ref"]
+    out = []
+    for dr in (k["draws"], k["plain_draws"]):
+        with hip.context(E.CAP_M, E.CAP_D, E.CAP_N, flags=0) as ctx:
+            ctx.set_data(k["XX"], k["t"])
+            out.append(ctx.gibbs_replay(*philox_tapes(dr, (ref if dr is k["draws"] else k["plain"])["attempts"])))
+    r, plain = out
+    np.testing.assert_array_equal(r["capped"], ref["capped"])
+    assert list(r["capped"]) == [0, 1, 0] and np.all(r["status"] == 0)
+    np.testing.assert_array_equal(r["attempts"], ref["attempts"])
+    assert r["attempts"][E.CAP_CHAIN, E.CAP_IT, E.CAP_ROW] == 64
+    errs = {key: rel_err(r[key], ref[key]) for key in ("beta", "B", "Z", "lam")}
+    print("capped row:", errs)
+    assert np.all(np.isfinite(r["beta"])) and np.all(np.isfinite(r["Z"])) and np.all(r["lam"] > 0)
+    assert errs["beta"] <= 1e-9 and errs["B"] <= 1e-9 and errs["Z"] <= 1e-8 and errs["lam"] <= 1e-8, errs
+    assert np.all(plain["capped"] == 0) and np.all(plain["status"] == 0)
+    for c in (0, 2):
+        for key in ("beta", "B", "Z", "lam", "attempts"):
+            np.testing.assert_array_equal(r[key][c], plain[key][c])
 
 
 def test_batched_chain_equals_single_chain_and_segments_do_not_matter(hip):
@@ -276,46 +317,82 @@ def test_one_launch_at_the_benchmark_size(tmp_path):
     assert np.all(np.isfinite(smp)) and np.abs(smp).max() < 10 and len(np.unique(smp[:, 2, 0])) == len(smp)   # chains differ, no runaway
 
 
+def _replay_truncated_normal(hip, k, what):
+    """replay of the batch k (tests/helpers/sampler_edges.py) against the restatement: attempts equal; beta, B norm-wise <= 1e-9; every Z
+    finite, non-zero and on its label's side; Z ELEMENT by element within 1e-8 |Z_ref| + 1e-12 (|m| + s), m and s the restatement's
+    values of that row's last draw (the project's Z bound per element; the absolute term is the rounding of the sum m + s y when m
+    comes from differently ordered sums).  Prints the worst error / tolerance per m/s bin of the last draw and returns it."""
+    ref, t, n = k["ref"], np.asarray(k["t"]).reshape(-1), k["n"]
+    with hip.context(E.TN_M, E.TN_D, n, flags=0) as ctx:
+        ctx.set_data(k["XX"], k["t"])
+        r = ctx.gibbs_replay(*philox_tapes(k["draws"], ref["attempts"]))
+    assert np.all(r["status"] == 0) and np.all(r["capped"] == 0)
+    np.testing.assert_array_equal(r["attempts"], ref["attempts"])
+    assert np.all(np.isfinite(r["Z"])) and np.all(r["Z"] != 0) and np.all(np.sign(r["Z"]) == np.where(t == 1, 1.0, -1.0)[None])
+    errs = {key: rel_err(r[key], ref[key]) for key in ("beta", "B", "Z", "lam")}
+    ratio, worst = E.tn_report(r["Z"], ref)
+    print("%s, %d iteration(s), norm-wise:" % (what, k["T"]), errs)
+    for b, (q, cnt) in worst.items():
+        print("    m/s in %-12s %5d elements of Z, worst error / tolerance %.3e" % (b, cnt, q))
+    if "extreme" in k:
+        print("    elements drawn at an extreme uniform: worst error / tolerance %.3e" % ratio[k["extreme"]].max())
+        low = ref["p_last"] < E.G.TINY                           # p = U Phi(-m/s) below TINY on the two-tail form: the fmax(p, TINY) clamp
+        assert low.sum() == 2
+        print("    elements whose p is clamped at TINY (Z = m + s Phi^-1(TINY)): device", r["Z"][low], "restatement", ref["Z"][low],
+              "error / tolerance %.3e" % ratio[low].max())
+    assert errs["beta"] <= 1e-9 and errs["B"] <= 1e-9, errs
+    assert np.all(ratio <= 1.0), (float(ratio.max()), np.argwhere(ratio > 1.0)[:8])
+    return errs, worst
+
+
+@pytest.mark.parametrize("T", [E.TN_T, 1])
+def test_device_truncated_normal_between_the_tapes_and_the_tail_form(hip, T):
+    """gibbs_truncnorm_neg on the device where neither the tapes (|m/s| <= 2.4) nor the far-tail test (m/s > 25) reach: the library
+    quantile polished by the Newton step on erfc for p = U Phi(-m/s) down to 1e-137, both sides of the switch to the asymptotic form
+    at m/s = 25, the complement branch p > 1/2 at m/s down to -30, and the two clamps.  24 chains of the intercept-dominated data set,
+    chain c started at Z = Phi^-1(Phi(-z0_c) / 2) on every label-0 row, z0 from 2.5 to 31 (tests/helpers/sampler_edges.py; the counts
+    per bin, the stability of the case and the extreme uniforms are asserted on the restatement in tests/test_sampler_edges_cpu.py).
+    The chains relax in one sweep, so the draws beyond m/s = 10 are all in the first one: the run of ONE iteration has them in its Z
+    and compares them element by element (34, 30, 29, 37, 75, 10, 9, 7 elements in the bins from (2.4, 5] to (26, 30], 1216 below
+    -15); the run of three iterations compares what follows from them.  In the last iteration of either, two rows of each label in
+    chains 3 and 13 (and two label-1 rows of chain 22, in the tail form) are drawn at U = 1e-300, 2^-53, 1/2 and 1 - 2^-53: where the
+    mirrored uniform of a label-1 row is 1, the draw is the rounding of m + s y and fmin(x, -TINY) holds it on its side.  One
+    label-0 row of chains 5 and 16 is drawn at a subnormal uniform (1e-310, 5e-324): p = U Phi(-m/s) is below TINY there and the
+    fmax(p, TINY) clamp gives m + s Phi^-1(TINY) (that p < TINY occurs on exactly these two draws is asserted on the restatement).
+    Measured on the MI355X, worst error / tolerance per bin of the one-iteration run: (2.4, 5] 9.6e-6, (5, 10] 3.2e-5, (10, 15]
+    4.7e-5, (15, 20] 4.6e-5, (20, 24] 2.0e-4, (24, 25] 1.5e-4, (25, 26] 7.9e-8, (26, 30] 3.0e-8, [-25, -15) 2.2e-7, [-40, -25)
+    8.7e-8, the extreme uniforms 1.7e-5, the two draws with p clamped at TINY 1.6e-8; of the three-iteration run 1.6e-3 at the most
+    (extreme uniforms 5.7e-5, clamped p 1.1e-6).  The restatement's
+    own values of these draws lie within 1.7e-4 of the tolerance of the exact quantile (mpmath), in every bin."""
+    _replay_truncated_normal(hip, E.tn_mid_case(T), "truncated normal, mid range")
+
+
+def _far_tail(hip, T):
+    k = E.tn_far_case(T)
+    ref = k["ref"]
+    far = int((ref["a_calls"] > E.G.TAIL).sum())
+    assert far >= 20 and np.all(ref["capped"] == 0), far
+    errs, worst = _replay_truncated_normal(hip, k, "far tail, %d draws beyond m/s = 25" % far)
+    assert errs["Z"] <= 1e-8 and errs["lam"] <= 1e-8, errs
+    return ref, worst
+
+
 def test_device_truncated_normal_far_tail(hip):
     """The device's own truncated normal beyond m/s = 25 (the asymptotic branch, which no tape reaches: |m/s| <= 2.4 there).  An
     intercept-dominated data set, nine labels 0 to one label 1, with the initial uniform of every label-0 row at 1e-300: Z_j = -37
     there, B_0 near -30, and the label-1 rows are drawn at m/s between 25 and 35 (counted on the restatement: at least 20 such
     draws).  Replay of the Philox streams with that u_init against the restatement: attempts equal, beta, B <= 1e-9, Z, lam <= 1e-8,
-    every Z finite and on its label's side."""
-    import test_gibbs_cpu as G
-    M, D, n, T = 100, 2, 3, 3
-    XX = np.c_[np.ones(M), np.random.RandomState(3).randn(M)]
-    t = (np.arange(M) % 10 == 0).astype(np.float64)
+    every Z finite and on its label's side, and Z element by element within 1e-8 |Z_ref| + 1e-12 (|m| + s): norm-wise, against
+    max |Z| = 37, a relative error of 1e-6 in a heavily truncated draw of 0.05 passed."""
+    _far_tail(hip, E.TN_T)
 
-    class Extreme(PhiloxDraws):
-        def u_init(self):
-            u = super().u_init().copy()
-            u[:, t == 0] = 1e-300
-            return u
 
-    far = [0]
-    orig = G.truncnorm_neg
-
-    def counting(U, Uc, m, s):
-        far[0] += int(np.sum(np.asarray(m) / np.asarray(s) > G.TAIL))
-        return orig(U, Uc, m, s)
-
-    G.truncnorm_neg = counting
-    try:
-        dr = Extreme(5, np.arange(n), M, D)
-        ref = gibbs_numpy(XX, t, T, dr, n=n)
-    finally:
-        G.truncnorm_neg = orig
-    assert far[0] >= 20 and np.all(ref["capped"] == 0), far
-    with hip.context(M, D, n, flags=0) as ctx:
-        ctx.set_data(XX, t)
-        r = ctx.gibbs_replay(*philox_tapes(dr, ref["attempts"]))
-    assert np.all(r["status"] == 0) and np.all(r["capped"] == 0)
-    np.testing.assert_array_equal(r["attempts"], ref["attempts"])
-    assert np.all(np.isfinite(r["Z"])) and np.all(np.sign(r["Z"]) == np.where(t == 1, 1.0, -1.0)[None])
-    errs = {k: rel_err(r[k], ref[k]) for k in ("beta", "B", "Z", "lam")}
-    print("far tail, %d draws beyond m/s = 25:" % far[0], errs)
-    assert errs["beta"] <= 1e-9 and errs["B"] <= 1e-9 and errs["Z"] <= 1e-8 and errs["lam"] <= 1e-8, errs
+def test_device_truncated_normal_far_tail_first_sweep(hip):
+    """All 30 far draws of the case above are in its first sweep (the chains relax at once: the Z it compares after three iterations
+    holds none of them).  The same batch run for ONE iteration: the far draws are the label-1 elements of Z, compared element by
+    element.  Measured on the MI355X: worst error / tolerance 7.4e-8 on the 30 far draws, 9.4e-8 over all of Z."""
+    ref, worst = _far_tail(hip, 1)
+    assert (ref["m_last"] / ref["s_last"] > E.G.TAIL).sum() >= 20
 
 
 def test_limits(hip):

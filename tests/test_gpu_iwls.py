@@ -2,6 +2,7 @@
 sampler against the NumPy restatement of tests/test_iwls_cpu.py in both modes and on both assembly paths, chain independence, the
 reference's truncation, agreement in distribution with the RMHMC sampler, limits, and the Python surface."""
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -10,6 +11,9 @@ from conftest import GOLDEN
 from riemannhamiltonianmontecarlo_amd import RMHMC, _capi, experiment, iwls
 from riemannhamiltonianmontecarlo_amd.data import synthetic_logreg
 from test_iwls_cpu import IWLS_TAPES, iwls_numpy, load_iwls_tape, philox_iwls_draws
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import sampler_edges as E  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -40,12 +44,17 @@ def test_replay_matches_reference_tape(hip, name):
         assert np.all(np.abs(r["ratio"][c][~nan] - g["ratio"][~nan]) <= 1e-9 * scale[~nan])
 
 
-def _sample_vs_numpy(hip, XX, t, n, T, B, seed, compat, flags=0):
+def _sample_vs_numpy(hip, XX, t, n, T, B, seed, compat, flags=0, ref=None):
+    """ref: the restatement's run where the caller shares it with other tests (tests/helpers/sampler_edges.py)"""
     M, D = XX.shape
     with hip.context(M, D, n, flags=flags) as ctx:
         ctx.set_data(XX, t)
+        if flags & _capi.FLAG_INT8_METRIC:     # the assembly really is the int8 one: no certificate has sent the data to the fp64 kernels
+            info = ctx.device_info().split("; options:")[0]
+            assert "int8 metric path %d slices: active" % ((flags >> 12) & 7) in info, info
         smp, acc, sat, _ = ctx.iwls_sample(T, B, compat=compat, seed=seed)
-    ref = iwls_numpy(XX, t, T, philox_iwls_draws(seed, np.arange(n), D), n=n, compat=compat)
+    if ref is None:
+        ref = iwls_numpy(XX, t, T, philox_iwls_draws(seed, np.arange(n), D), n=n, compat=compat)
     np.testing.assert_array_equal(acc, ref["accepted"].sum(axis=1))
     np.testing.assert_array_equal(sat, ref["saturated"].sum(axis=1))
     assert _rel(smp, ref["w"][:, B:]) <= 1e-9
@@ -76,6 +85,38 @@ def test_sample_matches_numpy_philox_int8_metric(hip, compat):
     """the assembly on the int8 matrix cores (6 exact byte slices) behind the same sampler"""
     d = np.load(os.path.join(GOLDEN, "data_german.npz"))
     _sample_vs_numpy(hip, d["XX"], d["t"], 4, 60, 30, 5, compat, flags=_capi.int8_metric_flags(6))
+
+
+@pytest.mark.parametrize("compat", [True, False])
+@pytest.mark.parametrize("case", E.IWLS_EDGE_CASES)
+def test_sample_matches_numpy_philox_block_counts_and_edges(hip, case, compat):
+    """the block counts and edges no other case runs (tests/helpers/sampler_edges.py): NB = 3 (D 33, 40, 48), D == DP (16, 48), D = 1,
+    D = 17 with M = 40 < 64, and 33 chains (a second, partly filled chain block of k_iwls_sat).  No decision of these cases is closer
+    than 1e-6 to its threshold on the restatement (tests/test_sampler_edges_cpu.py; measured: 8e-4 and 1.2e-2 at the least)."""
+    M, D, n, T, B, seed = case
+    k = E.iwls_edge_case(case, compat)
+    _sample_vs_numpy(hip, k["XX"], k["t"], n, T, B, seed, compat, ref=k["ref"])
+
+
+@pytest.mark.parametrize("compat", [True, False])
+def test_sample_matches_numpy_philox_int8_metric_nb3(hip, compat):
+    """the int8 assembly (6 exact byte slices) at D = 40, 33 chains: NB = 3 behind it (german above: D = 25)"""
+    case = E.IWLS_EDGE_CASES[0]
+    M, D, n, T, B, seed = case
+    assert D == 40 and n == 33
+    k = E.iwls_edge_case(case, compat)
+    _sample_vs_numpy(hip, k["XX"], k["t"], n, T, B, seed, compat, flags=_capi.int8_metric_flags(6), ref=k["ref"])
+
+
+def test_saturation_in_a_partly_filled_chain_block_australian(hip):
+    """33 chains, compat, 120 iterations on australian: chain 32 sits alone in the second 32-chain block of k_iwls_sat, where the guard
+    c0 + j < n covers the LDS fill and the store, and saturates (55 times on the restatement, about 2100 in all: asserted in
+    tests/test_sampler_edges_cpu.py).  Accepted and saturated counts per chain array-equal, samples <= 1e-9."""
+    k = E.iwls_sat_case()
+    ref = k["ref"]
+    assert ref["saturated"][32].sum() >= 1
+    acc, sat = _sample_vs_numpy(hip, k["XX"], k["t"], E.IWLS_SAT_N, E.IWLS_SAT_T, E.IWLS_SAT_B, E.IWLS_SAT_SEED, True, ref=ref)
+    assert sat[32] >= 1 and sat.sum() > 1000
 
 
 def test_batched_chain_equals_single_chain_with_offset(hip):
