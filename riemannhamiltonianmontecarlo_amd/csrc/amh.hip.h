@@ -30,6 +30,7 @@
 // Injected mode (AmhParams::z_in != nullptr) reads z and u from tapes [n][n_iter][D] instead and records, per proposal, the decision
 // (bit 0) and whether u was read (bit 1), w and CurrentLJL after every iteration.
 #pragma once
+#include "plan.h"  // AMH_MAX_ONCHIP_ROWS
 
 #define AMH_VALU_PER_ROW 60   // ESTIMATE (not counted from the ISA) of the fp64 VALU instructions per data row and proposal: ocml exp ~24,
                               // log ~30, plus the fma, the t f' product, 1 + e^f and the two adds
@@ -265,7 +266,6 @@ __global__ __launch_bounds__(NT) void k_amh(DevData dd, AmhParams p) {
     else if ((R) <= 32) { constexpr int NT_ = 256, R_ = 32; __VA_ARGS__; }                                      \
     else { constexpr int NT_ = 256, R_ = 48; __VA_ARGS__; }                                                     \
   } while (0)
-#define AMH_MAX_ONCHIP_ROWS (256 * 48)
 // Work bound of one launch, in (chain, proposal, data row) evaluations: 2^34, ~0.15 s at the 1.2e11 / s measured at 8192 chains x D 64
 // x M 10 000 (profiles/amh_bench.jsonl).  A segment whose work exceeds it runs as several launches (AmhParams::carry).
 #define AMH_LAUNCH_ROWS (1LL << 34)

@@ -16,6 +16,7 @@
 // two paths are interchangeable between launches.
 #pragma once
 #include "kernels.hip.h"
+#include "plan.h"  // FS_D, FS_WAVES, FS_PT
 
 // No implicit a*b+c contraction in this file: the global-step loop of k_fused_small may be peeled or
 // versioned by the optimiser, and with fp-contract=fast the copies can round differently, which would make a
@@ -23,10 +24,7 @@
 // (observed: 1 ulp).  Every multiply-add that matters for speed is written as an explicit fma().
 #pragma clang fp contract(off)
 
-#define FS_D 8
 #define FS_T 36                  // packed lower triangle of an 8x8 matrix
-#define FS_WAVES 4
-#define FS_PT 104                // doubles of one point record in LDS (w, grad, tr, L, Gi, ljl, hld; padded)
 #define FS_IDX(i, j) ((i) * ((i) + 1) / 2 + (j))   // i >= j
 
 struct FusedParams {

@@ -12,10 +12,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "plan.h"  // RM_LD
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
-#define RM_LD 66            // LDS leading dimension of the per-chain DxD matrix (even: 16-byte aligned rows for ds_read_b128, conflict free)
 #define RM_PI2 6.283185307179586476925286766559
 // Packed form of the same LDS image (PK = true in the routines below): only the lower BLOCK triangle of 16 x 16 blocks is kept - the
 // Cholesky / solve / inverse routines never touch a block above the diagonal -, row i of block row I = i >> 4 holding its 16 (I + 1)

@@ -15,14 +15,7 @@
 #pragma once
 #include "kernels.hip.h"
 #include "fused_small.hip.h"
-
-#define MS_MAXMP 2048  // rows (padded) whose v and c fit the LDS budget
-#define MS_GLD 34      // leading dimension of the G^-1 image
-
-template <int NB>
-constexpr int ms_lds_doubles(int Mp) {
-  return 64 * RM_LD + 32 * MS_GLD + 4 * (16 * NB) * (16 * NB) + 2 * Mp + 12 * 32 + 4 * 40;
-}
+#include "plan.h"  // MS_MAXMP, MS_GLD, ms_lds_doubles
 
 // RPT > 0: every thread keeps its RPT data rows (n = t, t + 256, ...; Mp <= 256 RPT) in registers for the whole launch, so the ~11 row
 // passes of a step read X once; RPT = 0: rows are re-read from L2 in every pass (one row ahead).

@@ -48,11 +48,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <utility>
+#include "plan.h"  // I8_BM
 
 typedef int i4v __attribute__((ext_vector_type(4)));
 typedef int i16v __attribute__((ext_vector_type(16)));
 
-#define I8_BM 128
 #define I8_ROWB 32  // LDS bytes per tile row per slice; the two 16-byte halves of rows 8..15 (mod 16) are swapped so that
                     // every ds_read_b128 lane group {0-3,12-15,20-27} / {4-11,16-19,28-31} hits 16 distinct 16-byte slots
 __device__ __forceinline__ int i8_lds_off(int row, int half) { return row * I8_ROWB + ((half ^ ((row >> 3) & 1)) << 4); }

@@ -9,6 +9,7 @@
 #include "../../include/rmhmc_amh.h"
 #include "../../include/rmhmc_iwls.h"
 #include "../../include/rmhmc_gibbs.h"
+#include "plan.h"
 #include "kernels.hip.h"
 #include "fused_small.hip.h"
 #include "large_d.hip.h"
@@ -39,67 +40,32 @@ struct EvPair { hipEvent_t a, b; };
 
 // The batch of chains a launch works on, with the per-chain arrays and the scratch sized for it.  There is one per context
 // (the whole batch); the work-sorted sampler narrows a copy of it to the prefix of chains still running (launch_global_step_prefix).
+// How the work is cut up (row splits, row ranges, k pieces) is decided once for the context: the Plan (plan.h).
 // (Cutting the batch into 2-4 groups ping-ponged over two streams was measured twice without gain on MI355X - the co-running
 // light kernels are starved and the heavy ones slow down by the same total, profiles/r01_groups_sweep.txt.)
 struct Group {
   Chains ch{};
   int n = 0;
-  int nsplit = 1;
+  int nCp = 0;           // int8 metric path: n padded to the tile
   int8_t* Vs = nullptr;  // int8 metric path: slices of v, [S][nks][nCp][32]
   int8_t* Qs = nullptr;  // slices of the doubled G^-1 entries, [S][nkp][nCp][32]
   double* qscale = nullptr;
-  double *Gpart = nullptr, *Rpart = nullptr;  // k-split planes of small batches ([ksplit][n][DP*DP], [ksplit][n][Mp])
+  double *Gpart = nullptr, *Rpart = nullptr;  // planes of small batches ([gpart_planes][n][DP*DP], [ksplit_l][n][Mp])
   int* Tq = nullptr;      // int32 accumulators of the ragged last pair block, [pieces][S][nCp][32 ntail] (k_assemble_i8_tail)
-  int tail_pieces = 1;
-  int ksplit_a = 1, ksplit_l = 1;
-  int fsplit = 1;  // fp64 assembly of small batches: row ranges per chain (planes in Gpart)
   int* vbad = nullptr;
   int* vexp = nullptr;   // per-chain extra binary digits of the v grid (VSlice)
   int* vexp_d = nullptr; int* rebase = nullptr; unsigned long long* dmax = nullptr;  // delta assembly (VSlice / I8Delta)
   unsigned long long* dcount = nullptr;  // [6] delta assemblies by slice count (I8Delta::count, rmhmc_kernel_time "i8_delta_*"; zeroed by chains_init)
   double* Gbase = nullptr;  // large-D path: copy of the G a delta assembly adds to (Gq is factored in place)
   d4* ctile = nullptr;   // c = v(1-2p) of trj.w in the tile layout of k_mompass, [ceil(n/16)][Mp/16][64] x 4 doubles
-  int nCp = 0;
 };
-
-// Tuning options (include/rmhmc.h: rmhmc_create_opts / rmhmc_set_option).  The library reads no environment variables.
-struct Options {
-  int64_t graph = 1, sorted = 1, inflight = 32, cdyn = 1, crestore = 1, i8_force_rebase = 0;                 // run time
-  int64_t ccache = 1, medium = 1, fused = 1, hmc_traj_maxn = -1, fsplit = 0, nsplit_max = 64, nsplit_waves = -1, i8_tail = -1,   // create time
-          i8_delta = 1, i8_delta_inner = 1;
-};
-struct OptionDesc { const char* key; int64_t Options::*slot; bool create_only; int64_t lo, hi; };
-const OptionDesc kOptions[] = {
-    {"graph", &Options::graph, false, 0, 1},
-    {"sorted", &Options::sorted, false, 0, 1},
-    {"inflight", &Options::inflight, false, 0, 1 << 20},
-    {"cdyn", &Options::cdyn, false, 0, 1},
-    {"crestore", &Options::crestore, false, 0, 1},
-    {"i8_force_rebase", &Options::i8_force_rebase, false, 0, 1},
-    {"ccache", &Options::ccache, true, 0, 1},
-    {"medium", &Options::medium, true, 0, 1},
-    {"fused", &Options::fused, true, 0, 1},
-    {"hmc_traj_maxn", &Options::hmc_traj_maxn, true, -1, (int64_t)1 << 40},
-    {"fsplit", &Options::fsplit, true, 0, 64},
-    {"nsplit_max", &Options::nsplit_max, true, 1, 1 << 20},
-    {"nsplit_waves", &Options::nsplit_waves, true, -1, 1 << 20},
-    {"i8_tail", &Options::i8_tail, true, -1, 1},
-    {"i8_delta", &Options::i8_delta, true, 0, 1},
-    {"i8_delta_inner", &Options::i8_delta_inner, true, 0, 1},
-};
-const OptionDesc* find_option(const char* key) {
-  if (!key) return nullptr;
-  for (const OptionDesc& d : kOptions)
-    if (!strcmp(d.key, key)) return &d;
-  return nullptr;
-}
 
 }  // namespace
 
-struct rmhmc_ctx {
+// The context IS its plan (plan.h: M, D, n, the padded sizes, the splits, the int8 layout, the stepping path - fixed at create),
+// plus the device state and what changes after create.
+struct rmhmc_ctx : Plan {
   int device = 0;
-  int64_t M = 0, n = 0;
-  int D = 0, DP = 0, NB = 0, Mp = 0, nblk = 0;
   uint32_t flags = 0;
   double alpha = 100.0;
   hipStream_t stream = nullptr;
@@ -112,20 +78,12 @@ struct rmhmc_ctx {
   std::vector<void*> allocs;
   bool have_data = false, chains_ready = false;
   int sampler = 0;           // 0: RMHMC (rmhmc.py), 1: plain HMC (hmc.py) -- selects the global step
-  bool big = false;          // large-D path: 64 < D <= 256 (large_d.hip.h)
-  int nbk = 1, npairs = 1;   // 64-column blocks and block pairs of the large-D path
   double *d_Wd = nullptr, *d_hpart = nullptr, *d_Gcopy = nullptr;
   bool want_G = false;
-  bool fused = false;        // small-problem path: D <= 8 and X fits in LDS (fused_small.hip.h)
-  size_t fused_lds = 0;
-  bool medium = false;       // one-launch leapfrog step for small batches with 8 < D <= 32 (medium_step.hip.h)
-  size_t medium_lds = 0;
   // (options crestore / cdyn / ccache: c = v(1-2p) kept per position in the momentum pass's tile layout; the first pass of a step re-uses
   //  the tiles of chains that did not just reject; those of the chains that did are recomputed by k_crestore, 16 to a wavefront)
-  bool hmc_traj = false;     // plain HMC in small batches: one launch per trajectory (k_hmc_traj)
   // int8 metric path (metric_i8.hip.h)
-  bool i8 = false;
-  int i8S = 0, i8_nks = 0, i8_bn = 128, i8_chunk = 1;  // i8_chunk: k-stages (of 32) per launch
+  bool i8 = false;           // in use: requested at create (Plan::i8_requested) and not switched off by the set_data certificate
   int i8_inner_drop = 1;     // inner assemblies from S-1 slices (launch_assemble; RMHMC_FLAG_INT8_INNER_FULL: off)
   // (options i8_delta / i8_delta_inner: G at the end of a leapfrog step, and the second position iterate, as the previous iterate's G + the
   //  assembly of the v differences; i8_force_rebase: tests treat every chain as if its v exponent had changed; i8_tail: ragged last pair
@@ -136,9 +94,7 @@ struct rmhmc_ctx {
   int* d_zre = nullptr;
   double *d_cmin = nullptr, *d_cmax = nullptr;  // min_n |x_nd|, max_n |x_nd| per column (VSlice)
   double* d_zscale = nullptr;
-  int i8_nkp = 0, i8_NRp = 0;
   I8Pairs pairs{};
-  bool i8_requested = false;   // RMHMC_FLAG_INT8_METRIC given at create (i8 may be switched off by the set_data certificate)
   double i8_bound = 0.0;       // certificate of the last set_data (metric_i8.hip.h: "Error bound"), 0 when the path is not requested
   // sampler parameters of the stateful API
   int L = 6, K = 4;
@@ -191,6 +147,13 @@ int dalloc(rmhmc_ctx* ctx, T** p, size_t count) {
   return RMHMC_OK;
 }
 
+// hipFuncAttributeMaxDynamicSharedMemorySize of one kernel (MAX_LDS above: per function and device, so never lowered)
+template <typename K>
+int raise_lds(rmhmc_ctx* ctx, K kernel, int bytes) {
+  HIPCK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  return RMHMC_OK;
+}
+
 struct Timed {
   rmhmc_ctx* ctx;
   hipStream_t st;
@@ -240,19 +203,19 @@ void flow_tick(rmhmc_ctx* ctx, long long steps = 1) {
   }
 
 #define I8_SWITCH(ctx, ...) I8_SWITCH_S((ctx)->i8S, __VA_ARGS__)
-#define I8_SWITCH_S(sval, ...)                                                     \
-  switch (sval) {                                                                  \
-    case 4: { constexpr int S_ = 4, WN_ = 4, TN_ = 1; __VA_ARGS__; } break;        \
-    case 5: { constexpr int S_ = 5, WN_ = 4, TN_ = 1; __VA_ARGS__; } break;        \
-    case 6: { constexpr int S_ = 6, WN_ = 4, TN_ = 1; __VA_ARGS__; } break;        \
-    default: { constexpr int S_ = 7, WN_ = 2, TN_ = 1; __VA_ARGS__; } break;       \
+#define I8_SWITCH_S(sval, ...)                                                                       \
+  switch (sval) {                                                                                    \
+    case 4: { constexpr int S_ = 4, WN_ = i8_tile_wn(4), TN_ = i8_tile_tn(4); __VA_ARGS__; } break;  \
+    case 5: { constexpr int S_ = 5, WN_ = i8_tile_wn(5), TN_ = i8_tile_tn(5); __VA_ARGS__; } break;  \
+    case 6: { constexpr int S_ = 6, WN_ = i8_tile_wn(6), TN_ = i8_tile_tn(6); __VA_ARGS__; } break;  \
+    default: { constexpr int S_ = 7, WN_ = i8_tile_wn(7), TN_ = i8_tile_tn(7); __VA_ARGS__; } break; \
   }
 
 // Delta assembly of the evaluation that ends a leapfrog step (I8Delta in metric_i8.hip.h): the last position iterate has left its N in
 // the slice planes and its G - summed from all six slices - in Gq, and v moves by 1e-6 between the two points, so the difference
 // needs four slices (10 slice products) where the full assembly needs six (21).
 static bool use_delta(const rmhmc_ctx* ctx, const Group& g) {
-  return ctx->i8 && ctx->opt.i8_delta && (!ctx->big || g.Gbase) && ctx->i8S == 6 && g.ctile && g.ksplit_a <= 1 && ctx->K >= 2 && g.dmax;
+  return ctx->i8 && ctx->opt.i8_delta && (!ctx->big || g.Gbase) && ctx->i8S == 6 && g.ctile && ctx->ksplit_a <= 1 && ctx->K >= 2 && g.dmax;
 }
 // The second position iterate as a delta of the first (both inner iterates on five slices: it = 2 < K - 1; later inner iterates would need
 // the N of a predecessor whose planes hold differences)
@@ -263,12 +226,12 @@ template <int MODE>
 void launch_rowpass(rmhmc_ctx* ctx, Group& g, const double* w, double* out0, double* out2 = nullptr, bool delta = false) {
   launch(ctx, "rowpass", [&](hipStream_t st) {
     if (ctx->big) {
-      dim3 grid((unsigned)((g.n + 15) / 16), g.nsplit);
-      hipLaunchKernelGGL((k_rowpass_big<MODE>), grid, dim3(256), 0, st, ctx->dd, g.n, g.nsplit, ctx->nbk, g.ch.phase, w, out0, out2,
+      dim3 grid((unsigned)((g.n + 15) / 16), ctx->nsplit);
+      hipLaunchKernelGGL((k_rowpass_big<MODE>), grid, dim3(256), 0, st, ctx->dd, g.n, ctx->nsplit, ctx->nbk, g.ch.phase, w, out0, out2,
                          g.ch.gpart, g.ch.ljl_part, g.ctile);
       return;
     }
-    dim3 grid((unsigned)((g.n + 63) / 64), g.nsplit);
+    dim3 grid((unsigned)((g.n + 63) / 64), ctx->nsplit);
     if (ctx->i8 && MODE != RP_G) {  // int8 metric path: v goes out as byte slices (no fp64 row vector, no k_vsplit)
       // (vbad and dmax are clear: the factor kernel behind the previous assembly has reset them, Chains::i8_vbad / i8_dmax)
       const VSlice vs{g.Vs, g.vbad, ctx->i8_nks, g.nCp, ctx->i8S, g.vexp, ctx->d_cmin, ctx->d_cmax};
@@ -277,22 +240,22 @@ void launch_rowpass(rmhmc_ctx* ctx, Group& g, const double* w, double* out0, dou
         VSlice vd = vs;
         vd.vexp_d = g.vexp_d; vd.rebase = g.rebase; vd.dmax = g.dmax; vd.force_rebase = (int)ctx->opt.i8_force_rebase;
         if (MODE == RP_F) {
-          NB_SWITCH(ctx, hipLaunchKernelGGL((k_rowpass<NB_, RP_F, 6, false, true>), grid, dim3(256), 0, st, ctx->dd, g.n, g.nsplit, g.ch.phase, w,
+          NB_SWITCH(ctx, hipLaunchKernelGGL((k_rowpass<NB_, RP_F, 6, false, true>), grid, dim3(256), 0, st, ctx->dd, g.n, ctx->nsplit, g.ch.phase, w,
                                             out0, nullptr, g.ch.gpart, g.ch.ljl_part, vd, g.ctile, g.ch.cstale));
         } else {
-          NB_SWITCH(ctx, hipLaunchKernelGGL((k_rowpass<NB_, RP_V, 6, true, true>), grid, dim3(256), 0, st, ctx->dd, g.n, g.nsplit, g.ch.phase, w,
+          NB_SWITCH(ctx, hipLaunchKernelGGL((k_rowpass<NB_, RP_V, 6, true, true>), grid, dim3(256), 0, st, ctx->dd, g.n, ctx->nsplit, g.ch.phase, w,
                                             out0, out2, g.ch.gpart, g.ch.ljl_part, vd, g.ctile, g.ch.cstale));
         }
       } else if (g.ctile && MODE == RP_F) {
-        I8_SWITCH(ctx, NB_SWITCH(ctx, hipLaunchKernelGGL((k_rowpass<NB_, MODE, S_, false>), grid, dim3(256), 0, st, ctx->dd, g.n, g.nsplit, g.ch.phase, w,
+        I8_SWITCH(ctx, NB_SWITCH(ctx, hipLaunchKernelGGL((k_rowpass<NB_, MODE, S_, false>), grid, dim3(256), 0, st, ctx->dd, g.n, ctx->nsplit, g.ch.phase, w,
                                                         out0, nullptr, g.ch.gpart, g.ch.ljl_part, vs, g.ctile, g.ch.cstale)));
       } else {
-        I8_SWITCH(ctx, NB_SWITCH(ctx, hipLaunchKernelGGL((k_rowpass<NB_, MODE, S_>), grid, dim3(256), 0, st, ctx->dd, g.n, g.nsplit, g.ch.phase, w, out0,
+        I8_SWITCH(ctx, NB_SWITCH(ctx, hipLaunchKernelGGL((k_rowpass<NB_, MODE, S_>), grid, dim3(256), 0, st, ctx->dd, g.n, ctx->nsplit, g.ch.phase, w, out0,
                                                         out2, g.ch.gpart, g.ch.ljl_part, vs, g.ctile, g.ch.cstale)));
       }
       return;
     }
-    NB_SWITCH(ctx, hipLaunchKernelGGL((k_rowpass<NB_, MODE>), grid, dim3(256), 0, st, ctx->dd, g.n, g.nsplit, g.ch.phase, w, out0,
+    NB_SWITCH(ctx, hipLaunchKernelGGL((k_rowpass<NB_, MODE>), grid, dim3(256), 0, st, ctx->dd, g.n, ctx->nsplit, g.ch.phase, w, out0,
                                       out2, g.ch.gpart, g.ch.ljl_part, VSlice{}, g.ctile, g.ch.cstale));
   });
 }
@@ -320,36 +283,29 @@ void launch_assemble_i8_t(rmhmc_ctx* ctx, Group& g, const double* v, hipStream_t
                        ctx->D, ctx->DP, ctx->dd.inv_alpha, g.ch.Gq, g.vexp, VDelta{});
     return;
   }
-  const int nCB = g.nCp / I8_BM, nPB = ctx->pairs.NPp / (32 * TN * WN);
   constexpr int lds = i8_lds_bytes<S, WN, TN>();
-  const unsigned nblk = (unsigned)(nCB < 8 ? nCB * nPB : (nCB + 7) / 8 * 8 * nPB);  // (fewer than 8 chain blocks: tiles are dealt round)
-  if (g.ksplit_a > 1) {  // small batch: too few tiles to fill the chip, so the k range is cut into planes that are summed afterwards
+  const I8Geometry t = i8_geometry(*ctx, g.nCp, WN, TN, WN == 4);  // (k_assemble_i8_tail pairs with the 8-wave tile)
+  if (ctx->ksplit_a > 1) {  // small batch: too few tiles to fill the chip, so the k range is cut into planes that are summed afterwards
+    // (a plan with k pieces has no tail accumulators: the main tiles are all pair blocks)
     const size_t plane = (size_t)g.n * ctx->DP * ctx->DP;
-    hipLaunchKernelGGL((k_assemble_i8<S, WN, TN>), dim3(nblk, (unsigned)g.ksplit_a), dim3(128 * WN), lds, st, g.Vs, ctx->d_Zs, g.nCp, ctx->i8_nks,
-                       0, ctx->i8_nks, 0, ctx->pairs, g.n, g.ch.phase, g.vbad, ctx->DP, ctx->dd.inv_alpha, g.Gpart, plane, g.vexp, nPB,
+    hipLaunchKernelGGL((k_assemble_i8<S, WN, TN>), dim3(t.nblk_main, (unsigned)ctx->ksplit_a), dim3(128 * WN), lds, st, g.Vs, ctx->d_Zs, g.nCp, ctx->i8_nks,
+                       0, ctx->i8_nks, 0, ctx->pairs, g.n, g.ch.phase, g.vbad, ctx->DP, ctx->dd.inv_alpha, g.Gpart, plane, g.vexp, t.npb,
                        I8Delta{nullptr, nullptr, 1.0, 0, 0, nullptr});
-    hipLaunchKernelGGL(k_sum_planes, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, st, g.ch.Gq, g.Gpart, g.ksplit_a, plane, plane);
+    hipLaunchKernelGGL(k_sum_planes, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, st, g.ch.Gq, g.Gpart, ctx->ksplit_a, plane, plane);
     return;
   }
-  // Ragged last pair block (D = 64: 2080 pairs = 16 blocks of 128 + 32): once the full blocks alone fill the chip, the rest goes to
-  // k_assemble_i8_tail (bit-identical results, see there).  option i8_tail = 0 / 1: never / whenever there is a ragged block.
-  const int nPBfull = ctx->pairs.NP / (32 * TN * WN);
-  const bool tail = WN == 4 && g.Tq && nPBfull < nPB && (ctx->opt.i8_tail == 1 || (ctx->opt.i8_tail < 0 && (long long)nCB * nPBfull >= 256));
-  const int npb = tail ? nPBfull : nPB;
-  const unsigned nblk_main = (unsigned)(nCB < 8 ? nCB * npb : (nCB + 7) / 8 * 8 * npb);
-  const int pb32_0 = nPBfull * TN * WN, ntail = (ctx->pairs.NP - pb32_0 * 32 + 31) / 32;
   // the k range in pieces whose int32 sums cannot overflow whatever the data (one piece up to M = 21845 at 6 slices)
   for (int ks0 = 0; ks0 < ctx->i8_nks; ks0 += ctx->i8_chunk) {
     const int nk = std::min(ctx->i8_chunk, ctx->i8_nks - ks0);
-    if (nblk_main)
-      hipLaunchKernelGGL((k_assemble_i8<S, WN, TN>), dim3(nblk_main), dim3(128 * WN), lds, st, Vs, ctx->d_Zs, g.nCp,
-                         ctx->i8_nks, ks0, nk, (ks0 > 0 ? 1 : 0) | acc0, ctx->pairs, g.n, g.ch.phase, g.vbad, ctx->DP, ctx->dd.inv_alpha, g.ch.Gq, (size_t)0, vexp, npb, dl);
-    if (tail) {
-      const int pieces = std::max(1, std::min({g.tail_pieces, nk / 8, (int)(256 / std::max(1, nCB * ntail))}));
-      hipLaunchKernelGGL((k_assemble_i8_tail<S>), dim3((unsigned)(nCB * ntail), (unsigned)pieces), dim3(128), (i8_lds_bytes<S, 1, 1>()), st, Vs, ctx->d_Zs,
-                         g.nCp, ctx->pairs.NPp, ctx->pairs.NP, ctx->i8_nks, ks0, nk, g.n, pb32_0, ntail, g.Tq, dl);
-      hipLaunchKernelGGL((k_assemble_i8_tailsum<S>), dim3((unsigned)(((size_t)g.n * 32 * ntail + 255) / 256)), dim3(256), 0, st, g.Tq, pieces, g.nCp, ntail,
-                         pb32_0, (ks0 > 0 ? 1 : 0) | acc0, ctx->pairs, g.n, g.ch.phase, g.vbad, ctx->DP, ctx->dd.inv_alpha, g.ch.Gq, vexp, dl);
+    if (t.nblk_main)
+      hipLaunchKernelGGL((k_assemble_i8<S, WN, TN>), dim3(t.nblk_main), dim3(128 * WN), lds, st, Vs, ctx->d_Zs, g.nCp,
+                         ctx->i8_nks, ks0, nk, (ks0 > 0 ? 1 : 0) | acc0, ctx->pairs, g.n, g.ch.phase, g.vbad, ctx->DP, ctx->dd.inv_alpha, g.ch.Gq, (size_t)0, vexp, t.npb, dl);
+    if (t.tail) {
+      const int pieces = i8_tail_pieces(*ctx, t, nk);
+      hipLaunchKernelGGL((k_assemble_i8_tail<S>), dim3((unsigned)(t.nCB * t.ntail), (unsigned)pieces), dim3(128), (i8_lds_bytes<S, 1, 1>()), st, Vs, ctx->d_Zs,
+                         g.nCp, ctx->pairs.NPp, ctx->pairs.NP, ctx->i8_nks, ks0, nk, g.n, t.pb32_0, t.ntail, g.Tq, dl);
+      hipLaunchKernelGGL((k_assemble_i8_tailsum<S>), dim3((unsigned)(((size_t)g.n * 32 * t.ntail + 255) / 256)), dim3(256), 0, st, g.Tq, pieces, g.nCp, t.ntail,
+                         t.pb32_0, (ks0 > 0 ? 1 : 0) | acc0, ctx->pairs, g.n, g.ch.phase, g.vbad, ctx->DP, ctx->dd.inv_alpha, g.ch.Gq, vexp, dl);
     }
   }
 }
@@ -359,14 +315,9 @@ void launch_assemble_i8_delta(rmhmc_ctx* ctx, Group& g, hipStream_t st, int seff
   constexpr int WN = 4, TN = 1;
   const size_t vplane = (size_t)ctx->i8_nks * g.nCp * 32;
   const I8Delta dl{g.dmax, g.rebase, 1.0, 0, 0, ctx->big ? g.Gbase : nullptr};
-  const int nCB = g.nCp / I8_BM, nPB = ctx->pairs.NPp / (32 * TN * WN);
+  const I8Geometry t = i8_geometry(*ctx, g.nCp, WN, TN);
   constexpr int lds = i8_lds_bytes<6, WN, TN>() > i8_lds_bytes<4, WN, TN>() ? i8_lds_bytes<6, WN, TN>() : i8_lds_bytes<4, WN, TN>();
   static_assert(lds >= (i8_lds_bytes<5, WN, TN>()), "dynamic LDS of the widest instantiation");
-  const int nPBfull = ctx->pairs.NP / (32 * TN * WN);
-  const bool tail = g.Tq && nPBfull < nPB && (ctx->opt.i8_tail == 1 || (ctx->opt.i8_tail < 0 && (long long)nCB * nPBfull >= 256));
-  const int npb = tail ? nPBfull : nPB;
-  const unsigned nblk_main = (unsigned)(nCB < 8 ? nCB * npb : (nCB + 7) / 8 * 8 * npb);
-  const int pb32_0 = nPBfull * TN * WN, ntail = (ctx->pairs.NP - pb32_0 * 32 + 31) / 32;
   constexpr int lds_t = i8_lds_bytes<6, 1, 1>() > i8_lds_bytes<4, 1, 1>() ? i8_lds_bytes<6, 1, 1>() : i8_lds_bytes<4, 1, 1>();
   static_assert(lds_t >= (i8_lds_bytes<5, 1, 1>()), "dynamic LDS of the widest tail instantiation");
   // the assembly is counted once (g.dcount): by the first k piece's main launch, or by its tail launch when there are no main tiles
@@ -374,16 +325,16 @@ void launch_assemble_i8_delta(rmhmc_ctx* ctx, Group& g, hipStream_t st, int seff
   dlc.count = g.dcount;
   for (int ks0 = 0; ks0 < ctx->i8_nks; ks0 += ctx->i8_chunk) {
     const int nk = std::min(ctx->i8_chunk, ctx->i8_nks - ks0);
-    if (nblk_main)
-      hipLaunchKernelGGL((k_assemble_i8_sel<WN, TN>), dim3(nblk_main), dim3(128 * WN), lds, st, g.Vs, vplane, seff, ctx->d_Zs, g.nCp, ctx->i8_nks, ks0, nk,
-                         (ks0 > 0 ? 1 : 0) | 2, ctx->pairs, g.n, g.ch.phase, g.vbad, ctx->DP, ctx->dd.inv_alpha, g.ch.Gq, (size_t)0, g.vexp_d, npb,
+    if (t.nblk_main)
+      hipLaunchKernelGGL((k_assemble_i8_sel<WN, TN>), dim3(t.nblk_main), dim3(128 * WN), lds, st, g.Vs, vplane, seff, ctx->d_Zs, g.nCp, ctx->i8_nks, ks0, nk,
+                         (ks0 > 0 ? 1 : 0) | 2, ctx->pairs, g.n, g.ch.phase, g.vbad, ctx->DP, ctx->dd.inv_alpha, g.ch.Gq, (size_t)0, g.vexp_d, t.npb,
                          ks0 == 0 ? dlc : dl);
-    if (tail) {
-      const int pieces = std::max(1, std::min({g.tail_pieces, nk / 8, (int)(256 / std::max(1, nCB * ntail))}));
-      hipLaunchKernelGGL(k_assemble_i8_tail_sel, dim3((unsigned)(nCB * ntail), (unsigned)pieces), dim3(128), lds_t, st, g.Vs, vplane, seff, ctx->d_Zs,
-                         g.nCp, ctx->pairs.NPp, ctx->pairs.NP, ctx->i8_nks, ks0, nk, g.n, pb32_0, ntail, g.Tq, (ks0 == 0 && !nblk_main) ? dlc : dl);
-      hipLaunchKernelGGL(k_assemble_i8_tailsum_sel, dim3((unsigned)(((size_t)g.n * 32 * ntail + 255) / 256)), dim3(256), 0, st, seff, g.Tq, pieces, g.nCp, ntail,
-                         pb32_0, (ks0 > 0 ? 1 : 0) | 2, ctx->pairs, g.n, g.ch.phase, g.vbad, ctx->DP, ctx->dd.inv_alpha, g.ch.Gq, g.vexp_d, dl);
+    if (t.tail) {
+      const int pieces = i8_tail_pieces(*ctx, t, nk);
+      hipLaunchKernelGGL(k_assemble_i8_tail_sel, dim3((unsigned)(t.nCB * t.ntail), (unsigned)pieces), dim3(128), lds_t, st, g.Vs, vplane, seff, ctx->d_Zs,
+                         g.nCp, ctx->pairs.NPp, ctx->pairs.NP, ctx->i8_nks, ks0, nk, g.n, t.pb32_0, t.ntail, g.Tq, (ks0 == 0 && !t.nblk_main) ? dlc : dl);
+      hipLaunchKernelGGL(k_assemble_i8_tailsum_sel, dim3((unsigned)(((size_t)g.n * 32 * t.ntail + 255) / 256)), dim3(256), 0, st, seff, g.Tq, pieces, g.nCp, t.ntail,
+                         t.pb32_0, (ks0 > 0 ? 1 : 0) | 2, ctx->pairs, g.n, g.ch.phase, g.vbad, ctx->DP, ctx->dd.inv_alpha, g.ch.Gq, g.vexp_d, dl);
     }
   }
 }
@@ -398,11 +349,11 @@ void launch_leverage_i8_t(rmhmc_ctx* ctx, Group& g, hipStream_t st, int part) {
   const int nCB = g.nCp / I8_BM, nRB = ctx->i8_NRp / (32 * TN * WN);
   constexpr int lds = i8_lds_bytes<S, WN, TN>();
   const unsigned nblk = (unsigned)(nCB < 8 ? nCB * nRB : (nCB + 7) / 8 * 8 * nRB);
-  if (g.ksplit_l > 1) {
+  if (ctx->ksplit_l > 1) {
     const size_t plane = (size_t)g.n * ctx->Mp;
-    hipLaunchKernelGGL((k_leverage_i8<S, WN, TN>), dim3(nblk, (unsigned)g.ksplit_l), dim3(128 * WN), lds, st, g.Qs, ctx->d_Zt, g.nCp, ctx->i8_NRp,
+    hipLaunchKernelGGL((k_leverage_i8<S, WN, TN>), dim3(nblk, (unsigned)ctx->ksplit_l), dim3(128 * WN), lds, st, g.Qs, ctx->d_Zt, g.nCp, ctx->i8_NRp,
                        ctx->i8_nkp, 0, ctx->i8_nkp, 0, (ctx->big || g.ctile) ? 0 : 1, g.n, ctx->Mp, g.ch.phase, g.qscale, ctx->d_zscale, g.ch.rv2, g.Rpart, plane);
-    hipLaunchKernelGGL(k_sum_planes, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, st, g.ch.rv0, g.Rpart, g.ksplit_l, plane, plane);
+    hipLaunchKernelGGL(k_sum_planes, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, st, g.ch.rv0, g.Rpart, ctx->ksplit_l, plane, plane);
     return;
   }
   for (int kp0 = 0; kp0 < ctx->i8_nkp; kp0 += ctx->i8_chunk) {
@@ -456,11 +407,11 @@ void launch_assemble(rmhmc_ctx* ctx, Group& g, const double* v, bool inner = fal
                          g.ch.Gq);
       return;
     }
-    if (g.fsplit > 1) {  // small batch: row ranges into planes, summed in a fixed order
+    if (ctx->fsplit > 1) {  // small batch: row ranges into planes, summed in a fixed order
       const size_t plane = (size_t)g.n * ctx->DP * ctx->DP;
-      dim3 grid((unsigned)((g.n + 3) / 4), (unsigned)g.fsplit);
+      dim3 grid((unsigned)((g.n + 3) / 4), (unsigned)ctx->fsplit);
       NB_SWITCH(ctx, hipLaunchKernelGGL((k_assemble<NB_>), grid, dim3(256), 0, st, ctx->dd, g.n, g.ch.phase, v, g.Gpart, plane));
-      hipLaunchKernelGGL(k_sum_planes, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, st, g.ch.Gq, g.Gpart, g.fsplit, plane, plane);
+      hipLaunchKernelGGL(k_sum_planes, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, st, g.ch.Gq, g.Gpart, ctx->fsplit, plane, plane);
       return;
     }
     dim3 grid((unsigned)((g.n + 3) / 4));
@@ -474,22 +425,22 @@ void launch_mompass(rmhmc_ctx* ctx, Group& g, const double* w, int cmode) {
   launch(ctx, "mompass", [&](hipStream_t st) {
     if (!ctx->opt.ccache) cmode = 0;
     if (ctx->big) {
-      dim3 grid((unsigned)((g.n + 15) / 16), g.nsplit);
+      dim3 grid((unsigned)((g.n + 15) / 16), ctx->nsplit);
       switch (cmode) {
-        case 1: hipLaunchKernelGGL(k_mompass_big<1>, grid, dim3(256), 0, st, ctx->dd, g.n, g.nsplit, ctx->nbk, w, g.ch.uq, g.ch.qpart, g.ctile); break;
-        case 2: hipLaunchKernelGGL(k_mompass_big<2>, grid, dim3(256), 0, st, ctx->dd, g.n, g.nsplit, ctx->nbk, w, g.ch.uq, g.ch.qpart, g.ctile); break;
-        default: hipLaunchKernelGGL(k_mompass_big<0>, grid, dim3(256), 0, st, ctx->dd, g.n, g.nsplit, ctx->nbk, w, g.ch.uq, g.ch.qpart, g.ctile); break;
+        case 1: hipLaunchKernelGGL(k_mompass_big<1>, grid, dim3(256), 0, st, ctx->dd, g.n, ctx->nsplit, ctx->nbk, w, g.ch.uq, g.ch.qpart, g.ctile); break;
+        case 2: hipLaunchKernelGGL(k_mompass_big<2>, grid, dim3(256), 0, st, ctx->dd, g.n, ctx->nsplit, ctx->nbk, w, g.ch.uq, g.ch.qpart, g.ctile); break;
+        default: hipLaunchKernelGGL(k_mompass_big<0>, grid, dim3(256), 0, st, ctx->dd, g.n, ctx->nsplit, ctx->nbk, w, g.ch.uq, g.ch.qpart, g.ctile); break;
       }
       return;
     }
-    dim3 grid((unsigned)((g.n + 63) / 64), g.nsplit);
+    dim3 grid((unsigned)((g.n + 63) / 64), ctx->nsplit);
     switch (cmode) {
       case 1:  // first pass of a step at this w: the tiles are at hand unless the chain has just rejected a proposal (k_mompass<.., 3>)
-        if (ctx->opt.cdyn) { NB_SWITCH(ctx, hipLaunchKernelGGL((k_mompass<NB_, 3>), grid, dim3(256), 0, st, ctx->dd, g.n, g.nsplit, w, g.ch.uq, g.ch.qpart, g.ctile, g.ch.cstale)); }
-        else { NB_SWITCH(ctx, hipLaunchKernelGGL((k_mompass<NB_, 1>), grid, dim3(256), 0, st, ctx->dd, g.n, g.nsplit, w, g.ch.uq, g.ch.qpart, g.ctile)); }
+        if (ctx->opt.cdyn) { NB_SWITCH(ctx, hipLaunchKernelGGL((k_mompass<NB_, 3>), grid, dim3(256), 0, st, ctx->dd, g.n, ctx->nsplit, w, g.ch.uq, g.ch.qpart, g.ctile, g.ch.cstale)); }
+        else { NB_SWITCH(ctx, hipLaunchKernelGGL((k_mompass<NB_, 1>), grid, dim3(256), 0, st, ctx->dd, g.n, ctx->nsplit, w, g.ch.uq, g.ch.qpart, g.ctile)); }
         break;
-      case 2: NB_SWITCH(ctx, hipLaunchKernelGGL((k_mompass<NB_, 2>), grid, dim3(256), 0, st, ctx->dd, g.n, g.nsplit, w, g.ch.uq, g.ch.qpart, g.ctile)); break;
-      default: NB_SWITCH(ctx, hipLaunchKernelGGL((k_mompass<NB_, 0>), grid, dim3(256), 0, st, ctx->dd, g.n, g.nsplit, w, g.ch.uq, g.ch.qpart, g.ctile)); break;
+      case 2: NB_SWITCH(ctx, hipLaunchKernelGGL((k_mompass<NB_, 2>), grid, dim3(256), 0, st, ctx->dd, g.n, ctx->nsplit, w, g.ch.uq, g.ch.qpart, g.ctile)); break;
+      default: NB_SWITCH(ctx, hipLaunchKernelGGL((k_mompass<NB_, 0>), grid, dim3(256), 0, st, ctx->dd, g.n, ctx->nsplit, w, g.ch.uq, g.ch.qpart, g.ctile)); break;
     }
   });
 }
@@ -502,7 +453,7 @@ static bool fused_trace(const rmhmc_ctx* ctx, const Group& g) { return ctx->i8 &
 void launch_leverage(rmhmc_ctx* ctx, Group& g, int part = 0) {
   if (ctx->i8 && part == 2) {
     launch(ctx, "small", [&](hipStream_t st) {
-      hipLaunchKernelGGL(k_reduce_tr, dim3((unsigned)g.n), dim3(64), 0, st, ctx->D, ctx->DP, g.ch, g.ch.gpart, g.nsplit);
+      hipLaunchKernelGGL(k_reduce_tr, dim3((unsigned)g.n), dim3(64), 0, st, ctx->D, ctx->DP, g.ch, g.ch.gpart, ctx->nsplit);
     });
     return;
   }
@@ -516,15 +467,15 @@ void launch_leverage(rmhmc_ctx* ctx, Group& g, int part = 0) {
     if (part == 1) return;
     launch(ctx, "trvec", [&](hipStream_t st) {
       if (ctx->big) {  // rv0 holds h (one "pair" plane), the large-D trace kernel multiplies by c itself
-        dim3 grid((unsigned)((g.n + 15) / 16), g.nsplit);
-        hipLaunchKernelGGL(k_trace_big, grid, dim3(256), 0, st, ctx->dd, g.n, g.nsplit, ctx->nbk, 1, g.ch.rv2, g.ch.rv0, g.ch.gpart);
+        dim3 grid((unsigned)((g.n + 15) / 16), ctx->nsplit);
+        hipLaunchKernelGGL(k_trace_big, grid, dim3(256), 0, st, ctx->dd, g.n, ctx->nsplit, ctx->nbk, 1, g.ch.rv2, g.ch.rv0, g.ch.gpart);
         return;
       }
-      dim3 grid((unsigned)((g.n + 63) / 64), g.nsplit);
-      NB_SWITCH(ctx, hipLaunchKernelGGL((k_trvec<NB_>), grid, dim3(256), 0, st, ctx->dd, g.n, g.nsplit, g.ch.rv0, g.ch.gpart, (const d4*)g.ctile));
+      dim3 grid((unsigned)((g.n + 63) / 64), ctx->nsplit);
+      NB_SWITCH(ctx, hipLaunchKernelGGL((k_trvec<NB_>), grid, dim3(256), 0, st, ctx->dd, g.n, ctx->nsplit, g.ch.rv0, g.ch.gpart, (const d4*)g.ctile));
     });
     launch(ctx, "small", [&](hipStream_t st) {
-      hipLaunchKernelGGL(k_reduce_tr, dim3((unsigned)g.n), dim3(64), 0, st, ctx->D, ctx->DP, g.ch, g.ch.gpart, g.nsplit);
+      hipLaunchKernelGGL(k_reduce_tr, dim3((unsigned)g.n), dim3(64), 0, st, ctx->D, ctx->DP, g.ch, g.ch.gpart, ctx->nsplit);
     });
     return;
   }
@@ -537,15 +488,15 @@ void launch_leverage(rmhmc_ctx* ctx, Group& g, int part = 0) {
                          g.ch.phase, g.ch.trj.Ginv, hpart);
     });
     launch(ctx, "leverage", [&](hipStream_t st) {
-      dim3 grid((unsigned)((g.n + 15) / 16), g.nsplit);
-      hipLaunchKernelGGL(k_trace_big, grid, dim3(256), 0, st, ctx->dd, g.n, g.nsplit, ctx->nbk, ctx->npairs, g.ch.rv2, hpart, g.ch.gpart);
+      dim3 grid((unsigned)((g.n + 15) / 16), ctx->nsplit);
+      hipLaunchKernelGGL(k_trace_big, grid, dim3(256), 0, st, ctx->dd, g.n, ctx->nsplit, ctx->nbk, ctx->npairs, g.ch.rv2, hpart, g.ch.gpart);
     });
     launch(ctx, "small", [&](hipStream_t st) {
-      hipLaunchKernelGGL(k_reduce_tr, dim3((unsigned)g.n), dim3(64), 0, st, ctx->D, ctx->DP, g.ch, g.ch.gpart, g.nsplit);
+      hipLaunchKernelGGL(k_reduce_tr, dim3((unsigned)g.n), dim3(64), 0, st, ctx->D, ctx->DP, g.ch, g.ch.gpart, ctx->nsplit);
     });
     return;
   }
-  const int fs = std::min(g.fsplit, g.nsplit);  // (the partials go to gpart, which holds nsplit planes)
+  const int fs = std::min(ctx->fsplit, ctx->nsplit);  // (the partials go to gpart, which holds nsplit planes)
   launch(ctx, "leverage", [&](hipStream_t st) {
     dim3 grid((unsigned)((g.n + 3) / 4), (unsigned)fs);
     NB_SWITCH(ctx, hipLaunchKernelGGL((k_leverage<NB_>), grid, dim3(256), 0, st, ctx->dd, g.n, g.ch.phase, g.ch.trj.Ginv, g.ch.rv2,
@@ -573,7 +524,7 @@ void eval_point_phases(rmhmc_ctx* ctx, Group& g, bool advance, int mode = 0) {
   // (advance: the evaluation that ends a leapfrog step - the last position iterate's slices and G are at hand)
   const bool delta = advance && use_delta(ctx, g);
   launch_rowpass<RP_F>(ctx, g, g.ch.trj.w, g.ch.rv0, g.ch.rv2, delta);
-  if (ctx->big) SMALL(ctx, g, "small", k_finish_big, ctx->dd, g.ch, g.nsplit);
+  if (ctx->big) SMALL(ctx, g, "small", k_finish_big, ctx->dd, g.ch, ctx->nsplit);
   launch_assemble(ctx, g, g.ch.rv0, false, delta);
   if (ctx->big) {
     if (ctx->want_G)
@@ -583,7 +534,7 @@ void eval_point_phases(rmhmc_ctx* ctx, Group& g, bool advance, int mode = 0) {
     SMALL(ctx, g, "small", k_ginv_matvec, ctx->D, ctx->DP, g.ch, g.ch.p);
   } else {
     launch(ctx, "factor", [&](hipStream_t st) {
-      NB_SWITCH(ctx, hipLaunchKernelGGL((k_factor_full<NB_>), dim3((unsigned)g.n), dim3(64), 0, st, ctx->dd, g.ch, g.nsplit));
+      NB_SWITCH(ctx, hipLaunchKernelGGL((k_factor_full<NB_>), dim3((unsigned)g.n), dim3(64), 0, st, ctx->dd, g.ch, ctx->nsplit));
     });
   }
   if (mode == 1) return;  // simplified mMALA needs neither the quadratic nor the trace term
@@ -594,14 +545,14 @@ void eval_point_phases(rmhmc_ctx* ctx, Group& g, bool advance, int mode = 0) {
   if (fused_trace(ctx, g)) {  // leverage GEMM first, then ONE pass for the quadratic term and the trace term
     launch_leverage(ctx, g, 1);
     launch(ctx, "mompass", [&](hipStream_t st) {
-      dim3 grid((unsigned)((g.n + 63) / 64), g.nsplit);
-      NB_SWITCH(ctx, hipLaunchKernelGGL((k_mompass_trv<NB_>), grid, dim3(256), 0, st, ctx->dd, g.n, g.nsplit, g.ch.uq, g.ch.qpart, g.ctile, g.ch.rv0, g.ch.gpart));
+      dim3 grid((unsigned)((g.n + 63) / 64), ctx->nsplit);
+      NB_SWITCH(ctx, hipLaunchKernelGGL((k_mompass_trv<NB_>), grid, dim3(256), 0, st, ctx->dd, g.n, ctx->nsplit, g.ch.uq, g.ch.qpart, g.ctile, g.ch.rv0, g.ch.gpart));
     });  // (k_mom_final below sums the trace partials itself)
   } else {
     launch_mompass(ctx, g, g.ch.trj.w, 2);  // (the row pass above has just stored c for trj.w)
     launch_leverage(ctx, g);
   }
-  SMALL(ctx, g, "small", k_mom_final, ctx->D, ctx->DP, g.ch, ctx->eps, advance ? 1 : 0, g.nsplit, fused_trace(ctx, g) ? g.ch.gpart : (const double*)nullptr);
+  SMALL(ctx, g, "small", k_mom_final, ctx->D, ctx->DP, g.ch, ctx->eps, advance ? 1 : 0, ctx->nsplit, fused_trace(ctx, g) ? g.ch.gpart : (const double*)nullptr);
 }
 
 // one-launch step / evaluation / folded global step for small batches (medium_step.hip.h).  Data rows per thread stay in registers
@@ -654,8 +605,8 @@ void step_phases(rmhmc_ctx* ctx, Group& g) {
   for (int it = 0; it < K; ++it) {
     if (it == 0 || !fuse) SMALL(ctx, g, "small", k_ginv_matvec, D, DP, g.ch, it == 0 ? g.ch.p : g.ch.PM);
     launch_mompass(ctx, g, g.ch.trj.w, it == 0 ? 1 : 2);
-    if (!fuse) SMALL(ctx, g, "small", k_mom_update, D, DP, g.ch, eps, it == K - 1 ? 1 : 0, g.nsplit);
-    else if (it < K - 1) SMALL(ctx, g, "small", k_mom_update_matvec, D, DP, g.ch, eps, g.nsplit);
+    if (!fuse) SMALL(ctx, g, "small", k_mom_update, D, DP, g.ch, eps, it == K - 1 ? 1 : 0, ctx->nsplit);
+    else if (it < K - 1) SMALL(ctx, g, "small", k_mom_update_matvec, D, DP, g.ch, eps, ctx->nsplit);
   }
   // implicit position step: K fixed-point iterations (rmhmc.py:113-123); the first one re-uses the
   // stored factor of G(w)
@@ -663,7 +614,7 @@ void step_phases(rmhmc_ctx* ctx, Group& g) {
     SMALL(ctx, g, "small", k_ginv_matvec, D, DP, g.ch, g.ch.p);
     SMALL(ctx, g, "small", k_pos_first_big, D, DP, g.ch, eps);
   } else {
-    SMALL(ctx, g, "factor", k_pos_first, D, DP, g.ch, eps, g.nsplit);
+    SMALL(ctx, g, "factor", k_pos_first, D, DP, g.ch, eps, ctx->nsplit);
   }
   for (int it = 1; it < K; ++it) {
     launch_rowpass<RP_V>(ctx, g, g.ch.wq, g.ch.rv0, nullptr, use_delta_inner(ctx, g, it));
@@ -745,7 +696,7 @@ void launch_hmc_global_step(rmhmc_ctx* ctx, Group& g, const IterBase& b) {
   } else {
     SMALL(ctx, g, "small", k_hmc_pre, ctx->D, ctx->DP, g.ch, eps);
     launch_rowpass<RP_G>(ctx, g, g.ch.trj.w, nullptr);
-    SMALL(ctx, g, "small", k_hmc_post, ctx->dd, g.ch, eps, g.nsplit);
+    SMALL(ctx, g, "small", k_hmc_post, ctx->dd, g.ch, eps, ctx->nsplit);
   }
   SMALL(ctx, g, "small", k_hmc_end, ctx->D, ctx->DP, g.ch, ip);
 }
@@ -818,6 +769,13 @@ int sync(rmhmc_ctx* ctx) {
 }
 
 #define RC(x) do { int rc_ = (x); if (rc_ != RMHMC_OK) return rc_; } while (0)
+// ... of every row-per-thread instantiation of the one-launch step
+template <int NB, int... RPT>
+int raise_lds_medium(rmhmc_ctx* ctx) {
+  for (const void* k : {(const void*)k_step_medium<NB, RPT>...}) RC(raise_lds(ctx, k, MAX_LDS));
+  return RMHMC_OK;
+}
+
 #define NEED_DATA(ctx)                                                              \
   do {                                                                              \
     if (!(ctx)) return fail(nullptr, RMHMC_ERR_INVALID, "null context");            \
@@ -868,24 +826,20 @@ int rmhmc_create(rmhmc_ctx** out, int32_t device_id, int64_t M, int32_t D, int64
 int rmhmc_create_opts(rmhmc_ctx** out, int32_t device_id, int64_t M, int32_t D, int64_t n_chains, int32_t dtype, uint32_t flags,
                       const rmhmc_option* opts, int32_t n_opts) {
   rmhmc_ctx* ctx = nullptr;  // for the macros: errors go to the global message
+  // 1. the options
   Options opt{};
   if (n_opts < 0 || (n_opts > 0 && !opts)) return fail(nullptr, RMHMC_ERR_INVALID, "rmhmc_create_opts: bad option array");
   for (int i = 0; i < n_opts; ++i) {
     const OptionDesc* d = find_option(opts[i].key);
-    if (!d) return fail(nullptr, RMHMC_ERR_INVALID, std::string("rmhmc_create_opts: unknown option '") + (opts[i].key ? opts[i].key : "(null)") + "'");
-    if (opts[i].value < d->lo || opts[i].value > d->hi)
-      return fail(nullptr, RMHMC_ERR_INVALID, std::string("rmhmc_create_opts: value out of range for option '") + d->key + "'");
-    opt.*(d->slot) = opts[i].value;
+    switch (check_option(d, opts[i].value, true)) {
+      case OPT_UNKNOWN: return fail(nullptr, RMHMC_ERR_INVALID, std::string("rmhmc_create_opts: unknown option '") + (opts[i].key ? opts[i].key : "(null)") + "'");
+      case OPT_RANGE: return fail(nullptr, RMHMC_ERR_INVALID, std::string("rmhmc_create_opts: value out of range for option '") + d->key + "'");
+      default: opt.*(d->slot) = opts[i].value; break;
+    }
   }
-  if (!out || M <= 0 || D <= 0 || n_chains <= 0) return fail(nullptr, RMHMC_ERR_INVALID, "rmhmc_create: bad shape");
-  if (dtype != RMHMC_F64) return fail(nullptr, RMHMC_ERR_UNSUPPORTED, "rmhmc_create: only float64 is built (the reference is float64)");
-  if (D > 256) return fail(nullptr, RMHMC_ERR_UNSUPPORTED, "rmhmc_create: D > 256 is not supported (64 < D <= 256 uses the blocked large-D path)");
-  if (flags & RMHMC_FLAG_ORACLE_LITERAL) return fail(nullptr, RMHMC_ERR_UNSUPPORTED, "rmhmc_create: the literal variant exists only in the CPU oracle");
-  if (M > (int64_t)1 << 30 || n_chains > (int64_t)1 << 30) return fail(nullptr, RMHMC_ERR_UNSUPPORTED, "rmhmc_create: M or n_chains too large");
-  // (the row passes of the D <= 64 path address X, the batch's c tiles and its leverages with 32-bit byte offsets from a buffer
-  //  descriptor's base: buf_rsrc in kernels.hip.h)
-  if (D <= 64 && (M + 63) / 64 * 64 * (int64_t)(16 * ((D + 15) / 16)) * 8 >= (int64_t)1 << 32)
-    return fail(nullptr, RMHMC_ERR_UNSUPPORTED, "rmhmc_create: the data matrix of the D <= 64 path must stay below 4 GB");
+  // 2. the arguments, before any device call
+  if (!out) return fail(nullptr, RMHMC_ERR_INVALID, "rmhmc_create: bad shape");
+  if (const PlanCheck chk = plan_check(M, D, n_chains, dtype, flags); chk.code != RMHMC_OK) return fail(nullptr, chk.code, chk.msg);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return fail(nullptr, RMHMC_ERR_NO_DEVICE, "rmhmc_create: no HIP device available (this library has no CPU fallback)");
@@ -895,19 +849,14 @@ int rmhmc_create_opts(rmhmc_ctx** out, int32_t device_id, int64_t M, int32_t D, 
   HIPCK(hipGetDeviceProperties(&prop, device_id));
   if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
     return fail(nullptr, RMHMC_ERR_NO_DEVICE, std::string("rmhmc_create: kernels are built for gfx950 only, device is ") + prop.gcnArchName);
+  // 3. every shape (plan.h)
   ctx = new rmhmc_ctx();
+  static_cast<Plan&>(*ctx) = make_plan(M, D, n_chains, flags, opt);
   ctx->device = device_id;
-  ctx->M = M; ctx->D = D; ctx->n = n_chains; ctx->flags = flags; ctx->opt = opt;
-  ctx->NB = (D + 15) / 16; ctx->DP = 16 * ctx->NB;
-  if (D > 64) {  // large-D path: 64-column blocks, NB = 4 tiles inside a block
-    ctx->big = true;
-    ctx->nbk = (D + 63) / 64;
-    ctx->npairs = ctx->nbk * (ctx->nbk + 1) / 2;
-    ctx->DP = 64 * ctx->nbk;
-    ctx->NB = 4;
-  }
-  ctx->Mp = (int)((M + 63) / 64 * 64); ctx->nblk = ctx->Mp / 64;
+  ctx->flags = flags; ctx->opt = opt;
+  ctx->i8 = ctx->i8_requested;
   if (flags & RMHMC_FLAG_INT8_INNER_FULL) ctx->i8_inner_drop = 0;
+  // 4. the allocations the plan asks for, and the LDS limits of the kernels it selects
   int rc = RMHMC_OK;
   auto body = [&]() -> int {
     HIPCK(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
@@ -917,9 +866,10 @@ int rmhmc_create_opts(rmhmc_ctx** out, int32_t device_id, int64_t M, int32_t D, 
     double *Xr, *Xt, *t;
     RC(dalloc(ctx, &Xr, Mp * DP)); RC(dalloc(ctx, &Xt, DP * Mp)); RC(dalloc(ctx, &t, Mp));
     ctx->dd.Xr = Xr; ctx->dd.Xt = Xt; ctx->dd.t = t;
-    ctx->dd.M = (int)M; ctx->dd.Mp = ctx->Mp; ctx->dd.D = D; ctx->dd.DP = ctx->DP; ctx->dd.nblk = ctx->nblk;
-    Chains& ch = ctx->batch.ch;
-    ch.n = (int)n;
+    ctx->dd.M = (int)M; ctx->dd.Mp = ctx->Mp; ctx->dd.D = D; ctx->dd.DP = ctx->DP; ctx->dd.nblk = ctx->nblk;  // (kernel arguments)
+    Group& g = ctx->batch;
+    Chains& ch = g.ch;
+    g.n = ch.n = (int)n;
     for (Rec* r : {&ch.cur, &ch.trj}) {
       RC(dalloc(ctx, &r->w, n * DP)); RC(dalloc(ctx, &r->grad, n * DP)); RC(dalloc(ctx, &r->tr, n * DP));
       RC(dalloc(ctx, &r->L, n * DP * DP)); RC(dalloc(ctx, &r->Ginv, n * DP * DP));
@@ -933,179 +883,66 @@ int rmhmc_create_opts(rmhmc_ctx** out, int32_t device_id, int64_t M, int32_t D, 
     RC(dalloc(ctx, &ch.wq, n * DP)); RC(dalloc(ctx, &ch.uq, n * DP)); RC(dalloc(ctx, &ch.PM, n * DP)); RC(dalloc(ctx, &ch.u0, n * DP));
     RC(dalloc(ctx, &ch.q, n * DP)); RC(dalloc(ctx, &ch.last, n * DP)); RC(dalloc(ctx, &ch.Gq, n * DP * DP));
     RC(dalloc(ctx, &ch.rv0, n * Mp)); RC(dalloc(ctx, &ch.rv2, n * Mp));
-    Group& g = ctx->batch;
-    {  // row splits and partial planes
-      g.n = (int)n_chains;
-      // row splits of the 16-chains-per-wave passes (option nsplit_waves).  D <= 64: ~2048 wavefronts per launch = ONE round of two
-      // four-wave workgroups per CU - measured against the 6144 of rounds 1-2 (three rounds) on one box, interleaved: 14.73-14.92
-      // against 14.99-15.08 ms per step at config 3, +2.7 % steps/s at 4096 chains, +6 % at 2048 and 1024 (fewer partial sums to write and
-      // to add up, fewer prologues); the blocked large-D passes keep 6144 (config 5: 472.8 against 475.4 ms per step).
-      const long long cgroups = (g.n + 15) / 16, nb16 = ctx->Mp / 16;
-      const long long target = ctx->opt.nsplit_waves > 0 ? ctx->opt.nsplit_waves : (ctx->big ? 6144 : 2048);
-      long long ns = (target + cgroups - 1) / cgroups;
-      if (ns < 1) ns = 1;
-      if (ns > nb16) ns = nb16;
-      // ... but no more than 64 splits (option nsplit_max): the consumers sum the partials serially.  (Round 1 kept up to Mp/16 splits for
-      // long data sets in small batches, when the one-chain-per-wave assembly dominated those shapes anyway; with the row ranges of
-      // k_assemble / k_leverage it is the serial sums that cost: D 64, M 10000, 64 / 128 / 256 chains: 2.44 / 2.28 / 2.52 -> 1.69 / 1.49 /
-      // 1.99 ms per step, the int8 path at 128-512 chains 10-30 % less; profiles/r02_fp64_batch_sweep.txt)
-      if (ns > ctx->opt.nsplit_max) ns = ctx->opt.nsplit_max;
-      g.nsplit = (int)ns;
-      RC(dalloc(ctx, &g.ch.qpart, (size_t)g.nsplit * g.n * DP));
-      RC(dalloc(ctx, &g.ch.gpart, (size_t)g.nsplit * g.n * DP));
-      RC(dalloc(ctx, &g.ch.ljl_part, (size_t)g.n * g.nsplit));
-      if (ctx->opt.ccache) RC(dalloc(ctx, &g.ctile, (size_t)((g.n + 15) / 16) * (ctx->Mp / 16) * 64));
-      if (!ctx->big) {
-        // fp64 assembly (k_assemble: one chain per wavefront over all M rows): below ~1024 chains the launch has fewer wavefronts than
-        // the chip has SIMDs, so the rows are cut until ~2048 wavefronts exist (at least 256 rows per range, at most 16 ranges).
-        // D 64, M 10000, 512 chains: the step took longer than with 1024 chains (13.0 vs 7.6 ms, profiles/r01_i8_threshold.txt).
-        const long long waves = g.n;
-        long long fs = waves >= 1024 ? 1 : std::min<long long>(16, (2048 + waves - 1) / waves);
-        fs = std::min<long long>(fs, std::max(1, ctx->Mp / 256));
-        if (ctx->opt.fsplit >= 1) fs = ctx->opt.fsplit;
-        g.fsplit = (int)fs;
-      }
-    }
-    int i8_slices = (int)((flags >> 12) & 7u);
-    if (i8_slices == 0) i8_slices = 6;
-    if (i8_slices < 4) i8_slices = 4;
-    // int32 accumulators: a weight-g set sums (g+1) K products of two bytes, |.| <= 2^14 each, so one launch covers at most
-    // i8_chunk stages of 32 (21845 rows at 6 slices); longer contractions are summed over several launches in fp64.
-    if (flags & RMHMC_FLAG_INT8_METRIC) {
-      const int S = i8_slices;
-      ctx->i8_chunk = std::max(1, (int)(2147483647.0 / (S * 16384.0)) / 32);
-      ctx->i8 = true;
-      ctx->i8_requested = true;
-      ctx->i8S = S;
-      ctx->i8_bn = S <= 6 ? 128 : 64;
-      ctx->i8_nks = (int)((M + 31) / 32);
-      const int NP = D * (D + 1) / 2, NPp = (NP + ctx->i8_bn - 1) / ctx->i8_bn * ctx->i8_bn;
+    // partial planes of the row splits, c tiles
+    RC(dalloc(ctx, &ch.qpart, (size_t)ctx->nsplit * n * DP));
+    RC(dalloc(ctx, &ch.gpart, (size_t)ctx->nsplit * n * DP));
+    RC(dalloc(ctx, &ch.ljl_part, n * ctx->nsplit));
+    if (ctx->opt.ccache) RC(dalloc(ctx, &g.ctile, (size_t)((n + 15) / 16) * (Mp / 16) * 64));
+    if (ctx->i8_requested) {
+      g.nCp = ctx->nCp;
+      const size_t S = ctx->i8S, NPp = ctx->NPp, nks = ctx->i8_nks, nkp = ctx->i8_nkp, NRp = ctx->i8_NRp, nCp = ctx->nCp;
       std::vector<short> pa(NPp, 0), pb(NPp, 0);
       for (int a = 0, q = 0; a < D; ++a)  // rows of the lower triangle
         for (int b = 0; b <= a; ++b, ++q) { pa[q] = (short)a; pb[q] = (short)b; }
       short *d_pa, *d_pb; double* d_scale;
-      RC(dalloc(ctx, &d_pa, (size_t)NPp)); RC(dalloc(ctx, &d_pb, (size_t)NPp)); RC(dalloc(ctx, &d_scale, (size_t)NPp));
-      RC(dalloc(ctx, &ctx->d_ze, (size_t)NPp));
+      RC(dalloc(ctx, &d_pa, NPp)); RC(dalloc(ctx, &d_pb, NPp)); RC(dalloc(ctx, &d_scale, NPp));
+      RC(dalloc(ctx, &ctx->d_ze, NPp));
       HIPCK(hipMemcpyAsync(d_pa, pa.data(), NPp * sizeof(short), hipMemcpyHostToDevice, ctx->stream));
       HIPCK(hipMemcpyAsync(d_pb, pb.data(), NPp * sizeof(short), hipMemcpyHostToDevice, ctx->stream));
       RC(sync(ctx));
       int* d_cexp;
-      RC(dalloc(ctx, &d_cexp, (size_t)ctx->DP));
-      RC(dalloc(ctx, &ctx->d_cmin, (size_t)ctx->DP)); RC(dalloc(ctx, &ctx->d_cmax, (size_t)ctx->DP));
-      ctx->pairs = I8Pairs{d_pa, d_pb, d_scale, NP, NPp, d_cexp};
-      RC(dalloc(ctx, &ctx->d_Zs, (size_t)S * ctx->i8_nks * NPp * 32));
-      ctx->i8_nkp = (NP + 31) / 32;
-      ctx->i8_NRp = (ctx->Mp + ctx->i8_bn - 1) / ctx->i8_bn * ctx->i8_bn;
-      RC(dalloc(ctx, &ctx->d_Zt, (size_t)S * ctx->i8_nkp * ctx->i8_NRp * 32));
-      RC(dalloc(ctx, &ctx->d_zre, (size_t)ctx->i8_NRp)); RC(dalloc(ctx, &ctx->d_zscale, (size_t)ctx->i8_NRp));
-      {  // slice planes and accumulators of the batch
-        g.nCp = (g.n + I8_BM - 1) / I8_BM * I8_BM;
-        RC(dalloc(ctx, &g.Vs, (size_t)S * ctx->i8_nks * g.nCp * 32));
-        RC(dalloc(ctx, &g.vbad, (size_t)g.nCp));
-        RC(dalloc(ctx, &g.vexp, (size_t)g.nCp));
-        RC(dalloc(ctx, &g.vexp_d, (size_t)g.nCp)); RC(dalloc(ctx, &g.rebase, (size_t)g.nCp)); RC(dalloc(ctx, &g.dmax, (size_t)1));
-        RC(dalloc(ctx, &g.dcount, (size_t)6));  // (before any graph is captured: every delta launch carries the pointer)
-        if (!ctx->big) { g.ch.i8_vbad = g.vbad; g.ch.i8_dmax = g.dmax; }
-        if (ctx->big && ctx->opt.i8_delta && S == 6) RC(dalloc(ctx, &g.Gbase, (size_t)g.n * ctx->DP * ctx->DP));
-        RC(dalloc(ctx, &g.Qs, (size_t)S * ctx->i8_nkp * g.nCp * 32));
-        RC(dalloc(ctx, &g.qscale, (size_t)g.nCp));
-        // small batches: cut the k range so that about 256 workgroups exist (at least 8 stages per piece, at most 16 pieces; only
-        // when the whole range fits one overflow-safe launch)
-        auto pieces = [&](long long tiles, int stages) {
-          long long k = std::min<long long>(16, 256 / std::max<long long>(1, tiles));
-          k = std::min<long long>(k, stages / 8);
-          if (k < 2 || stages > ctx->i8_chunk || ctx->big) return 1;  // (large-D: the identity padding of G lives in Gq itself)
-          const int per = (int)((stages + k - 1) / k);
-          return (stages + per - 1) / per;
-        };
-        g.ksplit_a = pieces((long long)(g.nCp / I8_BM) * (NPp / ctx->i8_bn), ctx->i8_nks);
-        g.ksplit_l = pieces((long long)(g.nCp / I8_BM) * (ctx->i8_NRp / ctx->i8_bn), ctx->i8_nkp);
-        if (g.ksplit_a > 1) RC(dalloc(ctx, &g.Gpart, (size_t)g.ksplit_a * g.n * ctx->DP * ctx->DP));
-        if (g.ksplit_a == 1 && ctx->i8_bn == 128 && NP % 128 != 0 && ctx->opt.i8_tail != 0) {
-          const int ntail = (NP % 128 + 31) / 32;
-          g.tail_pieces = (int)std::max<long long>(1, std::min<long long>(8, 256 / ((long long)(g.nCp / I8_BM) * ntail)));
-          RC(dalloc(ctx, &g.Tq, (size_t)g.tail_pieces * S * g.nCp * 32 * ntail));
-        }
-        if (g.ksplit_l > 1) RC(dalloc(ctx, &g.Rpart, (size_t)g.ksplit_l * g.n * ctx->Mp));
+      RC(dalloc(ctx, &d_cexp, DP));
+      RC(dalloc(ctx, &ctx->d_cmin, DP)); RC(dalloc(ctx, &ctx->d_cmax, DP));
+      ctx->pairs = I8Pairs{d_pa, d_pb, d_scale, ctx->NP, ctx->NPp, d_cexp};  // (kernel arguments)
+      RC(dalloc(ctx, &ctx->d_Zs, S * nks * NPp * 32));
+      RC(dalloc(ctx, &ctx->d_Zt, S * nkp * NRp * 32));
+      RC(dalloc(ctx, &ctx->d_zre, NRp)); RC(dalloc(ctx, &ctx->d_zscale, NRp));
+      // slice planes and accumulators of the batch
+      RC(dalloc(ctx, &g.Vs, S * nks * nCp * 32));
+      RC(dalloc(ctx, &g.vbad, nCp));
+      RC(dalloc(ctx, &g.vexp, nCp));
+      RC(dalloc(ctx, &g.vexp_d, nCp)); RC(dalloc(ctx, &g.rebase, nCp)); RC(dalloc(ctx, &g.dmax, (size_t)1));
+      RC(dalloc(ctx, &g.dcount, (size_t)6));  // (before any graph is captured: every delta launch carries the pointer)
+      if (!ctx->big) { ch.i8_vbad = g.vbad; ch.i8_dmax = g.dmax; }
+      if (ctx->gbase) RC(dalloc(ctx, &g.Gbase, n * DP * DP));
+      RC(dalloc(ctx, &g.Qs, S * nkp * nCp * 32));
+      RC(dalloc(ctx, &g.qscale, nCp));
+      if (ctx->tail_acc) RC(dalloc(ctx, &g.Tq, (size_t)ctx->tail_pieces * S * nCp * 32 * ctx->tail_blocks));
+      if (ctx->ksplit_l > 1) RC(dalloc(ctx, &g.Rpart, (size_t)ctx->ksplit_l * n * Mp));
+      // every instantiation the context can launch: its own slice count, at 6 slices also the 5 and 4 of the inner and delta assemblies
+      for (int sv = ctx->i8S == 6 ? 4 : ctx->i8S; sv <= ctx->i8S; ++sv)
+        I8_SWITCH_S(sv, {
+          // (the instantiation's own, fixed size: these kernels also hold a few KB of static LDS, and static + dynamic must stay within 160 KB)
+          constexpr int lds = i8_lds_bytes<S_, WN_, TN_>();
+          RC(raise_lds(ctx, k_assemble_i8<S_, WN_, TN_>, lds));
+          RC(raise_lds(ctx, k_leverage_i8<S_, WN_, TN_>, lds));
+          RC(raise_lds(ctx, k_assemble_i8_tail<S_>, (i8_lds_bytes<S_, 1, 1>())));
+        });
+      if (ctx->i8S == 6) {  // the one-launch delta assembly (launch_assemble_i8_delta): dynamic LDS of its widest instantiation
+        RC(raise_lds(ctx, k_assemble_i8_sel<4, 1>, std::max((i8_lds_bytes<6, 4, 1>()), (i8_lds_bytes<4, 4, 1>()))));
+        RC(raise_lds(ctx, k_assemble_i8_tail_sel, std::max((i8_lds_bytes<6, 1, 1>()), (i8_lds_bytes<4, 1, 1>()))));
       }
-      I8_SWITCH(ctx, {
-        constexpr int lds = i8_lds_bytes<S_, WN_, TN_>();
-        // (the instantiation's own, fixed size: these kernels also hold a few KB of static LDS, and static + dynamic must stay within 160 KB)
-        auto kfn = k_assemble_i8<S_, WN_, TN_>;
-        HIPCK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        auto kfn2 = k_leverage_i8<S_, WN_, TN_>;
-        HIPCK(hipFuncSetAttribute((const void*)kfn2, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        auto kfn3 = k_assemble_i8_tail<S_>;
-        HIPCK(hipFuncSetAttribute((const void*)kfn3, hipFuncAttributeMaxDynamicSharedMemorySize, (i8_lds_bytes<S_, 1, 1>())));
-      });
-      if (S == 6) {  // the one-launch delta assembly (launch_assemble_i8_delta): dynamic LDS of its widest instantiation
-        constexpr int ld = i8_lds_bytes<6, 4, 1>() > i8_lds_bytes<4, 4, 1>() ? i8_lds_bytes<6, 4, 1>() : i8_lds_bytes<4, 4, 1>();
-        constexpr int ldt = i8_lds_bytes<6, 1, 1>() > i8_lds_bytes<4, 1, 1>() ? i8_lds_bytes<6, 1, 1>() : i8_lds_bytes<4, 1, 1>();
-        HIPCK(hipFuncSetAttribute((const void*)k_assemble_i8_sel<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, ld));
-        HIPCK(hipFuncSetAttribute((const void*)k_assemble_i8_tail_sel, hipFuncAttributeMaxDynamicSharedMemorySize, ldt));
-      }
-      if (S == 6)  // the instantiations of the inner assemblies (launch_assemble)
-        for (int sv = S - 2; sv < S; ++sv)
-          I8_SWITCH_S(sv, {
-            auto kfn = k_assemble_i8<S_, WN_, TN_>;
-            HIPCK(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (i8_lds_bytes<S_, WN_, TN_>())));
-            auto kfn2 = k_leverage_i8<S_, WN_, TN_>;
-            HIPCK(hipFuncSetAttribute((const void*)kfn2, hipFuncAttributeMaxDynamicSharedMemorySize, (i8_lds_bytes<S_, WN_, TN_>())));
-            auto kfn3 = k_assemble_i8_tail<S_>;
-            HIPCK(hipFuncSetAttribute((const void*)kfn3, hipFuncAttributeMaxDynamicSharedMemorySize, (i8_lds_bytes<S_, 1, 1>())));
-          });
     }
-    {  // planes of the fp64 small-batch assembly (shared with the int8 k-split planes, whichever is larger)
-      const int need = std::max(g.fsplit, g.ksplit_a);
-      if (g.fsplit > 1 && (!g.Gpart || g.fsplit > g.ksplit_a)) RC(dalloc(ctx, &g.Gpart, (size_t)need * g.n * ctx->DP * ctx->DP));
-    }
+    if (ctx->gpart_planes) RC(dalloc(ctx, &g.Gpart, (size_t)ctx->gpart_planes * n * DP * DP));
     RC(dalloc(ctx, &ctx->d_z, n * (size_t)D)); RC(dalloc(ctx, &ctx->d_ulen, n)); RC(dalloc(ctx, &ctx->d_gdir, n)); RC(dalloc(ctx, &ctx->d_uacc, n));
-    if (ctx->big) {
-      RC(dalloc(ctx, &ctx->d_Wd, n * (size_t)ctx->nbk * 4096));
-      // (the fp64 leverage pass of the large-D path; with the int8 path it is allocated only if the certificate sends set_data back to fp64)
-      if (!(flags & RMHMC_FLAG_INT8_METRIC)) RC(dalloc(ctx, &ctx->d_hpart, (size_t)ctx->npairs * n * Mp));
-    }
+    if (ctx->big) RC(dalloc(ctx, &ctx->d_Wd, n * (size_t)ctx->nbk * 4096));
+    if (ctx->hpart_at_create) RC(dalloc(ctx, &ctx->d_hpart, (size_t)ctx->npairs * n * Mp));
     fill_int(ctx, ch.cstale, 1, n);  // (no c tiles yet; the first evaluation clears it)
     RC(dalloc(ctx, &ctx->d_nsteps, n)); RC(dalloc(ctx, &ctx->d_dir, n)); RC(dalloc(ctx, &ctx->d_done, 1)); RC(dalloc(ctx, &ctx->d_steps0, n));
     RC(dalloc(ctx, &ctx->d_miniter, 1));
     RC(dalloc(ctx, &ctx->d_orig, n)); RC(dalloc(ctx, &ctx->d_T, 2 * n));
-    {  // mid-size problems in small batches: one launch per leapfrog step (option medium = 0 disables it)
-      // measured per global step at one chain (tools/bench_single.py): australian (D = 15) 108 us vs 218 us generic, heart (D = 14)
-      // 85 vs 154, german (D = 25) 236 vs 386
-      const bool on = ctx->opt.medium && !ctx->big && D > FS_D && D <= 32 && ctx->Mp <= MS_MAXMP && n_chains <= 512;
-      if (on) {
-        const size_t lds = sizeof(double) * (ctx->NB == 1 ? ms_lds_doubles<1>(ctx->Mp) : ms_lds_doubles<2>(ctx->Mp));
-        if (ctx->NB == 1) {
-          HIPCK(hipFuncSetAttribute((const void*)k_step_medium<1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS));
-          HIPCK(hipFuncSetAttribute((const void*)k_step_medium<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS));
-          HIPCK(hipFuncSetAttribute((const void*)k_step_medium<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS));
-          HIPCK(hipFuncSetAttribute((const void*)k_step_medium<1, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS));
-          HIPCK(hipFuncSetAttribute((const void*)k_step_medium<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS));
-        } else {
-          HIPCK(hipFuncSetAttribute((const void*)k_step_medium<2, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS));
-          HIPCK(hipFuncSetAttribute((const void*)k_step_medium<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS));
-          HIPCK(hipFuncSetAttribute((const void*)k_step_medium<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS));
-        }
-        ctx->medium = true;
-        ctx->medium_lds = lds;
-      }
-    }
-    {  // plain HMC in small batches: one launch per trajectory (option medium = 0 disables it too)
-      // any batch for short data sets (rows in registers; australian, tools/bench_hmc_batch.py: 2048 chains 89 M leapfrog-steps/s vs 39 M
-      // generic, 512 chains 59 M vs 9 M; at 8192 chains the generic path has caught up since its row passes run in one round of
-      // workgroups - 107 M vs 114 M), small batches otherwise
-      long long maxn = ctx->Mp <= 1024 ? (1ll << 40) : 512;
-      if (ctx->opt.hmc_traj_maxn >= 0) maxn = ctx->opt.hmc_traj_maxn;
-      ctx->hmc_traj = ctx->opt.medium && !ctx->big && D <= 32 && n_chains <= maxn;
-    }
-    {  // small-problem path eligibility (option fused = 0 disables it)
-      const size_t lds = ((size_t)(FS_D + 1 + FS_WAVES) * ctx->Mp + (size_t)FS_WAVES * FS_PT) * sizeof(double);
-      if (ctx->opt.fused && D <= FS_D && lds <= 160 * 1024) {
-        HIPCK(hipFuncSetAttribute((const void*)k_fused_small, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS));
-        ctx->fused = true;
-        ctx->fused_lds = lds;
-      }
-    }
+    if (ctx->medium) RC(ctx->NB == 1 ? (raise_lds_medium<1, 0, 1, 2, 3, 4>(ctx)) : (raise_lds_medium<2, 0, 1, 2>(ctx)));
+    if (ctx->fused) RC(raise_lds(ctx, k_fused_small, MAX_LDS));
     RC(sync(ctx));
     return RMHMC_OK;
   };
@@ -1135,9 +972,12 @@ void rmhmc_destroy(rmhmc_ctx* ctx) {
 int rmhmc_set_option(rmhmc_ctx* ctx, const char* key, int64_t value) {
   if (!ctx) return fail(nullptr, RMHMC_ERR_INVALID, "set_option: null context");
   const OptionDesc* d = find_option(key);
-  if (!d) return fail(ctx, RMHMC_ERR_INVALID, std::string("set_option: unknown option '") + (key ? key : "(null)") + "'");
-  if (d->create_only) return fail(ctx, RMHMC_ERR_INVALID, std::string("set_option: '") + key + "' shapes the context and can only be given to rmhmc_create_opts");
-  if (value < d->lo || value > d->hi) return fail(ctx, RMHMC_ERR_INVALID, std::string("set_option: value out of range for '") + key + "'");
+  switch (check_option(d, value, false)) {
+    case OPT_UNKNOWN: return fail(ctx, RMHMC_ERR_INVALID, std::string("set_option: unknown option '") + (key ? key : "(null)") + "'");
+    case OPT_CREATE_ONLY: return fail(ctx, RMHMC_ERR_INVALID, std::string("set_option: '") + key + "' shapes the context and can only be given to rmhmc_create_opts");
+    case OPT_RANGE: return fail(ctx, RMHMC_ERR_INVALID, std::string("set_option: value out of range for '") + key + "'");
+    case OPT_OK: break;
+  }
   HIPCK(hipSetDevice(ctx->device));
   HIPCK(hipStreamSynchronize(ctx->stream));
   ctx->opt.*(d->slot) = value;
@@ -1549,8 +1389,8 @@ static void launch_global_step_prefix(rmhmc_ctx* ctx, const IterBase& ib, int na
   Group g = ctx->batch;
   g.n = na; g.ch.n = na;
   if (g.nCp) g.nCp = (na + I8_BM - 1) / I8_BM * I8_BM;
-  // (row ranges, k-split planes and row splits stay as chosen for the whole batch: every chain's sums keep their order, so the
-  // results are bit-identical to the unsorted run)
+  // (only the chain count and its int8 padding narrow.  Row ranges, k-split planes and row splits are the plan's, chosen for the
+  // whole batch: every chain's sums keep their order, so the results are bit-identical to the unsorted run)
   launch_global_step(ctx, g, ib);
 }
 
@@ -1774,7 +1614,7 @@ static int hmc_init_chains(rmhmc_ctx* ctx, const double* theta0_host /* [n][D] o
     launch_hmc_traj(ctx, g, 1);
   } else {
     launch_rowpass<RP_G>(ctx, g, g.ch.trj.w, nullptr);
-    SMALL(ctx, g, "small", k_hmc_init, ctx->dd, g.ch, g.nsplit);
+    SMALL(ctx, g, "small", k_hmc_init, ctx->dd, g.ch, ctx->nsplit);
   }
   fill_int(ctx, ctx->batch.ch.phase, 0, ctx->n);
   fill_int(ctx, ctx->batch.ch.steps_left, 0, ctx->n);
@@ -2045,15 +1885,6 @@ int rmhmc_kernel_time(rmhmc_ctx* ctx, const char* which, double* seconds_out, in
 // ---- adaptive Metropolis (metropolis.py, amh.hip.h) --------------------------------------------------------------------------------
 namespace {
 
-// Block size and rows per thread of k_amh: one wavefront per chain when the batch fills the chip and f fits in 16 registers per lane,
-// a 256-thread workgroup otherwise (short latency per proposal for few chains, room for long data sets); R = 0: f is streamed.
-void amh_shape(const rmhmc_ctx* ctx, int* nt, int* rows) {
-  const long long M = ctx->M;
-  const int NT = (M <= 64 * 16 && ctx->n >= 1024) ? 64 : 256;
-  *nt = NT;
-  *rows = M > AMH_MAX_ONCHIP_ROWS ? 0 : (int)((M + NT - 1) / NT);
-}
-
 // Runs iterations 0..n_iter-1 of every chain in segments (metropolis.py:38-91), p carries the mode.  Progress reports and the timer
 // sit between segments.  A segment ends after at most 1000 iterations, after every reported iteration and after iteration burn_in,
 // the same cuts for any number of chains; its launches are cut by work (AMH_LAUNCH_ROWS), which leaves the results unchanged.
@@ -2067,8 +1898,8 @@ int amh_run(rmhmc_ctx* ctx, AmhParams p, const double* theta0, double* seconds_o
   HIPCK(hipMemsetAsync(ch.u0, 0, sizeof(double) * n * DP, ctx->stream));
   fill_ll(ctx, ch.accepted, 0, n);
   p.w = ch.cur.w; p.sd = ch.PM; p.accw = ch.u0; p.ljl = ch.cur.ljl; p.accepted = ch.accepted; p.fa = ch.rv0; p.fb = ch.rv2;
-  int NT = 256, R = 0;
-  amh_shape(ctx, &NT, &R);
+  const AmhShape shape = amh_shape(ctx->M, ctx->n);  // (plan.h)
+  const int NT = shape.nt, R = shape.rows;
   const bool sampling = p.z_in == nullptr;
   const long long N = p.n_iter, B = p.burn_in;
   auto t0 = std::chrono::steady_clock::now();

@@ -12,6 +12,7 @@ import numpy as np
 
 from riemannhamiltonianmontecarlo_amd import _capi
 from riemannhamiltonianmontecarlo_amd.data import synthetic_logreg
+from plan_probe import plan
 
 I8 = _capi.int8_metric_flags
 
@@ -38,13 +39,6 @@ CERT_PATHS = {
 ESS_S = 200
 
 
-def expected_fsplit(M, n):
-    """row ranges of the fp64 assembly for a batch of n < 1024 chains, the rule of rmhmc_create_opts (D <= 64, option fsplit = 0)"""
-    Mp = (M + 63) // 64 * 64
-    fs = 1 if n >= 1024 else min(16, (2048 + n - 1) // n)
-    return min(fs, max(1, Mp // 256))
-
-
 def assert_path(ctx, path, certify_active=True, paths=None):
     """the stepping path the shape was chosen for is the one the context reports (paths: the table the shape is from, PATHS by default;
     certify_active = False: an int8 context whose data the certificate has sent to the fp64 kernels)"""
@@ -61,10 +55,10 @@ def assert_path(ctx, path, certify_active=True, paths=None):
         assert ctx.int8_certificate()[1] == bool(certify_active)
     else:
         assert "int8" not in info, (path, info)
-    if path == "generic":
-        assert expected_fsplit(M, n) == 1
+    if path == "generic":                      # (row ranges of the fp64 assembly: the rule itself, csrc/plan.h)
+        assert plan(M, D, n, flags)["fsplit"] == 1
     if path == "generic_rowsplit":
-        assert expected_fsplit(M, n) > 1
+        assert plan(M, D, n, flags)["fsplit"] > 1
 
 
 def data_of(spec, variant="own"):

@@ -298,7 +298,8 @@ def iwls_sat_case():
 
 
 # ---- AMH: wide D and the register-tile edges of M -------------------------------------------------------------------------------------------
-# id: (chains, M, D, T, B, seed, (NT, R) the host's amh_shape chooses); KW = (256 + NT - 1) / NT coordinates per thread
+# id: (chains, M, D, T, B, seed, (NT, R) of the instantiation of k_amh that amh_shape (csrc/plan.h) and AMH_SWITCH select);
+# KW = (256 + NT - 1) / NT coordinates per thread
 AMH_EDGE_CASES = {
     "nt64_d256": (1024, 300, 256, 6, 3, 61, (64, 8)),          # KW 4, every lane owns four coordinates
     "nt64_d129_odd": (1024, 250, 129, 6, 3, 62, (64, 4)),      # lane 0 owns three coordinates, the others two; half a Box-Muller pair
@@ -309,17 +310,6 @@ AMH_EDGE_CASES = {
     "m12288": (3, 12288, 3, 10, 5, 67, (256, 48)),             # AMH_MAX_ONCHIP_ROWS: R = 48 full
     "m12289": (3, 12289, 3, 10, 5, 68, (256, 0)),              # the first streamed size
 }
-
-
-def amh_shape(n, M):
-    """(NT, R as instantiated) of k_amh for n chains and M rows.  A COPY of the host's rule, to be kept in step with amh_shape in
-    csrc/rmhmc_hip.hip and AMH_SWITCH / AMH_MAX_ONCHIP_ROWS in csrc/amh.hip.h: the library does not report the variant it launches, so
-    tests/test_sampler_edges_cpu.py holds this copy against the text of those two sources and fails when their thresholds move."""
-    NT = 64 if (M <= 64 * 16 and n >= 1024) else 256
-    if M > 256 * 48:
-        return NT, 0
-    R = (M + NT - 1) // NT
-    return NT, min(r for r in ((4, 8, 16) if NT == 64 else (2, 4, 8, 16, 32, 48)) if R <= r)
 
 
 def amh_follow(n):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import plan_probe  # noqa: E402
 import sampler_edges as E  # noqa: E402
 
 
@@ -159,30 +160,38 @@ def test_iwls_chain_32_saturates_on_australian():
 
 # ---- AMH --------------------------------------------------------------------------------------------------------------------------------
 def test_amh_edge_cases_select_the_variants_they_are_named_for():
-    """amh_shape / AMH_SWITCH of the host, restated: NT, R as the table says; D > 128 at NT 64, D > 64 at NT 256, D = 256, an odd D above
-    64, and the four edges of M"""
-    # E.amh_shape is a copy of the host's rule: held against the text of the rule itself, so that it cannot go stale unnoticed
+    """amh_shape of the host (csrc/plan.h, asked through the probe) and AMH_SWITCH of the device header: NT, R as the table says; D > 128
+    at NT 64, D > 64 at NT 256, D = 256, an odd D above 64, and the four edges of M"""
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "riemannhamiltonianmontecarlo_amd", "csrc")
-    host, dev = open(os.path.join(csrc, "rmhmc_hip.hip")).read(), open(os.path.join(csrc, "amh.hip.h")).read()
-    assert "const int NT = (M <= 64 * 16 && ctx->n >= 1024) ? 64 : 256;" in host
-    assert "*rows = M > AMH_MAX_ONCHIP_ROWS ? 0 : (int)((M + NT - 1) / NT);" in host
-    assert "#define AMH_MAX_ONCHIP_ROWS (256 * 48)" in dev
-    switch = dev[dev.index("#define AMH_SWITCH("):dev.index("#define AMH_MAX_ONCHIP_ROWS")]
-    assert re.findall(r"NT_ = (\d+), R_ = (\d+)", switch) == [(str(nt), str(r)) for nt, r in
-                                                               [(64, 4), (64, 8), (64, 16), (256, 0), (256, 2), (256, 4), (256, 8), (256, 16),
-                                                                (256, 32), (256, 48)]]
+    plan_h, dev = open(os.path.join(csrc, "plan.h")).read(), open(os.path.join(csrc, "amh.hip.h")).read()
+    assert "#define AMH_MAX_ONCHIP_ROWS (256 * 48)" in plan_h
+    switch = dev[dev.index("#define AMH_SWITCH("):]
+    switch = switch[:switch.index("while (0)")]
+    variants = [(int(nt), int(r)) for nt, r in re.findall(r"NT_ = (\d+), R_ = (\d+)", switch)]
+    assert variants == [(64, 4), (64, 8), (64, 16), (256, 0), (256, 2), (256, 4), (256, 8), (256, 16), (256, 32), (256, 48)]
     assert re.findall(r"\(R\) (<=|==) (\d+)", switch) == [("<=", "4"), ("<=", "8"), ("==", "0"), ("<=", "2"), ("<=", "4"), ("<=", "8"),
                                                           ("<=", "16"), ("<=", "32")]
+
+    def instantiated(shape):
+        """(NT, R) of the variant AMH_SWITCH runs for the host's (NT, rows per thread): the smallest R_ that holds the rows"""
+        nt, rows = shape["nt"], shape["rows"]
+        return nt, (0 if rows == 0 else min(r for v, r in variants if v == nt and rows <= r))
+
     cases = E.AMH_EDGE_CASES
-    for name, (n, M, D, T, B, seed, shape) in cases.items():
-        assert E.amh_shape(n, M) == shape, name
+    edges = [(1024, 1024), (1024, 1025), (3, 12288), (3, 12289)]
+    res = plan_probe.probe_many([plan_probe.probe_line(M, D, n) for n, M, D, *_ in cases.values()]
+                                + [plan_probe.probe_line(M, 4, n) for n, M in edges])
+    shapes = [instantiated(r["amh"]) for r in res]
+    for (name, (n, M, D, T, B, seed, shape)), got in zip(cases.items(), shapes):
+        assert got == shape, name
         assert 0 < B < T <= 10 and D <= 256
     assert any(s[6][0] == 64 and s[2] == 256 for s in cases.values())
     assert any(s[6][0] == 64 and s[2] > 128 and s[2] % 2 == 1 for s in cases.values())
     assert sum(s[6][0] == 256 and s[2] > 64 for s in cases.values()) >= 2
     assert {1024, 1025, 12288, 12289} <= {s[1] for s in cases.values()}
-    assert E.amh_shape(1024, 1024) == (64, 16) and E.amh_shape(1024, 1025)[0] == 256
-    assert E.amh_shape(3, 12288) == (256, 48) and E.amh_shape(3, 12289) == (256, 0)
+    e = shapes[len(cases):]
+    assert e[0] == (64, 16) and e[1][0] == 256
+    assert e[2] == (256, 48) and e[3] == (256, 0)
 
 
 @pytest.mark.parametrize("name", list(E.AMH_EDGE_CASES))
