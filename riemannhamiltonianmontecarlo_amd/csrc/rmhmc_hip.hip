@@ -60,6 +60,24 @@ struct Group {
   d4* ctile = nullptr;   // c = v(1-2p) of trj.w in the tile layout of k_mompass, [ceil(n/16)][Mp/16][64] x 4 doubles
 };
 
+// What one call asks of the stepping code.  The entry point builds it from its own arguments and hands it down by const&; nothing
+// below writes it, and the context keeps none of it (rmhmc_ctx::chains is the one exception).  A parameter the call's sampler
+// never reads is 0 (K of plain HMC, L of rmhmc_leapfrog, seed and chain_offset where the randomness is the caller's).
+enum Sampler { RMHMC, HMC };  // rmhmc.py / hmc.py: selects the global step
+struct Run {
+  Sampler sampler;
+  int L, K;
+  double eps;
+  uint64_t seed; int64_t chain_offset;  // Philox key of chain c: (seed, chain_offset + c)
+  const int* orig;  // work-sorted layout (sample_core): [n] position -> chain index in the caller's order, or nullptr: position = chain
+};
+struct IterBase {  // ... and of the transition bookkeeping of the steps it issues
+  long long limit, burn_in, S;
+  double* samples;
+  bool explicit_rng;
+  bool count_done;
+};
+
 }  // namespace
 
 // The context IS its plan (plan.h: M, D, n, the padded sizes, the splits, the int8 layout, the stepping path - fixed at create),
@@ -77,9 +95,8 @@ struct rmhmc_ctx : Plan {
   Group batch;  // all n chains; batch.ch holds the per-chain arrays
   std::vector<void*> allocs;
   bool have_data = false, chains_ready = false;
-  int sampler = 0;           // 0: RMHMC (rmhmc.py), 1: plain HMC (hmc.py) -- selects the global step
+  Run chains{};  // stateful API only: written by rmhmc_chains_init, read by rmhmc_chains_run while chains_ready holds
   double *d_Wd = nullptr, *d_hpart = nullptr, *d_Gcopy = nullptr;
-  bool want_G = false;
   // (options crestore / cdyn / ccache: c = v(1-2p) kept per position in the momentum pass's tile layout; the first pass of a step re-uses
   //  the tiles of chains that did not just reject; those of the chains that did are recomputed by k_crestore, 16 to a wavefront)
   // int8 metric path (metric_i8.hip.h)
@@ -96,25 +113,18 @@ struct rmhmc_ctx : Plan {
   double* d_zscale = nullptr;
   I8Pairs pairs{};
   double i8_bound = 0.0;       // certificate of the last set_data (metric_i8.hip.h: "Error bound"), 0 when the path is not requested
-  // sampler parameters of the stateful API
-  int L = 6, K = 4;
-  double eps = 0.5;
-  uint64_t seed = 0;
-  int64_t chain_offset = 0;
   // unit-API staging (device)
   double *d_z = nullptr, *d_ulen = nullptr, *d_gdir = nullptr, *d_uacc = nullptr;
   int *d_nsteps = nullptr, *d_dir = nullptr, *d_done = nullptr;
   long long* d_steps0 = nullptr;
   unsigned long long* d_miniter = nullptr;
   // work-sorted layout of the bulk sampler (sample_core)
-  int* d_orig = nullptr;            // [n] position -> chain index in the caller's order
-  long long* d_T = nullptr;         // [2n] scratch: trajectory-length sums / un-permuted counters
-  bool sorted = false;              // in use by the running sampler (iter_params)
-  bool counters_sorted = false;     // the last sampler run left its counters un-permuted in d_T
+  int* d_orig = nullptr;            // [n] position -> chain index in the caller's order (Run::orig of a sorted run)
+  long long* d_T = nullptr;         // [2n] scratch: trajectory-length sums / counters back in the caller's order
   // progress reports of the bulk samplers (rmhmc_set_progress)
   rmhmc_progress_fn progress_fn = nullptr;
   void* progress_user = nullptr;
-  long long progress_first = 0, progress_every = 0, progress_next = 0;
+  long long progress_first = 0, progress_every = 0;
   // timing
   bool timing = false;
   std::map<std::string, std::vector<EvPair>> events;
@@ -214,13 +224,13 @@ void flow_tick(rmhmc_ctx* ctx, long long steps = 1) {
 // Delta assembly of the evaluation that ends a leapfrog step (I8Delta in metric_i8.hip.h): the last position iterate has left its N in
 // the slice planes and its G - summed from all six slices - in Gq, and v moves by 1e-6 between the two points, so the difference
 // needs four slices (10 slice products) where the full assembly needs six (21).
-static bool use_delta(const rmhmc_ctx* ctx, const Group& g) {
-  return ctx->i8 && ctx->opt.i8_delta && (!ctx->big || g.Gbase) && ctx->i8S == 6 && g.ctile && ctx->ksplit_a <= 1 && ctx->K >= 2 && g.dmax;
+static bool use_delta(const rmhmc_ctx* ctx, const Run& run, const Group& g) {
+  return ctx->i8 && ctx->opt.i8_delta && (!ctx->big || g.Gbase) && ctx->i8S == 6 && g.ctile && ctx->ksplit_a <= 1 && run.K >= 2 && g.dmax;
 }
 // The second position iterate as a delta of the first (both inner iterates on five slices: it = 2 < K - 1; later inner iterates would need
 // the N of a predecessor whose planes hold differences)
-static bool use_delta_inner(const rmhmc_ctx* ctx, const Group& g, int it) {
-  return use_delta(ctx, g) && ctx->opt.i8_delta_inner && ctx->i8_inner_drop && it == 2 && it < ctx->K - 1;
+static bool use_delta_inner(const rmhmc_ctx* ctx, const Run& run, const Group& g, int it) {
+  return use_delta(ctx, run, g) && ctx->opt.i8_delta_inner && ctx->i8_inner_drop && it == 2 && it < run.K - 1;
 }
 template <int MODE>
 void launch_rowpass(rmhmc_ctx* ctx, Group& g, const double* w, double* out0, double* out2 = nullptr, bool delta = false) {
@@ -516,20 +526,21 @@ void launch_leverage(rmhmc_ctx* ctx, Group& g, int part = 0) {
 #define BIG(ctx, g, name, kern, ...)                                                                       \
   launch(ctx, name, [&](hipStream_t st_) { hipLaunchKernelGGL(kern, dim3((unsigned)(g).n), dim3(256), 0, st_, __VA_ARGS__); })
 
-// Evaluate the point record at trj.w for every chain in phase 1 (rmhmc.py:134-161; with advance the
-// explicit momentum half step :163 too): v, r, c, log-joint partials -> G and gradient on the matrix cores
-// -> factor / inverse / u = G^-1 p -> quadratic term -> leverage pass (trace term) -> momentum update.
+// Evaluate the point record at trj.w for every chain in phase 1 (rmhmc.py:134-161): v, r, c, log-joint partials -> G and gradient
+// on the matrix cores -> factor / inverse / u = G^-1 p -> quadratic term -> leverage pass (trace term) -> momentum update.
+// step: the run whose leapfrog step this evaluation ends (the explicit momentum half step :163 follows; the last position iterate's
+// slices and G are at hand), or nullptr: evaluate only, which needs no run parameters.  want_G (large-D): copy G to d_Gcopy.
 // mode 0: everything; 1: metric, factor, inverse, gradient, log joint only (simplified mMALA); 2: mode 1 + the trace term (full mMALA)
-void eval_point_phases(rmhmc_ctx* ctx, Group& g, bool advance, int mode = 0) {
-  // (advance: the evaluation that ends a leapfrog step - the last position iterate's slices and G are at hand)
-  const bool delta = advance && use_delta(ctx, g);
+void eval_point_phases(rmhmc_ctx* ctx, Group& g, const Run* step, int mode = 0, bool want_G = false) {
+  const double eps = step ? step->eps : 0.0;  // (read by the kernels below only when they advance, see the two calls)
+  const bool delta = step && use_delta(ctx, *step, g);
   launch_rowpass<RP_F>(ctx, g, g.ch.trj.w, g.ch.rv0, g.ch.rv2, delta);
   if (ctx->big) SMALL(ctx, g, "small", k_finish_big, ctx->dd, g.ch, ctx->nsplit);
   launch_assemble(ctx, g, g.ch.rv0, false, delta);
   if (ctx->big) {
-    if (ctx->want_G)
+    if (want_G)
       (void)hipMemcpyAsync(ctx->d_Gcopy, g.ch.Gq, sizeof(double) * (size_t)g.n * ctx->DP * ctx->DP, hipMemcpyDeviceToDevice, ctx->stream);
-    BIG(ctx, g, "factor", k_chol_big<1>, ctx->dd, g.ch, ctx->nbk, ctx->d_Wd, ctx->eps);
+    BIG(ctx, g, "factor", k_chol_big<1>, ctx->dd, g.ch, ctx->nbk, ctx->d_Wd, eps);  // (MODE 1 does not read eps: only MODE 0 solves for wq)
     BIG(ctx, g, "factor", k_inverse_big, ctx->dd, g.ch, ctx->nbk, ctx->d_Wd);
     SMALL(ctx, g, "small", k_ginv_matvec, ctx->D, ctx->DP, g.ch, g.ch.p);
   } else {
@@ -552,36 +563,40 @@ void eval_point_phases(rmhmc_ctx* ctx, Group& g, bool advance, int mode = 0) {
     launch_mompass(ctx, g, g.ch.trj.w, 2);  // (the row pass above has just stored c for trj.w)
     launch_leverage(ctx, g);
   }
-  SMALL(ctx, g, "small", k_mom_final, ctx->D, ctx->DP, g.ch, ctx->eps, advance ? 1 : 0, ctx->nsplit, fused_trace(ctx, g) ? g.ch.gpart : (const double*)nullptr);
+  // (without advance k_mom_final leaves p alone: the half step h = tau eps / 2 is formed and not used)
+  SMALL(ctx, g, "small", k_mom_final, ctx->D, ctx->DP, g.ch, eps, step ? 1 : 0, ctx->nsplit, fused_trace(ctx, g) ? g.ch.gpart : (const double*)nullptr);
 }
 
 // one-launch step / evaluation / folded global step for small batches (medium_step.hip.h).  Data rows per thread stay in registers
 // when at most 64 doubles are needed for them.
+// step: the run that advances, or nullptr: eval_only (the kernel reads K, eps and h = tau eps / 2 in its `!eval_only` parts alone)
 template <int NB>
-void launch_step_medium_nb(rmhmc_ctx* ctx, Group& g, hipStream_t st, int guards, int eval_only, int fold, const IterParams& ip) {
+void launch_step_medium_nb(rmhmc_ctx* ctx, Group& g, hipStream_t st, int guards, const Run* step, int fold, const IterParams& ip) {
+  const double eps = step ? step->eps : 0.0;
+  const int K = step ? step->K : 0, eval_only = step ? 0 : 1;
   const int rpt = (ctx->Mp + 255) / 256;
   const dim3 grid((unsigned)g.n), block(256);
   const size_t lds = ctx->medium_lds;
   switch (rpt * 16 * NB <= 64 ? rpt : 0) {
-    case 1: hipLaunchKernelGGL((k_step_medium<NB, 1>), grid, block, lds, st, ctx->dd, g.ch, ctx->eps, ctx->K, guards, eval_only, fold, ip); break;
-    case 2: hipLaunchKernelGGL((k_step_medium<NB, 2>), grid, block, lds, st, ctx->dd, g.ch, ctx->eps, ctx->K, guards, eval_only, fold, ip); break;
-    case 3: hipLaunchKernelGGL((k_step_medium<NB, (NB == 1 ? 3 : 0)>), grid, block, lds, st, ctx->dd, g.ch, ctx->eps, ctx->K, guards, eval_only, fold, ip); break;
-    case 4: hipLaunchKernelGGL((k_step_medium<NB, (NB == 1 ? 4 : 0)>), grid, block, lds, st, ctx->dd, g.ch, ctx->eps, ctx->K, guards, eval_only, fold, ip); break;
-    default: hipLaunchKernelGGL((k_step_medium<NB, 0>), grid, block, lds, st, ctx->dd, g.ch, ctx->eps, ctx->K, guards, eval_only, fold, ip); break;
+    case 1: hipLaunchKernelGGL((k_step_medium<NB, 1>), grid, block, lds, st, ctx->dd, g.ch, eps, K, guards, eval_only, fold, ip); break;
+    case 2: hipLaunchKernelGGL((k_step_medium<NB, 2>), grid, block, lds, st, ctx->dd, g.ch, eps, K, guards, eval_only, fold, ip); break;
+    case 3: hipLaunchKernelGGL((k_step_medium<NB, (NB == 1 ? 3 : 0)>), grid, block, lds, st, ctx->dd, g.ch, eps, K, guards, eval_only, fold, ip); break;
+    case 4: hipLaunchKernelGGL((k_step_medium<NB, (NB == 1 ? 4 : 0)>), grid, block, lds, st, ctx->dd, g.ch, eps, K, guards, eval_only, fold, ip); break;
+    default: hipLaunchKernelGGL((k_step_medium<NB, 0>), grid, block, lds, st, ctx->dd, g.ch, eps, K, guards, eval_only, fold, ip); break;
   }
 }
-void launch_step_medium(rmhmc_ctx* ctx, Group& g, hipStream_t st, int guards, int eval_only, int fold, const IterParams& ip) {
-  if (ctx->NB == 1) launch_step_medium_nb<1>(ctx, g, st, guards, eval_only, fold, ip);
-  else launch_step_medium_nb<2>(ctx, g, st, guards, eval_only, fold, ip);
+void launch_step_medium(rmhmc_ctx* ctx, Group& g, hipStream_t st, int guards, const Run* step, int fold, const IterParams& ip) {
+  if (ctx->NB == 1) launch_step_medium_nb<1>(ctx, g, st, guards, step, fold, ip);
+  else launch_step_medium_nb<2>(ctx, g, st, guards, step, fold, ip);
 }
 
 // One generalised leapfrog step for every chain in phase 1 (rmhmc.py:96-163).
-void step_phases(rmhmc_ctx* ctx, Group& g) {
-  const int D = ctx->D, DP = ctx->DP, K = ctx->K;
-  const double eps = ctx->eps;
+void step_phases(rmhmc_ctx* ctx, const Run& run, Group& g) {
+  const int D = ctx->D, DP = ctx->DP, K = run.K;
+  const double eps = run.eps;
   const int guards = (ctx->flags & RMHMC_FLAG_GUARDS) ? 1 : 0;
   if (ctx->medium) {  // the whole step in one launch, one workgroup per chain
-    launch(ctx, "medium", [&](hipStream_t st) { launch_step_medium(ctx, g, st, guards, 0, 0, IterParams{}); });
+    launch(ctx, "medium", [&](hipStream_t st) { launch_step_medium(ctx, g, st, guards, &run, 0, IterParams{}); });
     return;
   }
   // c tiles of the chains whose last proposal was rejected (their trj has fallen back to cur): recomputed for them alone, so that the
@@ -617,9 +632,9 @@ void step_phases(rmhmc_ctx* ctx, Group& g) {
     SMALL(ctx, g, "factor", k_pos_first, D, DP, g.ch, eps, ctx->nsplit);
   }
   for (int it = 1; it < K; ++it) {
-    launch_rowpass<RP_V>(ctx, g, g.ch.wq, g.ch.rv0, nullptr, use_delta_inner(ctx, g, it));
-    const bool base = (it == 1 && use_delta_inner(ctx, g, 2)) || (it == K - 1 && use_delta(ctx, g));
-    launch_assemble(ctx, g, g.ch.rv0, it < K - 1, use_delta_inner(ctx, g, it), base);
+    launch_rowpass<RP_V>(ctx, g, g.ch.wq, g.ch.rv0, nullptr, use_delta_inner(ctx, run, g, it));
+    const bool base = (it == 1 && use_delta_inner(ctx, run, g, 2)) || (it == K - 1 && use_delta(ctx, run, g));
+    launch_assemble(ctx, g, g.ch.rv0, it < K - 1, use_delta_inner(ctx, run, g, it), base);
     if (ctx->big)
       BIG(ctx, g, "factor", k_chol_big<0>, ctx->dd, g.ch, ctx->nbk, ctx->d_Wd, eps);
     else
@@ -629,70 +644,64 @@ void step_phases(rmhmc_ctx* ctx, Group& g) {
   }
   if (ctx->big || K < 2) SMALL(ctx, g, "small", k_pos_final, D, DP, g.ch, guards);
   // explicit momentum half step at the new point (rmhmc.py:134-163)
-  eval_point_phases(ctx, g, true);
+  eval_point_phases(ctx, g, &run);
 }
 
-struct IterBase {
-  long long limit, burn_in, S;
-  double* samples;
-  bool explicit_rng;
-  bool count_done;
-};
-
-IterParams iter_params(rmhmc_ctx* ctx, const IterBase& b) {
+IterParams iter_params(rmhmc_ctx* ctx, const Run& run, const IterBase& b) {
   IterParams ip{};
   ip.flags = ctx->flags;
-  ip.L = ctx->L;
-  ip.seed = ctx->seed;
-  ip.chain_offset = ctx->chain_offset;
+  ip.L = run.L;
+  ip.seed = run.seed;
+  ip.chain_offset = run.chain_offset;
   ip.iter_limit = b.limit;
   ip.burn_in = b.burn_in;
   ip.S = b.S;
   ip.samples = b.samples;
-  if (ctx->sorted) ip.orig = ctx->d_orig;  // chain ids and sample blocks through the position -> chain map
+  ip.orig = run.orig;  // chain ids and sample blocks through the position -> chain map
   if (b.explicit_rng) {
     ip.z_in = ctx->d_z; ip.ulen_in = ctx->d_ulen; ip.gdir_in = ctx->d_gdir; ip.uacc_in = ctx->d_uacc;
   }
   ip.done_count = b.count_done ? ctx->d_done : nullptr;
-  ip.lower_L = (!ctx->big && !ctx->medium && !ctx->fused && ctx->sampler == 0) ? 1 : 0;  // (k_factor_full is the only writer of trj.L there)
+  ip.lower_L = (!ctx->big && !ctx->medium && !ctx->fused && run.sampler == RMHMC) ? 1 : 0;  // (k_factor_full is the only writer of trj.L there)
   return ip;
 }
 
-void launch_iter_begin(rmhmc_ctx* ctx, Group& g, const IterBase& b) {
-  const IterParams ip = iter_params(ctx, b);
-  SMALL(ctx, g, "small", k_iter_begin, ctx->D, ctx->DP, g.ch, ip);
+void launch_iter_begin(rmhmc_ctx* ctx, const Run& run, Group& g, const IterBase& b) {
+  SMALL(ctx, g, "small", k_iter_begin, ctx->D, ctx->DP, g.ch, iter_params(ctx, run, b));
 }
-void launch_iter_end(rmhmc_ctx* ctx, Group& g, const IterBase& b) {
-  const IterParams ip = iter_params(ctx, b);
-  SMALL(ctx, g, "small", k_iter_end, ctx->D, ctx->DP, g.ch, ip);
+void launch_iter_end(rmhmc_ctx* ctx, const Run& run, Group& g, const IterBase& b) {
+  SMALL(ctx, g, "small", k_iter_end, ctx->D, ctx->DP, g.ch, iter_params(ctx, run, b));
 }
 
 // plain HMC (hmc.py:38-84): begin / half step + position / gradient pass / half step / end
+// step: the run whose trajectories these are, or nullptr: eval_only (the kernel reads eps in its `!eval_only` half steps alone)
 template <int NB>
-void launch_hmc_traj_nb(rmhmc_ctx* ctx, Group& g, int eval_only, hipStream_t st) {
+void launch_hmc_traj_nb(rmhmc_ctx* ctx, Group& g, const Run* step, hipStream_t st) {
+  const double eps = step ? step->eps : 0.0;
+  const int eval_only = step ? 0 : 1;
   const int rpt = (ctx->Mp + 255) / 256;  // data rows per thread; up to 4 of them stay in registers for the whole trajectory
   const dim3 grid((unsigned)g.n), block(256);
   switch (rpt <= 4 ? rpt : 0) {
-    case 1: hipLaunchKernelGGL((k_hmc_traj<NB, 1>), grid, block, 0, st, ctx->dd, g.ch, ctx->eps, eval_only); break;
-    case 2: hipLaunchKernelGGL((k_hmc_traj<NB, 2>), grid, block, 0, st, ctx->dd, g.ch, ctx->eps, eval_only); break;
-    case 3: hipLaunchKernelGGL((k_hmc_traj<NB, 3>), grid, block, 0, st, ctx->dd, g.ch, ctx->eps, eval_only); break;
-    case 4: hipLaunchKernelGGL((k_hmc_traj<NB, 4>), grid, block, 0, st, ctx->dd, g.ch, ctx->eps, eval_only); break;
-    default: hipLaunchKernelGGL((k_hmc_traj<NB, 0>), grid, block, 0, st, ctx->dd, g.ch, ctx->eps, eval_only); break;
+    case 1: hipLaunchKernelGGL((k_hmc_traj<NB, 1>), grid, block, 0, st, ctx->dd, g.ch, eps, eval_only); break;
+    case 2: hipLaunchKernelGGL((k_hmc_traj<NB, 2>), grid, block, 0, st, ctx->dd, g.ch, eps, eval_only); break;
+    case 3: hipLaunchKernelGGL((k_hmc_traj<NB, 3>), grid, block, 0, st, ctx->dd, g.ch, eps, eval_only); break;
+    case 4: hipLaunchKernelGGL((k_hmc_traj<NB, 4>), grid, block, 0, st, ctx->dd, g.ch, eps, eval_only); break;
+    default: hipLaunchKernelGGL((k_hmc_traj<NB, 0>), grid, block, 0, st, ctx->dd, g.ch, eps, eval_only); break;
   }
 }
-void launch_hmc_traj(rmhmc_ctx* ctx, Group& g, int eval_only) {
+void launch_hmc_traj(rmhmc_ctx* ctx, Group& g, const Run* step) {
   launch(ctx, "medium", [&](hipStream_t st) {
-    if (ctx->NB == 1) launch_hmc_traj_nb<1>(ctx, g, eval_only, st);
-    else launch_hmc_traj_nb<2>(ctx, g, eval_only, st);
+    if (ctx->NB == 1) launch_hmc_traj_nb<1>(ctx, g, step, st);
+    else launch_hmc_traj_nb<2>(ctx, g, step, st);
   });
 }
 
-void launch_hmc_global_step(rmhmc_ctx* ctx, Group& g, const IterBase& b) {
-  const double eps = ctx->eps;
-  const IterParams ip = iter_params(ctx, b);
+void launch_hmc_global_step(rmhmc_ctx* ctx, const Run& run, Group& g, const IterBase& b) {
+  const double eps = run.eps;
+  const IterParams ip = iter_params(ctx, run, b);
   SMALL(ctx, g, "small", k_hmc_begin, ctx->D, ctx->DP, g.ch, ip);
   if (ctx->hmc_traj) {  // the whole trajectory of every chain in one launch
-    launch_hmc_traj(ctx, g, 0);
+    launch_hmc_traj(ctx, g, &run);
   } else {
     SMALL(ctx, g, "small", k_hmc_pre, ctx->D, ctx->DP, g.ch, eps);
     launch_rowpass<RP_G>(ctx, g, g.ch.trj.w, nullptr);
@@ -702,27 +711,27 @@ void launch_hmc_global_step(rmhmc_ctx* ctx, Group& g, const IterBase& b) {
 }
 
 // One global step of the batch g: transition start, one leapfrog step and transition end of every chain
-void launch_global_step(rmhmc_ctx* ctx, Group& g, const IterBase& b) {
-  if (ctx->sampler == 1) { launch_hmc_global_step(ctx, g, b); return; }
+void launch_global_step(rmhmc_ctx* ctx, const Run& run, Group& g, const IterBase& b) {
+  if (run.sampler == HMC) { launch_hmc_global_step(ctx, run, g, b); return; }
   if (ctx->medium) {  // ... in ONE launch
     const int guards = (ctx->flags & RMHMC_FLAG_GUARDS) ? 1 : 0;
-    const IterParams ip = iter_params(ctx, b);
-    launch(ctx, "medium", [&](hipStream_t st) { launch_step_medium(ctx, g, st, guards, 0, 1, ip); });
+    const IterParams ip = iter_params(ctx, run, b);
+    launch(ctx, "medium", [&](hipStream_t st) { launch_step_medium(ctx, g, st, guards, &run, 1, ip); });
     return;
   }
-  launch_iter_begin(ctx, g, b);
-  step_phases(ctx, g);
-  launch_iter_end(ctx, g, b);
+  launch_iter_begin(ctx, run, g, b);
+  step_phases(ctx, run, g);
+  launch_iter_end(ctx, run, g, b);
 }
 
 // Small-problem path: one launch = `nsteps` global steps of every chain (fused_small.hip.h).
-void launch_fused(rmhmc_ctx* ctx, const IterBase& b, long long nsteps) {
+void launch_fused(rmhmc_ctx* ctx, const Run& run, const IterBase& b, long long nsteps) {
   Group& g = ctx->batch;
   while (nsteps > 0) {
     const int chunk = (int)std::min<long long>(nsteps, 4096);
     FusedParams fp{};
-    fp.ip = iter_params(ctx, b);
-    fp.eps = ctx->eps; fp.K = ctx->K; fp.nsteps = chunk; fp.DPs = ctx->DP; fp.init_eval = 0;
+    fp.ip = iter_params(ctx, run, b);
+    fp.eps = run.eps; fp.K = run.K; fp.nsteps = chunk; fp.DPs = ctx->DP; fp.init_eval = 0;
     launch(ctx, "fused", [&](hipStream_t st) {
       hipLaunchKernelGGL(k_fused_small, dim3((unsigned)((g.n + FS_WAVES - 1) / FS_WAVES)), dim3(64 * FS_WAVES), ctx->fused_lds, st,
                          ctx->dd, g.ch, fp);
@@ -784,8 +793,8 @@ int raise_lds_medium(rmhmc_ctx* ctx) {
   } while (0)
 
 // upload w into trj.w, zero (or upload) p, mark every chain active, evaluate the record (asynchronous: callers sync before they
-// read the downloads).  one_launch: by the one-launch step kernel where the context has it
-int eval_at(rmhmc_ctx* ctx, const double* w, const double* p, bool one_launch = false) {
+// read the downloads).  one_launch: by the one-launch step kernel where the context has it; want_G: see eval_point_phases
+int eval_at(rmhmc_ctx* ctx, const double* w, const double* p, bool one_launch = false, bool want_G = false) {
   Group& g = ctx->batch;
   Chains& ch = g.ch;
   RC(upload_vec(ctx, ch.trj.w, w));
@@ -794,10 +803,10 @@ int eval_at(rmhmc_ctx* ctx, const double* w, const double* p, bool one_launch = 
   fill_int(ctx, ch.phase, 1, ctx->n);
   fill_int(ctx, ch.status, 0, ctx->n);
   if (one_launch && ctx->medium) {  // same arithmetic as inside the one-launch steps (bit-exact checkpoint / resume)
-    launch(ctx, "medium", [&](hipStream_t st) { launch_step_medium(ctx, g, st, 0, 1, 0, IterParams{}); });
+    launch(ctx, "medium", [&](hipStream_t st) { launch_step_medium(ctx, g, st, 0, nullptr, 0, IterParams{}); });
     return RMHMC_OK;
   }
-  eval_point_phases(ctx, g, false);
+  eval_point_phases(ctx, g, nullptr, 0, want_G);
   return RMHMC_OK;
 }
 
@@ -1114,11 +1123,9 @@ int rmhmc_metric(rmhmc_ctx* ctx, const double* w, double* G_out, double* half_lo
   NEED_DATA(ctx);
   if (!w) return fail(ctx, RMHMC_ERR_INVALID, "metric: null pointer");
   ctx->chains_ready = false;
-  if (ctx->big && G_out && !ctx->d_Gcopy) RC(dalloc(ctx, &ctx->d_Gcopy, (size_t)ctx->n * ctx->DP * ctx->DP));
-  ctx->want_G = ctx->big && G_out;
-  int rc_eval = eval_at(ctx, w, nullptr);
-  ctx->want_G = false;
-  RC(rc_eval);
+  const bool want_G = ctx->big && G_out;
+  if (want_G && !ctx->d_Gcopy) RC(dalloc(ctx, &ctx->d_Gcopy, (size_t)ctx->n * ctx->DP * ctx->DP));
+  RC(eval_at(ctx, w, nullptr, false, want_G));
   if (G_out)
     for (int64_t c = 0; c < ctx->n; ++c)  // strip the padding: [DP][DP] -> [D][D]
       HIPCK(hipMemcpy2DAsync(G_out + c * ctx->D * ctx->D, ctx->D * 8, (ctx->big ? ctx->d_Gcopy : ctx->batch.ch.Gq) + c * ctx->DP * ctx->DP, ctx->DP * 8, ctx->D * 8, ctx->D,
@@ -1155,7 +1162,7 @@ int rmhmc_leapfrog(rmhmc_ctx* ctx, double* w, double* p, double eps, const int32
     if (nsteps[c] < 0 || (dir[c] != 1 && dir[c] != -1)) return fail(ctx, RMHMC_ERR_INVALID, "leapfrog: nsteps >= 0 and dir = +-1 required");
     if (nsteps[c] > maxs) maxs = nsteps[c];
   }
-  ctx->eps = eps; ctx->K = K;
+  const Run run{RMHMC, 0, K, eps, 0, 0, nullptr};  // (no transitions: nothing draws a trajectory length from L)
   RC(upload(ctx, ctx->d_nsteps, nsteps, ctx->n));
   RC(upload(ctx, ctx->d_dir, dir, ctx->n));
   RC(eval_at(ctx, w, p));
@@ -1164,7 +1171,7 @@ int rmhmc_leapfrog(rmhmc_ctx* ctx, double* w, double* p, double eps, const int32
     hipLaunchKernelGGL(k_set_leapfrog, dim3((unsigned)((g.n + 255) / 256)), dim3(256), 0, st, g.n, ctx->d_nsteps, ctx->d_dir, g.ch);
   });
   for (int s = 0; s < maxs; ++s) {
-    step_phases(ctx, g);
+    step_phases(ctx, run, g);
     launch(ctx, "small", [&](hipStream_t st) {
       hipLaunchKernelGGL(k_park_finished, dim3((unsigned)((g.n + 255) / 256)), dim3(256), 0, st, g.n, g.ch);
     });
@@ -1173,6 +1180,19 @@ int rmhmc_leapfrog(rmhmc_ctx* ctx, double* w, double* p, double eps, const int32
   RC(download_vec(ctx, p, ctx->batch.ch.p));
   if (half_logdet_out) RC(download(ctx, half_logdet_out, ctx->batch.ch.trj.hld, ctx->n));
   if (status_out) RC(download(ctx, status_out, ctx->batch.ch.status, ctx->n));
+  return sync(ctx);
+}
+
+// every chain between transitions with its counters at zero, nobody done; synchronises
+static int reset_chains(rmhmc_ctx* ctx) {
+  Chains& ch = ctx->batch.ch;
+  fill_int(ctx, ch.phase, 0, ctx->n);
+  fill_int(ctx, ch.steps_left, 0, ctx->n);
+  fill_int(ctx, ch.status, 0, ctx->n);
+  fill_ll(ctx, ch.iter, 0, ctx->n);
+  fill_ll(ctx, ch.accepted, 0, ctx->n);
+  fill_ll(ctx, ch.steps_done, 0, ctx->n);
+  HIPCK(hipMemsetAsync(ctx->d_done, 0, sizeof(int), ctx->stream));
   return sync(ctx);
 }
 
@@ -1188,9 +1208,8 @@ static int init_chains(rmhmc_ctx* ctx, const double* theta0_host /* [n][D] or NU
   }
   if (ctx->fused && allow_fused) {  // the fused path evaluates its own initial record (same arithmetic as inside its steps)
     RC(upload_vec(ctx, g.ch.cur.w, theta0_host));
-    FusedParams fp{};
-    fp.ip = iter_params(ctx, IterBase{0, 0, 0, nullptr, false, false});
-    fp.eps = ctx->eps; fp.K = ctx->K; fp.nsteps = 0; fp.DPs = ctx->DP; fp.init_eval = 1;
+    FusedParams fp{};  // (init_eval returns before the kernel reads ip, eps or K: an evaluation needs no run parameters)
+    fp.nsteps = 0; fp.DPs = ctx->DP; fp.init_eval = 1;
     launch(ctx, "fused", [&](hipStream_t st) {
       hipLaunchKernelGGL(k_fused_small, dim3((unsigned)((g.n + FS_WAVES - 1) / FS_WAVES)), dim3(64 * FS_WAVES), ctx->fused_lds, st,
                          ctx->dd, g.ch, fp);
@@ -1199,14 +1218,7 @@ static int init_chains(rmhmc_ctx* ctx, const double* theta0_host /* [n][D] or NU
     RC(eval_at(ctx, theta0_host, nullptr, allow_medium));
     SMALL(ctx, g, "small", k_commit_all, ctx->D, ctx->DP, g.ch);
   }
-  fill_int(ctx, ctx->batch.ch.phase, 0, ctx->n);
-  fill_int(ctx, ctx->batch.ch.steps_left, 0, ctx->n);
-  fill_int(ctx, ctx->batch.ch.status, 0, ctx->n);
-  fill_ll(ctx, ctx->batch.ch.iter, 0, ctx->n);
-  fill_ll(ctx, ctx->batch.ch.accepted, 0, ctx->n);
-  fill_ll(ctx, ctx->batch.ch.steps_done, 0, ctx->n);
-  HIPCK(hipMemsetAsync(ctx->d_done, 0, sizeof(int), ctx->stream));
-  return sync(ctx);  // theta0 staging vector goes out of scope
+  return reset_chains(ctx);  // (synchronises: the theta0 staging vector goes out of scope)
 }
 
 int rmhmc_transition(rmhmc_ctx* ctx, double* w, const double* z, const double* u_len, const double* g_dir, const double* u_acc,
@@ -1215,7 +1227,7 @@ int rmhmc_transition(rmhmc_ctx* ctx, double* w, const double* z, const double* u
   NEED_DATA(ctx);
   if (!w || !z || !u_len || !g_dir || !u_acc || L < 1 || K < 1) return fail(ctx, RMHMC_ERR_INVALID, "transition: null pointer, L < 1 or K < 1");
   ctx->chains_ready = false;
-  ctx->L = L; ctx->eps = eps; ctx->K = K;
+  const Run run{RMHMC, L, K, eps, 0, 0, nullptr};  // (the randomness is the caller's: no seed)
   RC(init_chains(ctx, w));
   RC(upload(ctx, ctx->d_z, z, (size_t)ctx->n * ctx->D));
   RC(upload(ctx, ctx->d_ulen, u_len, ctx->n));
@@ -1223,14 +1235,14 @@ int rmhmc_transition(rmhmc_ctx* ctx, double* w, const double* z, const double* u
   RC(upload(ctx, ctx->d_uacc, u_acc, ctx->n));
   const IterBase ib{1, 0, 0, nullptr, true, false};
   if (ctx->fused) {
-    launch_fused(ctx, ib, L);
+    launch_fused(ctx, run, ib, L);
   } else {
     Group& g = ctx->batch;
-    launch_iter_begin(ctx, g, ib);
-    launch_iter_end(ctx, g, ib);  // trajectories of zero steps
+    launch_iter_begin(ctx, run, g, ib);
+    launch_iter_end(ctx, run, g, ib);  // trajectories of zero steps
     for (int s = 0; s < L; ++s) {
-      step_phases(ctx, g);
-      launch_iter_end(ctx, g, ib);
+      step_phases(ctx, run, g);
+      launch_iter_end(ctx, run, g, ib);
     }
   }
   std::vector<long long> acc(ctx->n);
@@ -1259,25 +1271,25 @@ struct StepGraph {
     if (graph) (void)hipGraphDestroy(graph);
   }
 };
-static bool step_graph_usable(const rmhmc_ctx* ctx, long long nsteps) {
+static bool step_graph_usable(const rmhmc_ctx* ctx, const Run& run, long long nsteps) {
   if (ctx->timing || nsteps < 8) return false;
-  if (ctx->fused && ctx->sampler == 0) return false;
-  if (ctx->medium && ctx->sampler == 0) return false;  // (the global step is ONE launch there: a one-node graph only costs its instantiation)
+  if (ctx->fused && run.sampler == RMHMC) return false;
+  if (ctx->medium && run.sampler == RMHMC) return false;  // (the global step is ONE launch there: a one-node graph only costs its instantiation)
   return ctx->opt.graph != 0;
 }
-static bool build_step_graph(rmhmc_ctx* ctx, const IterBase& ib, StepGraph& sg) {
+static bool build_step_graph(rmhmc_ctx* ctx, const Run& run, const IterBase& ib, StepGraph& sg) {
   if (hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return false;
-  launch_global_step(ctx, ctx->batch, ib);
+  launch_global_step(ctx, run, ctx->batch, ib);
   if (hipStreamEndCapture(ctx->stream, &sg.graph) != hipSuccess || !sg.graph) { (void)hipGetLastError(); return false; }
   if (hipGraphInstantiate(&sg.exec, sg.graph, nullptr, nullptr, 0) != hipSuccess) { (void)hipGetLastError(); sg.exec = nullptr; return false; }
   return true;
 }
 // nsteps global steps of the generic path (graph replay when it pays, plain launches otherwise)
-static void run_generic_steps(rmhmc_ctx* ctx, const IterBase& ib, long long nsteps, StepGraph* sg) {
+static void run_generic_steps(rmhmc_ctx* ctx, const Run& run, const IterBase& ib, long long nsteps, StepGraph* sg) {
   if (sg && sg->exec) {
     for (long long s = 0; s < nsteps; ++s) { (void)hipGraphLaunch(sg->exec, ctx->stream); flow_tick(ctx); }
   } else {
-    for (long long s = 0; s < nsteps; ++s) { launch_global_step(ctx, ctx->batch, ib); flow_tick(ctx); }
+    for (long long s = 0; s < nsteps; ++s) { launch_global_step(ctx, run, ctx->batch, ib); flow_tick(ctx); }
   }
 }
 
@@ -1310,15 +1322,16 @@ static int report_progress(rmhmc_ctx* ctx, int event, long long iters) {
 // milestone, as the one-chain mode does to reproduce the reference's print-out exactly, would make every chain wait for the
 // slowest fifty iterations at a time (+27 % at 8192 chains).
 static bool progress_ticking(const rmhmc_ctx* ctx) { return ctx->progress_fn && ctx->progress_every > 0 && ctx->n > 1; }
-static int progress_fire(rmhmc_ctx* ctx, long long min_iter) {
-  if (!progress_ticking(ctx)) return RMHMC_OK;
+// next: the sampling call's next milestone to report, or nullptr: a phase without reports (run_phase: none for ONE chain either)
+static int progress_fire(rmhmc_ctx* ctx, long long* next, long long min_iter) {
+  if (!next || !progress_ticking(ctx)) return RMHMC_OK;
   long long last = -1;
-  while (ctx->progress_next <= min_iter) { last = ctx->progress_next; ctx->progress_next += ctx->progress_every; }
+  while (*next <= min_iter) { last = *next; *next += ctx->progress_every; }
   if (last >= 0) RC(report_progress(ctx, RMHMC_EV_PROGRESS, last));
   return RMHMC_OK;
 }
 
-static int run_until_done(rmhmc_ctx* ctx, const IterBase& ib, long long min_steps) {
+static int run_until_done(rmhmc_ctx* ctx, const Run& run, const IterBase& ib, long long min_steps, long long* progress_next) {
   // Every chain needs at least min_steps more global steps.  Afterwards the host looks at the device state and issues, each time,
   // as many steps as the slowest chain is certain to need: (limit - its completed transitions), a transition taking >= 1 step.
   // The remaining work shrinks geometrically (a transition averages (L+1)/2 steps), so a run costs O(log) host round trips
@@ -1326,31 +1339,31 @@ static int run_until_done(rmhmc_ctx* ctx, const IterBase& ib, long long min_step
   int done = 0;
   long long s = min_steps, min_iter = 0;
   const long long poll = 4;
-  const bool fused = ctx->fused && ctx->sampler == 0;
-  const bool ticking = progress_ticking(ctx);
-  const long long chunk = ticking ? std::max<long long>(8, ctx->progress_every * (ctx->L + 1) / 2) : min_steps;  // ~ one report per chunk
+  const bool fused = ctx->fused && run.sampler == RMHMC;
+  const bool ticking = progress_next && progress_ticking(ctx);
+  const long long chunk = ticking ? std::max<long long>(8, ctx->progress_every * (run.L + 1) / 2) : min_steps;  // ~ one report per chunk
   StepGraph sg;
-  if (!fused && step_graph_usable(ctx, std::min(min_steps, chunk))) (void)build_step_graph(ctx, ib, sg);
+  if (!fused && step_graph_usable(ctx, run, std::min(min_steps, chunk))) (void)build_step_graph(ctx, run, ib, sg);
   for (long long left = min_steps; left > 0;) {
     const long long k = std::min(left, chunk);
-    if (fused) launch_fused(ctx, ib, k);
-    else run_generic_steps(ctx, ib, k, &sg);
+    if (fused) launch_fused(ctx, run, ib, k);
+    else run_generic_steps(ctx, run, ib, k, &sg);
     left -= k;
     if (ticking && left > 0) {
       RC(poll_progress(ctx, &done, &min_iter));
-      RC(progress_fire(ctx, min_iter));
+      RC(progress_fire(ctx, progress_next, min_iter));
     }
   }
   for (;;) {
     RC(poll_progress(ctx, &done, &min_iter));
-    RC(progress_fire(ctx, min_iter));
+    RC(progress_fire(ctx, progress_next, min_iter));
     if (done >= ctx->n) break;
     long long next = std::max(poll, ib.limit - min_iter);
     if (ticking) next = std::min(next, chunk);
-    if (fused) launch_fused(ctx, ib, next);
-    else run_generic_steps(ctx, ib, next, &sg);
+    if (fused) launch_fused(ctx, run, ib, next);
+    else run_generic_steps(ctx, run, ib, next, &sg);
     s += next;
-    if (s > min_steps * (long long)ctx->L + 1000000) return fail(ctx, RMHMC_ERR_RUNTIME, "sampler did not terminate");
+    if (s > min_steps * (long long)run.L + 1000000) return fail(ctx, RMHMC_ERR_RUNTIME, "sampler did not terminate");
   }
   return RMHMC_OK;
 }
@@ -1361,8 +1374,8 @@ static int run_until_done(rmhmc_ctx* ctx, const IterBase& ib, long long min_step
 // A milestone that coincides with a phase boundary (burn_in + 1 completed transitions) is reported on the side of the burn-in banner
 // where the reference prints it: rmhmc.py:38-45 prints at the TOP of the next iteration, i.e. after the banner of :194-196
 // (at_from of phase B); hmc.py:85-94 prints at the bottom of the iteration itself, just before the banner (at_limit of phase A).
-static int run_phase(rmhmc_ctx* ctx, const IterBase& ib, long long from, bool at_from = false, bool at_limit = false) {
-  if (ctx->progress_fn && ctx->progress_every > 0 && ctx->n == 1) {
+static int run_phase(rmhmc_ctx* ctx, const Run& run, const IterBase& ib, long long from, long long* progress_next, bool at_from = false, bool at_limit = false) {
+  if (progress_next && ctx->progress_fn && ctx->progress_every > 0 && ctx->n == 1) {
     long long m = ctx->progress_first;
     if (from > m) m += ((from - m + ctx->progress_every - 1) / ctx->progress_every) * ctx->progress_every;   // first milestone >= from
     if (m == from) {
@@ -1373,25 +1386,25 @@ static int run_phase(rmhmc_ctx* ctx, const IterBase& ib, long long from, bool at
       IterBase seg = ib;
       seg.limit = m;
       HIPCK(hipMemsetAsync(ctx->d_done, 0, sizeof(int), ctx->stream));
-      RC(run_until_done(ctx, seg, m - from));
+      RC(run_until_done(ctx, run, seg, m - from, progress_next));
       RC(report_progress(ctx, RMHMC_EV_PROGRESS, m));
       from = m;
     }
     HIPCK(hipMemsetAsync(ctx->d_done, 0, sizeof(int), ctx->stream));
   }
-  if (ib.limit > from) RC(run_until_done(ctx, ib, ib.limit - from));
+  if (ib.limit > from) RC(run_until_done(ctx, run, ib, ib.limit - from, progress_next));
   return RMHMC_OK;
 }
 
 // One global step on the first na chains only (na a multiple of 128 or n), on a narrowed copy of the batch: every kernel takes its
 // chain count and its partial-plane strides from the batch it is handed, so producers and consumers agree.
-static void launch_global_step_prefix(rmhmc_ctx* ctx, const IterBase& ib, int na) {
+static void launch_global_step_prefix(rmhmc_ctx* ctx, const Run& run, const IterBase& ib, int na) {
   Group g = ctx->batch;
   g.n = na; g.ch.n = na;
   if (g.nCp) g.nCp = (na + I8_BM - 1) / I8_BM * I8_BM;
   // (only the chain count and its int8 padding narrow.  Row ranges, k-split planes and row splits are the plan's, chosen for the
   // whole batch: every chain's sums keep their order, so the results are bit-identical to the unsorted run)
-  launch_global_step(ctx, g, ib);
+  launch_global_step(ctx, run, g, ib);
 }
 
 // Work-sorted phase B.  The trajectory lengths do not depend on the state (RandomStep = ceil(rand() L), rmhmc.py:89), so the number of
@@ -1400,21 +1413,21 @@ static void launch_global_step_prefix(rmhmc_ctx* ctx, const IterBase& ib, int na
 // the phase costs sum_c T_c chain-steps instead of n max_c T_c (8192 chains, 199 transitions: 791 global steps for a mean of 696, i.e.
 // 12 % of the TimeTaken window spent on finished chains).  Samples do not change: chains are independent and their randomness is keyed
 // by the chain's index in the caller's order (IterParams::orig).
-static int run_sorted_phase(rmhmc_ctx* ctx, const IterBase& ib, const std::vector<long long>& T /* descending */) {
+static int run_sorted_phase(rmhmc_ctx* ctx, const Run& run, const IterBase& ib, const std::vector<long long>& T /* descending */, long long* progress_next) {
   const int n = (int)ctx->n;
   const long long Tmin = T[n - 1], Tmax = T[0];
   const bool ticking = progress_ticking(ctx);
-  const long long chunk = ticking ? std::max<long long>(8, ctx->progress_every * (ctx->L + 1) / 2) : Tmax + 1;
+  const long long chunk = ticking ? std::max<long long>(8, ctx->progress_every * (run.L + 1) / 2) : Tmax + 1;
   int done = 0;
   long long mi = 0;
   {
     StepGraph sg;
-    if (step_graph_usable(ctx, std::min(Tmin, chunk))) (void)build_step_graph(ctx, ib, sg);
+    if (step_graph_usable(ctx, run, std::min(Tmin, chunk))) (void)build_step_graph(ctx, run, ib, sg);
     for (long long left = Tmin; left > 0;) {
       const long long k = std::min(left, chunk);
-      run_generic_steps(ctx, ib, k, &sg);
+      run_generic_steps(ctx, run, ib, k, &sg);
       left -= k;
-      if (ticking) { RC(poll_progress(ctx, &done, &mi)); RC(progress_fire(ctx, mi)); }
+      if (ticking) { RC(poll_progress(ctx, &done, &mi)); RC(progress_fire(ctx, progress_next, mi)); }
     }
     HIPCK(hipStreamSynchronize(ctx->stream));  // (the graph goes out of scope)
   }
@@ -1422,31 +1435,34 @@ static int run_sorted_phase(rmhmc_ctx* ctx, const IterBase& ib, const std::vecto
   for (long long s = Tmin; s < Tmax; ++s) {
     while (na > 0 && T[na - 1] <= s) --na;  // chains with T > s are still running: positions [0, na)
     const int nar = std::min(n, (na + 127) / 128 * 128);
-    if (nar == n) launch_global_step(ctx, ctx->batch, ib);
-    else launch_global_step_prefix(ctx, ib, nar);
+    if (nar == n) launch_global_step(ctx, run, ctx->batch, ib);
+    else launch_global_step_prefix(ctx, run, ib, nar);
     flow_tick(ctx);
-    if (ticking && (s - Tmin) % chunk == chunk - 1) { RC(poll_progress(ctx, &done, &mi)); RC(progress_fire(ctx, mi)); }
+    if (ticking && (s - Tmin) % chunk == chunk - 1) { RC(poll_progress(ctx, &done, &mi)); RC(progress_fire(ctx, progress_next, mi)); }
   }
   RC(poll_progress(ctx, &done, &mi));
-  RC(progress_fire(ctx, mi));
-  if (done < n) RC(run_until_done(ctx, ib, 1));  // (safety net: never taken if the schedule above is right)
+  RC(progress_fire(ctx, progress_next, mi));
+  if (done < n) RC(run_until_done(ctx, run, ib, 1, progress_next));  // (safety net: never taken if the schedule above is right)
   return RMHMC_OK;
 }
 
-// Runs the sampler; the saved states go to the device buffer d_samples ([n][S][D], caller-provided).  Per-chain counters are left
-// on the device: ch.accepted, and the post-burn-in leapfrog steps in d_steps0 (steps_done at the end minus at the burn-in mark).
-static int sample_core(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, const double* theta0, double* d_samples, double* seconds_out) {
+// per-chain counters of a sampler run, on the device in the caller's order: accepted proposals and post-burn-in leapfrog steps
+struct Counters { const long long *accepted, *steps; };
+
+// Runs the RMHMC sampler; the saved states go to the device buffer d_samples ([n][S][D], caller-provided) and `counters` says where
+// the run left its counters.  asked: the call's parameters in the caller's order (orig == nullptr); a work-sorted run steps with a
+// copy that carries the map.
+static int sample_core(rmhmc_ctx* ctx, const Run& asked, int64_t n_iter, int64_t burn_in, const double* theta0, double* d_samples, double* seconds_out, Counters* counters) {
   const long long S = n_iter - burn_in;
   const int n = (int)ctx->n;
-  // work-sorted layout (see run_sorted_phase): generic and one-launch stepping paths of the RMHMC sampler
+  // work-sorted layout (see run_sorted_phase): generic and one-launch stepping paths
   std::vector<long long> T;
   std::vector<double> th_perm;
-  bool sorted = ctx->sampler == 0 && !ctx->fused && n >= 2 && n_iter > burn_in + 1;
-  ctx->progress_next = ctx->progress_first;
-  sorted = sorted && ctx->opt.sorted;
+  const bool sorted = !ctx->fused && n >= 2 && n_iter > burn_in + 1 && ctx->opt.sorted;
+  long long progress_next = ctx->progress_first;
   if (sorted) {
-    hipLaunchKernelGGL(k_traj_steps, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (unsigned long long)ctx->seed,
-                       (long long)ctx->chain_offset, ctx->L, (long long)burn_in + 1, (long long)n_iter, (size_t)n, ctx->d_T);
+    hipLaunchKernelGGL(k_traj_steps, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (unsigned long long)asked.seed,
+                       (long long)asked.chain_offset, asked.L, (long long)burn_in + 1, (long long)n_iter, (size_t)n, ctx->d_T);
     std::vector<long long> t0(n);
     RC(download(ctx, t0.data(), ctx->d_T, (size_t)n));
     RC(sync(ctx));
@@ -1462,44 +1478,40 @@ static int sample_core(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, const do
       for (int d = 0; d < ctx->D; ++d) th_perm[(size_t)i * ctx->D + d] = theta0 ? theta0[(size_t)orig[i] * ctx->D + d] : 1e-3;  // rmhmc.py:27
     theta0 = th_perm.data();
   }
-  ctx->sorted = sorted;
-  int rc = [&]() -> int {
-    RC(init_chains(ctx, theta0));
-    // phase A: every chain completes transitions 0..burn_in; chains that get there first wait, so that
-    // the timed phase B covers exactly the post-burn-in transitions (TimeTaken, rmhmc.py:194-198)
-    const IterBase ipA{burn_in + 1, burn_in, S, d_samples, false, true};
-    RC(run_phase(ctx, ipA, 0));
-    HIPCK(hipMemcpyAsync(ctx->d_steps0, ctx->batch.ch.steps_done, sizeof(long long) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCK(hipMemsetAsync(ctx->d_done, 0, sizeof(int), ctx->stream));
-    RC(sync(ctx));
-    if (ctx->progress_fn) RC(report_progress(ctx, RMHMC_EV_BURNIN_DONE, burn_in + 1));  // rmhmc.py:194-196: banner, then the timer starts
-    const auto t0 = std::chrono::steady_clock::now();
-    if (n_iter > burn_in + 1) {
-      const IterBase ipB{n_iter, burn_in, S, d_samples, false, true};
-      if (sorted) RC(run_sorted_phase(ctx, ipB, T));
-      else RC(run_phase(ctx, ipB, burn_in + 1, true));
-    }
-    RC(sync(ctx));
-    if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    hipLaunchKernelGGL(k_sub_ll, dim3((unsigned)((ctx->n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_steps0, ctx->batch.ch.steps_done, (size_t)ctx->n);
-    if (sorted) {  // counters back into the caller's order: d_T[0..n) accepted, d_T[n..2n) post-burn-in steps
-      const dim3 grid((unsigned)((n + 255) / 256));
-      hipLaunchKernelGGL(k_scatter_ll, grid, dim3(256), 0, ctx->stream, ctx->d_T, ctx->batch.ch.accepted, ctx->d_orig, (size_t)n);
-      hipLaunchKernelGGL(k_scatter_ll, grid, dim3(256), 0, ctx->stream, ctx->d_T + n, ctx->d_steps0, ctx->d_orig, (size_t)n);
-    }
-    return RMHMC_OK;
-  }();
-  ctx->sorted = false;
-  ctx->counters_sorted = sorted && rc == RMHMC_OK;
-  return rc;
+  Run run = asked;
+  if (sorted) run.orig = ctx->d_orig;
+  RC(init_chains(ctx, theta0));
+  // phase A: every chain completes transitions 0..burn_in; chains that get there first wait, so that
+  // the timed phase B covers exactly the post-burn-in transitions (TimeTaken, rmhmc.py:194-198)
+  const IterBase ipA{burn_in + 1, burn_in, S, d_samples, false, true};
+  RC(run_phase(ctx, run, ipA, 0, &progress_next));
+  HIPCK(hipMemcpyAsync(ctx->d_steps0, ctx->batch.ch.steps_done, sizeof(long long) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
+  HIPCK(hipMemsetAsync(ctx->d_done, 0, sizeof(int), ctx->stream));
+  RC(sync(ctx));
+  if (ctx->progress_fn) RC(report_progress(ctx, RMHMC_EV_BURNIN_DONE, burn_in + 1));  // rmhmc.py:194-196: banner, then the timer starts
+  const auto t0 = std::chrono::steady_clock::now();
+  if (n_iter > burn_in + 1) {
+    const IterBase ipB{n_iter, burn_in, S, d_samples, false, true};
+    if (sorted) RC(run_sorted_phase(ctx, run, ipB, T, &progress_next));
+    else RC(run_phase(ctx, run, ipB, burn_in + 1, &progress_next, true));
+  }
+  RC(sync(ctx));
+  if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  hipLaunchKernelGGL(k_sub_ll, dim3((unsigned)((ctx->n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_steps0, ctx->batch.ch.steps_done, (size_t)ctx->n);
+  *counters = Counters{ctx->batch.ch.accepted, ctx->d_steps0};
+  if (sorted) {  // counters back into the caller's order: d_T[0..n) accepted, d_T[n..2n) post-burn-in steps
+    const dim3 grid((unsigned)((n + 255) / 256));
+    hipLaunchKernelGGL(k_scatter_ll, grid, dim3(256), 0, ctx->stream, ctx->d_T, ctx->batch.ch.accepted, ctx->d_orig, (size_t)n);
+    hipLaunchKernelGGL(k_scatter_ll, grid, dim3(256), 0, ctx->stream, ctx->d_T + n, ctx->d_steps0, ctx->d_orig, (size_t)n);
+    *counters = Counters{ctx->d_T, ctx->d_T + n};
+  }
+  return RMHMC_OK;
 }
 // the counters of sample_core to host or device int64 arrays (either may be NULL)
-static int sample_counters(rmhmc_ctx* ctx, int64_t* accept_out, int64_t* steps_out, hipMemcpyKind kind) {
+static int sample_counters(rmhmc_ctx* ctx, const Counters& c, int64_t* accept_out, int64_t* steps_out, hipMemcpyKind kind) {
   static_assert(sizeof(long long) == sizeof(int64_t), "int64");
-  const long long* acc = ctx->counters_sorted ? ctx->d_T : ctx->batch.ch.accepted;
-  const long long* stp = ctx->counters_sorted ? ctx->d_T + ctx->n : ctx->d_steps0;
-  if (accept_out) HIPCK(hipMemcpyAsync(accept_out, acc, sizeof(int64_t) * ctx->n, kind, ctx->stream));
-  if (steps_out) HIPCK(hipMemcpyAsync(steps_out, stp, sizeof(int64_t) * ctx->n, kind, ctx->stream));
+  if (accept_out) HIPCK(hipMemcpyAsync(accept_out, c.accepted, sizeof(int64_t) * ctx->n, kind, ctx->stream));
+  if (steps_out) HIPCK(hipMemcpyAsync(steps_out, c.steps, sizeof(int64_t) * ctx->n, kind, ctx->stream));
   return RMHMC_OK;
 }
 
@@ -1509,14 +1521,15 @@ static int sample_impl(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t 
   if (!samples_out || burn_in < 0 || burn_in >= n_iter || L < 1 || K < 1)
     return fail(ctx, RMHMC_ERR_INVALID, "sample: need samples_out, 0 <= burn_in < n_iter, L >= 1, K >= 1");
   ctx->chains_ready = false;
-  ctx->L = L; ctx->eps = eps; ctx->K = K; ctx->seed = seed; ctx->chain_offset = chain_offset;
+  const Run run{RMHMC, L, K, eps, seed, chain_offset, nullptr};
   const size_t count = (size_t)ctx->n * (n_iter - burn_in) * ctx->D;
   double* d_samples = dev ? samples_out : nullptr;  // device-resident write-out: the sampler saves straight into the caller's HBM buffer
   if (!dev) HIPCK(hipMalloc((void**)&d_samples, sizeof(double) * count));
   int rc = [&]() -> int {
-    RC(sample_core(ctx, n_iter, burn_in, theta0, d_samples, seconds_out));
+    Counters counters{};
+    RC(sample_core(ctx, run, n_iter, burn_in, theta0, d_samples, seconds_out, &counters));
     if (!dev) HIPCK(hipMemcpyAsync(samples_out, d_samples, sizeof(double) * count, hipMemcpyDeviceToHost, ctx->stream));
-    RC(sample_counters(ctx, accept_out, steps_out, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    RC(sample_counters(ctx, counters, accept_out, steps_out, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
     return sync(ctx);
   }();
   if (!dev && d_samples) (void)hipFree(d_samples);
@@ -1568,13 +1581,14 @@ static int sample_stats_impl(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, in
   if (burn_in < 0 || burn_in >= n_iter || L < 1 || K < 1)
     return fail(ctx, RMHMC_ERR_INVALID, "sample_stats: need 0 <= burn_in < n_iter, L >= 1, K >= 1");
   ctx->chains_ready = false;
-  ctx->L = L; ctx->eps = eps; ctx->K = K; ctx->seed = seed; ctx->chain_offset = chain_offset;
+  const Run run{RMHMC, L, K, eps, seed, chain_offset, nullptr};
   const long long S = n_iter - burn_in;
   double* d_samples = nullptr;
   double* d_out = nullptr;  // [3][n][D]: ess, mean, var
   HIPCK(hipMalloc((void**)&d_samples, sizeof(double) * (size_t)ctx->n * S * ctx->D));
   int rc = [&]() -> int {
-    RC(sample_core(ctx, n_iter, burn_in, theta0, d_samples, seconds_out));
+    Counters counters{};
+    RC(sample_core(ctx, run, n_iter, burn_in, theta0, d_samples, seconds_out, &counters));
     const size_t nd = (size_t)ctx->n * ctx->D;
     HIPCK(hipMalloc((void**)&d_out, sizeof(double) * 3 * nd));
     RC(launch_ess(ctx, d_samples, ctx->n, S, ctx->D, d_out, d_out + nd, d_out + 2 * nd));
@@ -1582,7 +1596,7 @@ static int sample_stats_impl(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, in
     if (ess_out) HIPCK(hipMemcpyAsync(ess_out, d_out, sizeof(double) * nd, kind, ctx->stream));
     if (mean_out) HIPCK(hipMemcpyAsync(mean_out, d_out + nd, sizeof(double) * nd, kind, ctx->stream));
     if (var_out) HIPCK(hipMemcpyAsync(var_out, d_out + 2 * nd, sizeof(double) * nd, kind, ctx->stream));
-    RC(sample_counters(ctx, accept_out, steps_out, kind));
+    RC(sample_counters(ctx, counters, accept_out, steps_out, kind));
     return sync(ctx);
   }();
   if (d_samples) (void)hipFree(d_samples);
@@ -1603,7 +1617,7 @@ int rmhmc_sample_stats_dev(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int3
 }
 
 // ---- plain HMC (code/hmc.py) -------------------------------------------------------------------------
-// evaluate gradient and log joint at theta0 and commit them as the current point of every chain
+// evaluate gradient and log joint at theta0 and commit them as the current point of every chain (no run parameters, as init_chains)
 static int hmc_init_chains(rmhmc_ctx* ctx, const double* theta0_host /* [n][D] or NULL: zeros, hmc.py:27 */) {
   std::vector<double> th;
   if (!theta0_host) { th.assign((size_t)ctx->n * ctx->D, 0.0); theta0_host = th.data(); }
@@ -1611,19 +1625,12 @@ static int hmc_init_chains(rmhmc_ctx* ctx, const double* theta0_host /* [n][D] o
   fill_int(ctx, ctx->batch.ch.phase, 1, ctx->n);
   Group& g = ctx->batch;
   if (ctx->hmc_traj) {
-    launch_hmc_traj(ctx, g, 1);
+    launch_hmc_traj(ctx, g, nullptr);
   } else {
     launch_rowpass<RP_G>(ctx, g, g.ch.trj.w, nullptr);
     SMALL(ctx, g, "small", k_hmc_init, ctx->dd, g.ch, ctx->nsplit);
   }
-  fill_int(ctx, ctx->batch.ch.phase, 0, ctx->n);
-  fill_int(ctx, ctx->batch.ch.steps_left, 0, ctx->n);
-  fill_int(ctx, ctx->batch.ch.status, 0, ctx->n);
-  fill_ll(ctx, ctx->batch.ch.iter, 0, ctx->n);
-  fill_ll(ctx, ctx->batch.ch.accepted, 0, ctx->n);
-  fill_ll(ctx, ctx->batch.ch.steps_done, 0, ctx->n);
-  HIPCK(hipMemsetAsync(ctx->d_done, 0, sizeof(int), ctx->stream));
-  return sync(ctx);
+  return reset_chains(ctx);
 }
 
 int rmhmc_hmc_transition(rmhmc_ctx* ctx, double* w, const double* z, const double* u_len, const double* u_acc, int32_t L, double eps,
@@ -1632,28 +1639,24 @@ int rmhmc_hmc_transition(rmhmc_ctx* ctx, double* w, const double* z, const doubl
   NEED_DATA(ctx);
   if (!w || !z || !u_len || !u_acc || L < 1) return fail(ctx, RMHMC_ERR_INVALID, "hmc_transition: null pointer or L < 1");
   ctx->chains_ready = false;
-  ctx->L = L; ctx->eps = eps; ctx->sampler = 1;
-  int rc = [&]() -> int {
-    RC(hmc_init_chains(ctx, w));
-    RC(upload(ctx, ctx->d_z, z, (size_t)ctx->n * ctx->D));
-    RC(upload(ctx, ctx->d_ulen, u_len, ctx->n));
-    RC(upload(ctx, ctx->d_uacc, u_acc, ctx->n));
-    const IterBase ib{1, 0, 0, nullptr, true, false};
-    for (int s = 0; s < L; ++s) launch_hmc_global_step(ctx, ctx->batch, ib);
-    std::vector<long long> acc(ctx->n);
-    RC(download_vec(ctx, w, ctx->batch.ch.cur.w));
-    RC(download(ctx, acc.data(), ctx->batch.ch.accepted, ctx->n));
-    if (nsteps_out) RC(download(ctx, nsteps_out, ctx->batch.ch.nsteps_last, ctx->n));
-    if (H_cur_out) RC(download(ctx, H_cur_out, ctx->batch.ch.Hcur, ctx->n));
-    if (H_prop_out) RC(download(ctx, H_prop_out, ctx->batch.ch.Hprop, ctx->n));
-    if (w_prop_out) RC(download_vec(ctx, w_prop_out, ctx->batch.ch.trj.w));
-    if (p_prop_out) RC(download_vec(ctx, p_prop_out, ctx->batch.ch.p));
-    RC(sync(ctx));
-    if (accepted_out) for (int64_t c = 0; c < ctx->n; ++c) accepted_out[c] = (int32_t)acc[c];
-    return RMHMC_OK;
-  }();
-  ctx->sampler = 0;
-  return rc;
+  const Run run{HMC, L, 0, eps, 0, 0, nullptr};  // (no fixed-point iterations: no K; the randomness is the caller's: no seed)
+  RC(hmc_init_chains(ctx, w));
+  RC(upload(ctx, ctx->d_z, z, (size_t)ctx->n * ctx->D));
+  RC(upload(ctx, ctx->d_ulen, u_len, ctx->n));
+  RC(upload(ctx, ctx->d_uacc, u_acc, ctx->n));
+  const IterBase ib{1, 0, 0, nullptr, true, false};
+  for (int s = 0; s < L; ++s) launch_hmc_global_step(ctx, run, ctx->batch, ib);
+  std::vector<long long> acc(ctx->n);
+  RC(download_vec(ctx, w, ctx->batch.ch.cur.w));
+  RC(download(ctx, acc.data(), ctx->batch.ch.accepted, ctx->n));
+  if (nsteps_out) RC(download(ctx, nsteps_out, ctx->batch.ch.nsteps_last, ctx->n));
+  if (H_cur_out) RC(download(ctx, H_cur_out, ctx->batch.ch.Hcur, ctx->n));
+  if (H_prop_out) RC(download(ctx, H_prop_out, ctx->batch.ch.Hprop, ctx->n));
+  if (w_prop_out) RC(download_vec(ctx, w_prop_out, ctx->batch.ch.trj.w));
+  if (p_prop_out) RC(download_vec(ctx, p_prop_out, ctx->batch.ch.p));
+  RC(sync(ctx));
+  if (accepted_out) for (int64_t c = 0; c < ctx->n; ++c) accepted_out[c] = (int32_t)acc[c];
+  return RMHMC_OK;
 }
 
 int rmhmc_hmc_sample(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L, double eps, uint64_t seed, int64_t chain_offset,
@@ -1662,16 +1665,15 @@ int rmhmc_hmc_sample(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L,
   if (!samples_out || burn_in < 0 || burn_in >= n_iter || L < 1)
     return fail(ctx, RMHMC_ERR_INVALID, "hmc_sample: need samples_out, 0 <= burn_in < n_iter, L >= 1");
   ctx->chains_ready = false;
-  ctx->L = L; ctx->eps = eps; ctx->seed = seed; ctx->chain_offset = chain_offset;
+  const Run run{HMC, L, 0, eps, seed, chain_offset, nullptr};  // (no fixed-point iterations: no K)
   const long long S = n_iter - burn_in;
   double* d_samples = nullptr;
   HIPCK(hipMalloc((void**)&d_samples, sizeof(double) * (size_t)ctx->n * S * ctx->D));
-  ctx->sampler = 1;  // (after the allocation: an early return above must not leave the context in HMC mode)
-  ctx->progress_next = ctx->progress_first;
+  long long progress_next = ctx->progress_first;
   int rc = [&]() -> int {
     RC(hmc_init_chains(ctx, theta0));
     const IterBase ipA{burn_in + 1, burn_in, S, d_samples, false, true};
-    RC(run_phase(ctx, ipA, 0, false, true));
+    RC(run_phase(ctx, run, ipA, 0, &progress_next, false, true));
     HIPCK(hipMemcpyAsync(ctx->d_steps0, ctx->batch.ch.steps_done, sizeof(long long) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
     HIPCK(hipMemsetAsync(ctx->d_done, 0, sizeof(int), ctx->stream));
     RC(sync(ctx));
@@ -1679,12 +1681,8 @@ int rmhmc_hmc_sample(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L,
     const auto t0 = std::chrono::steady_clock::now();
     if (n_iter > burn_in + 1) {
       // hmc.py:83-89 reports during burn-in only (`elif` of the save branch): no milestones, hence no cuts, inside TimeTaken
-      const rmhmc_progress_fn fn = ctx->progress_fn;
-      ctx->progress_fn = nullptr;
       const IterBase ipB{n_iter, burn_in, S, d_samples, false, true};
-      const int rcB = run_phase(ctx, ipB, burn_in + 1);
-      ctx->progress_fn = fn;
-      RC(rcB);
+      RC(run_phase(ctx, run, ipB, burn_in + 1, nullptr));
     }
     RC(sync(ctx));
     if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -1701,17 +1699,17 @@ int rmhmc_hmc_sample(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L,
     return RMHMC_OK;
   }();
   (void)hipFree(d_samples);
-  ctx->sampler = 0;
   return rc;
 }
 
 // ---- simplified manifold MALA (BLR_mMALA_Simp.m) -------------------------------------------------------------
-static void launch_mmala_step(rmhmc_ctx* ctx, Group& g, const IterBase& b) {
-  const double eps = ctx->eps;
+// (run: the step size, the Philox key and the sampler kind of the RMHMC records; mMALA has no L and no K)
+static void launch_mmala_step(rmhmc_ctx* ctx, const Run& run, Group& g, const IterBase& b) {
+  const double eps = run.eps;
   const int full = (ctx->flags & RMHMC_FLAG_MMALA_FULL) ? 1 : 0;
-  const IterParams ip = iter_params(ctx, b);
+  const IterParams ip = iter_params(ctx, run, b);
   SMALL(ctx, g, "small", k_mmala_begin, ctx->D, ctx->DP, g.ch, ip, eps, full);
-  eval_point_phases(ctx, g, false, full ? 2 : 1);
+  eval_point_phases(ctx, g, nullptr, full ? 2 : 1);
   SMALL(ctx, g, "small", k_mmala_end, ctx->D, ctx->DP, g.ch, ip, eps, full);
 }
 // record at theta0: mMALA never uses the fused stepping kernel, so not by its evaluation either; by the one-launch step kernel's where
@@ -1727,12 +1725,12 @@ int rmhmc_mmala_transition(rmhmc_ctx* ctx, double* w, const double* z, const dou
   NEED_DATA(ctx);
   if (!w || !z || !u_acc || !(eps > 0)) return fail(ctx, RMHMC_ERR_INVALID, "mmala_transition: null pointer or eps <= 0");
   ctx->chains_ready = false;
-  ctx->eps = eps;
+  const Run run{RMHMC, 0, 0, eps, 0, 0, nullptr};
   RC(mmala_init(ctx, w));
   RC(upload(ctx, ctx->d_z, z, (size_t)ctx->n * ctx->D));
   RC(upload(ctx, ctx->d_uacc, u_acc, ctx->n));
   const IterBase ib{1, 0, 0, nullptr, true, false};
-  launch_mmala_step(ctx, ctx->batch, ib);
+  launch_mmala_step(ctx, run, ctx->batch, ib);
   std::vector<long long> acc(ctx->n);
   RC(download_vec(ctx, w, ctx->batch.ch.cur.w));
   RC(download(ctx, acc.data(), ctx->batch.ch.accepted, ctx->n));
@@ -1749,17 +1747,17 @@ int rmhmc_mmala_sample(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, double e
   if (!samples_out || burn_in < 0 || burn_in >= n_iter || !(eps > 0))
     return fail(ctx, RMHMC_ERR_INVALID, "mmala_sample: need samples_out, 0 <= burn_in < n_iter, eps > 0");
   ctx->chains_ready = false;
-  ctx->eps = eps; ctx->seed = seed; ctx->chain_offset = chain_offset;
+  const Run run{RMHMC, 0, 0, eps, seed, chain_offset, nullptr};
   const long long S = n_iter - burn_in;
   double* d_samples = nullptr;
   HIPCK(hipMalloc((void**)&d_samples, sizeof(double) * (size_t)ctx->n * S * ctx->D));
   int rc = [&]() -> int {
     RC(mmala_init(ctx, theta0));
     const IterBase ib{n_iter, burn_in, S, d_samples, false, false};
-    for (int64_t it = 0; it <= burn_in; ++it) { launch_mmala_step(ctx, ctx->batch, ib); flow_tick(ctx); }
+    for (int64_t it = 0; it <= burn_in; ++it) { launch_mmala_step(ctx, run, ctx->batch, ib); flow_tick(ctx); }
     RC(sync(ctx));
     const auto t0 = std::chrono::steady_clock::now();
-    for (int64_t it = burn_in + 1; it < n_iter; ++it) { launch_mmala_step(ctx, ctx->batch, ib); flow_tick(ctx); }
+    for (int64_t it = burn_in + 1; it < n_iter; ++it) { launch_mmala_step(ctx, run, ctx->batch, ib); flow_tick(ctx); }
     RC(sync(ctx));
     if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     HIPCK(hipMemcpyAsync(samples_out, d_samples, sizeof(double) * (size_t)ctx->n * S * ctx->D, hipMemcpyDeviceToHost, ctx->stream));
@@ -1776,9 +1774,9 @@ int rmhmc_mmala_sample(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, double e
 int rmhmc_chains_init(rmhmc_ctx* ctx, const double* theta0, uint64_t seed, int64_t chain_offset, int32_t L, double eps, int32_t K) {
   NEED_DATA(ctx);
   if (L < 1 || K < 1) return fail(ctx, RMHMC_ERR_INVALID, "chains_init: L >= 1 and K >= 1 required");
-  ctx->L = L; ctx->eps = eps; ctx->K = K; ctx->seed = seed; ctx->chain_offset = chain_offset;
   RC(init_chains(ctx, theta0));
   if (ctx->batch.dcount) HIPCK(hipMemsetAsync(ctx->batch.dcount, 0, 6 * sizeof(unsigned long long), ctx->stream));
+  ctx->chains = Run{RMHMC, L, K, eps, seed, chain_offset, nullptr};
   ctx->chains_ready = true;
   return RMHMC_OK;
 }
@@ -1786,15 +1784,16 @@ int rmhmc_chains_init(rmhmc_ctx* ctx, const double* theta0, uint64_t seed, int64
 int rmhmc_chains_run(rmhmc_ctx* ctx, int64_t n_steps) {
   NEED_DATA(ctx);
   if (!ctx->chains_ready) return fail(ctx, RMHMC_ERR_INVALID, "chains_run: rmhmc_chains_init has not been called");
+  const Run& run = ctx->chains;  // (chains_ready holds)
   const IterBase ib{(long long)1 << 62, 0, 0, nullptr, false, false};
   {
     Timed t(ctx, "total", ctx->stream);
     if (ctx->fused) {
-      launch_fused(ctx, ib, n_steps);
+      launch_fused(ctx, run, ib, n_steps);
     } else {
       StepGraph sg;
-      if (step_graph_usable(ctx, n_steps)) (void)build_step_graph(ctx, ib, sg);
-      run_generic_steps(ctx, ib, n_steps, &sg);
+      if (step_graph_usable(ctx, run, n_steps)) (void)build_step_graph(ctx, run, ib, sg);
+      run_generic_steps(ctx, run, ib, n_steps, &sg);
       HIPCK(hipStreamSynchronize(ctx->stream));  // the graph is destroyed at the end of this scope
     }
   }
@@ -2031,7 +2030,7 @@ void launch_iwls_ljit(rmhmc_ctx* ctx, Group& g, const double* Ginv, double* out)
 // decision
 void launch_iwls_iter(rmhmc_ctx* ctx, Group& g, const IwlsParams& p) {
   SMALL(ctx, g, "iwls", k_iwls_begin, ctx->D, ctx->DP, g.ch, p);
-  eval_point_phases(ctx, g, false, 1);
+  eval_point_phases(ctx, g, nullptr, 1);
   if (p.compat) {
     launch_iwls_ljit(ctx, g, g.ch.trj.Ginv, p.lq_trj);
     launch(ctx, "iwls_sat", [&](hipStream_t st) {

@@ -418,6 +418,19 @@ def option_toggles(ctx, spec, inp):
     assert ctx.options() == defaults
 
 
+def other_params(ctx, spec, inp):
+    """the stepping entry points with run parameters the battery never uses: K = 1 and K = 2 (the two values at which the delta
+    assemblies of the int8 path switch), L = 1, another step size, a large chain offset"""
+    far = (1 << 40) + 12345
+    with np.errstate(all="ignore"):
+        for K in (1, 2):
+            ctx.sample(12, 3, L=1, eps=0.25, K=K, seed=61, chain_offset=far)
+            ctx.chains_init(seed=62, chain_offset=far, L=1, eps=0.25, K=K)
+            ctx.chains_run(10)
+            ctx.transition(inp["wt"], inp["z"], inp["ul"], inp["gd"], inp["ua"], L=1, eps=0.25, K=K)
+            ctx.leapfrog(inp["wl"], inp["pl"], 0.25, inp["dir"], inp["ns"], K)
+
+
 POLLUTERS = {"other_data_larger": other_data_larger, "other_data_smaller": other_data_smaller, "diverged": diverged,
              "other_samplers": other_samplers, "other_run": other_run,
-             "failed_calls": failed_calls, "option_toggles": option_toggles}
+             "failed_calls": failed_calls, "option_toggles": option_toggles, "other_params": other_params}

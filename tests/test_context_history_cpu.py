@@ -13,7 +13,7 @@ import context_history as H  # noqa: E402
 
 # the fused, medium and generic shapes of the GPU file (the oracle has one path only; a battery takes it well under a second at these)
 CPU_PATHS = {k: H.PATHS[k] for k in ("fused", "medium", "generic")}
-CPU_POLLUTERS = ["other_data_larger", "other_data_smaller", "diverged", "other_samplers", "other_run", "failed_calls"]
+CPU_POLLUTERS = ["other_data_larger", "other_data_smaller", "diverged", "other_samplers", "other_run", "failed_calls", "other_params"]
 _fresh = {}
 
 

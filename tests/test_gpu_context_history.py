@@ -1,8 +1,8 @@
 """A context's results must not depend on its earlier calls.
 
 An rmhmc_ctx is long-lived: about forty device buffers (c-tile cache and stale list, int8 slice planes with their per-chain exponents,
-partial planes shared by the fp64 row split and the int8 k split, the work-sorted sampler's permutation ...) and a dozen host-side mode
-fields.  Every entry point is supposed to overwrite or reset what it reads; INTEGRATION.md promises that one context serves RMHMC, HMC,
+partial planes shared by the fp64 row split and the int8 k split, the work-sorted sampler's permutation ...) and a few host-side
+fields (lists them).  Every entry point is supposed to overwrite or reset what it reads; INTEGRATION.md promises that one context serves RMHMC, HMC,
 mMALA, AMH, IWLS and Gibbs calls in any order.  Here one battery of calls with fixed inputs (tests/helpers/context_history.py) runs on
 every stepping path
 
