@@ -98,6 +98,23 @@ typedef struct rmhmc_ctx rmhmc_ctx;
 #define RMHMC_ST_NONFINITE (1 << 1)    /* w or p became inf/NaN                 */
 #define RMHMC_ST_GUARD_P (1 << 2)      /* momentum guard fired (rmhmc.py:81)    */
 #define RMHMC_ST_GUARD_W (1 << 3)      /* position guard fired (rmhmc.py:125)   */
+/* NOT_PD and NONFINITE are the FAILURE bits, GUARD_P and GUARD_W report that one of the reference's RENORMALIZE guards
+ * (RMHMC_FLAG_GUARDS) rescaled the chain, which then carries on as an ordinary one.  A chain FAILS when its position is NaN or inf
+ * on entry, when its trajectory overflows, or when a Cholesky pivot along it is <= 0 or NaN.  What every entry point guarantees
+ * for such a chain, on every stepping path (where the reference raises LinAlgError or carries NaN along):
+ *   - the proposal is REJECTED: accepted_out = 0, the accept counters do not move;
+ *   - its STATE IS UNTOUCHED: rmhmc_transition returns w as it was given, bit for bit (a NaN or inf input included), the bulk
+ *     samplers repeat the previous state in samples_out; the chain stays in the run and draws its next proposal as usual, so a
+ *     chain whose start fails from every momentum returns theta0 in every sample;
+ *   - status_out carries AT LEAST ONE failure bit.  A position that is NaN or inf on entry raises both.  Which of the two an
+ *     overflow raises first depends on the order of the arithmetic (exp(f) overflows into G before or after a pivot is tested),
+ *     so the library and the oracle may differ there in WHICH failure bit is set, never in whether one is; the guard bits are
+ *     exact;
+ *   - its NEIGHBOURS ARE UNAFFECTED: every output of every other chain of the batch is bit-identical to a call in which the
+ *     failing chain was well behaved, on the paths where chains share a wavefront, an MFMA tile or a batch-wide slice count too.
+ * rmhmc_leapfrog reports the same bits; its w, p and half_logdet_out of a failed chain are unspecified (NaN as a rule).
+ * nsteps_out, H_cur_out and the *_prop_out of a failed chain are what the trajectory produced up to the failure (NaN as a rule).
+ * tests/test_gpu_failing_chains.py pins all of this on every path.                                                             */
 
 const char *rmhmc_version(void);
 

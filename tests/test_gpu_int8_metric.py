@@ -91,18 +91,29 @@ def test_one_leapfrog_step_theta_and_logdet_vs_reference(hip, name):
     assert abs(2 * hld1[0] - logdet_ref) < 1e-9 * max(1, abs(logdet_ref))
 
 
-def test_nonfinite_chain_is_rejected_and_isolated(hip):
-    """A NaN position makes v non-finite: that chain's G must come out NaN (rejected, flagged), its neighbours in the same
-    128-chain tile must be bit-identical to a run without it."""
-    M, D, n = 400, 20, 140
+@pytest.mark.parametrize("M,D,n,one_launch", [(400, 40, 140, False), (400, 20, 140, True)])
+def test_nonfinite_chain_is_rejected_and_isolated(hip, M, D, n, one_launch):
+    """A NaN position makes v non-finite: that chain's G must come out NaN (rejected, flagged), its neighbours must be bit-identical to
+    a run without it.  D = 40: the int8 assembly steps the chains, and the NaN chain shares a 128-chain tile with 127 others.  D = 20:
+    a shape of the one-launch medium step, which steps with k_step_medium whatever the int8 flag says (the int8 kernels see the NaN
+    chain at the evaluation points only)."""
     XX, t = synthetic_logreg(M, D, 6)
     rs = np.random.RandomState(2)
     w = 0.05 * rs.randn(n, D); z = rs.randn(n, D)
     ul = rs.rand(n); gd = rs.randn(n); ua = rs.rand(n)
     wbad = w.copy(); wbad[17, 3] = np.nan
     fl = _capi.int8_metric_flags(6)
-    good = _run(hip, M, D, n, XX, t, lambda c: c.transition(w, z, ul, gd, ua, L=3, eps=0.5, K=4), fl)
-    bad = _run(hip, M, D, n, XX, t, lambda c: c.transition(wbad, z, ul, gd, ua, L=3, eps=0.5, K=4), fl)
+
+    def fn(w0):
+        def run(ctx):
+            info = ctx.device_info().split("; options:")[0]
+            assert "int8 metric path 6 slices: active" in info and "fused small-problem path" not in info, info
+            assert ("one-launch step" in info) == one_launch, info
+            return ctx.transition(w0, z, ul, gd, ua, L=3, eps=0.5, K=4)
+        return run
+
+    good = _run(hip, M, D, n, XX, t, fn(w), fl)
+    bad = _run(hip, M, D, n, XX, t, fn(wbad), fl)
     assert bad["accepted"][17] == 0 and bad["status"][17] != 0
     keep = np.arange(n) != 17
     for k in ("w", "w_prop", "H_prop", "accepted"):
