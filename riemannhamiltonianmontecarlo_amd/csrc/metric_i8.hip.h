@@ -168,7 +168,27 @@ constexpr int i8_nbuf() {
   return (I8_NBUF4 && S <= 4 && 2 * ROWS == NU * NT && 4 * S * ROWS * 32 <= 140 * 1024) ? 4 : 3;
 }
 
+// the accumulators of a wave tile to the epilogue: epi(row, col, value)
 // RAW: the epilogue gets the int32 accumulators themselves, epi(row, col, g, acc_g), instead of their fp64 combination.
+template <int S, int TN, int BN, bool RAW, class Epilogue>
+__device__ __forceinline__ void i8_tile_epilogue(const i16v (&acc)[S][2][TN], int cb, int pb, int wm, int wn, int lane, Epilogue&& epi) {
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < TN; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = cb * I8_BM + wm * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int col = pb * BN + wn * 32 * TN + b * 32 + (lane & 31);
+        if constexpr (RAW) {
+#pragma unroll
+          for (int g = 0; g < S; ++g) epi(row, col, g, acc[g][a][b][r]);
+        } else {
+          epi(row, col, i8_combine<S>([&](int g) { return acc[g][a][b][r]; }));
+        }
+      }
+}
+
 template <int S, int WN, int TN, int PIN, bool RAW = false, class Epilogue>
 __device__ __forceinline__ void gemm_i8_tile(const int8_t* __restrict__ Vs, const int8_t* __restrict__ Zs, int nCp, int NPp, int nks_total, int nks,
                                              int cb, int pb, int rows_real, int cols_real, Epilogue&& epi) {
@@ -353,38 +373,183 @@ __device__ __forceinline__ void gemm_i8_tile(const int8_t* __restrict__ Vs, cons
     cur = nxt;
   }
   if (ALLON) wait_vmcnt<0>();  // (the re-fetches of the last two stages: no LDS-DMA write may outlive the workgroup)
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < TN; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = cb * BM + wm * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        const int col = pb * BN + wn * 32 * TN + b * 32 + (lane & 31);
-        if constexpr (RAW) {
-#pragma unroll
-          for (int g = 0; g < S; ++g) epi(row, col, g, acc[g][a][b][r]);
-        } else {
-          epi(row, col, i8_combine<S>([&](int g) { return acc[g][a][b][r]; }));
-        }
-      }
+  i8_tile_epilogue<S, TN, BN, RAW>(acc, cb, pb, wm, wn, lane, epi);
 }
 
-template <int S, int WN, int TN>
-constexpr int i8_lds_bytes() { return i8_nbuf<S, WN, TN>() * S * (I8_BM + 32 * TN * WN) * I8_ROWB; }
+
+// ---------------------------------------------------------------------------------------------
+// ZDIRECT form of the 8-wave tile at S = 4 (option i8_zdirect; WN = 4, TN = 1): the Z (B) operand never touches LDS.
+// A wave's B fragments of one slice and stage - 32 pairs x 32 bytes - are 1 KB contiguous in the stage-major Zs and already in fragment
+// order (lane & 31 = pair, lane >> 5 = 16-byte half), so one global_load_dwordx4 per slice and stage brings them straight into the
+// fragment registers.  LDS then carries the V (A) part alone: a stage is S x 128 rows x 32 B = 16 KB of LDS-DMA and 64 KB of fragment
+// reads per workgroup, where the LDS form moves 32 + 96 KB for the same 20 MFMAs per wave.
+//   ring      P stages ahead for both operands (I8_ZRING): P + 1 LDS buffers of the V stage, P register sets fb[P][S] of 16 bytes per lane
+//             (the S' = 4 branch has the registers: 128 accumulators against the 192 of S = 6).  The loop is unrolled P times so
+//             that every ring index is a constant.
+//   LDS-DMA   256 units of 16 bytes per slice and 512 threads: the waves 0-3 stage the even slices, the waves 4-7 the odd ones, every
+//             thread one unit of every second slice, unconditionally (ALLON above; past the end the last stage is fetched again).
+//   issue     stage ks issues the loads of stage ks + P behind its MFMAs, one Z slice per product group: group i is the last to
+//             use fb[S-1-i], which is then re-loaded in place.  The S/2 DMA loads go in front of the first groups.  Per wave and
+//             stage that is Q = S + S/2 vector-memory instructions in a fixed order, DMA and register loads in ONE vmcnt queue that
+//             returns in order.
+//   waits     at the end of stage ks: vmcnt((P-1) Q) - everything but the loads issued in the last P - 1 stages has landed, i.e. all
+//             of stage ks + 1: its fb registers (named on the wait, so that no MFMA is hoisted above it; the Z loads need no barrier)
+//             and this wave's share of its V stage, which is read after the barrier that follows (one barrier after the wait that
+//             retired it).  Buffer of stage ks + P = buffer of stage ks - 1: free since the barrier that ended that stage.
+//   the end   one vmcnt(0) named on every fb register: no LDS-DMA write outlives the workgroup and no register load the registers'
+//             last use.
+// Waves whose tile is all padding stage their V units and skip everything else.  The integer sums are those of gemm_i8_tile in
+// another association: bit-identical results.
+// ---------------------------------------------------------------------------------------------
+#ifndef I8_ZRING
+#define I8_ZRING 3   // stages ahead, as the LDS form at S = 4; 2, 3 and 4 time alike on the tile alone (tools/i8_gemm_probe 4, profiles/i8_zdirect_ab.txt)
+#endif
+constexpr bool i8_zdirect_tile(int S, int WN, int TN) { return S == 4 && WN == 4 && TN == 1; }
+template <int S, int P>
+constexpr int i8_zd_lds_bytes() { return (P + 1) * S * I8_BM * I8_ROWB; }
+
+__device__ __forceinline__ void gbl_load_b128(i4v& r, unsigned off, const void* base) {  // wave-uniform base + 32-bit lane offset
+  asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(r) : "v"(off), "s"(base) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void wait_vmcnt(i4v& a, i4v& b, i4v& c, i4v& d) {
+  static_assert(N >= 0 && N < 64, "vmcnt immediate");
+  asm volatile("s_waitcnt vmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N) : "memory");
+}
+
+template <int S, int P, class Epilogue>
+__device__ __forceinline__ void gemm_i8_tile_zd(const int8_t* __restrict__ Vs, const int8_t* __restrict__ Zs, int nCp, int NPp, int nks_total, int nks,
+                                                int cb, int pb, int rows_real, int cols_real, Epilogue&& epi) {
+  constexpr int BM = I8_BM, BN = 128, NBUF = P + 1;
+  constexpr int SLICE = BM * I8_ROWB, STAGE = S * SLICE;  // LDS bytes of one slice / one stage of V
+  constexpr int ND = S / 2, Q = S + ND;                    // LDS-DMA loads, all loads per wave and stage
+  static_assert(S == 4, "four fb registers per ring slot are named on the waits");
+  static_assert(P >= 2 && (P - 1) * Q < 64, "vmcnt immediate");
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int wm = wave & 1, wn = wave >> 1;
+  const size_t strideV = (size_t)nks_total * nCp * 32, strideZ = (size_t)nks_total * NPp * 32;
+  const size_t stepV = (size_t)nCp * 32, stepZ = (size_t)NPp * 32;
+  // LDS-DMA: unit u of the slices sp, sp + 2, ..; the unit stored at LDS slot u holds the logical half (u & 1) ^ swizzle bit (i8_lds_off)
+  const int sp = wave >> 2, u = t & 255, urow = u >> 1;
+  const int8_t* const va = Vs + ((size_t)cb * BM) * 32 + sp * strideV;                    // wave-uniform
+  const unsigned goff = (unsigned)(urow * 32 + (((u & 1) ^ ((urow >> 3) & 1)) << 4));     // per lane
+  const int lbase = sp * SLICE + (wave & 3) * 64 * 16;                                    // wave-uniform: (u & ~63) * 16 inside slice sp
+  auto dma = [&](int ks, int buf, int q) {  // slice sp + 2 q of stage ks
+    __builtin_amdgcn_global_load_lds((gbl_ptr_t)(va + (2 * q * strideV + (size_t)ks * stepV) + goff),
+                                     (lds_ptr_t)(lds + buf * STAGE + 2 * q * SLICE + lbase), 16, 0, 0);
+  };
+  // Z: the wave's 32 pairs, slice j of stage ks, in fragment order
+  const int8_t* const zw = Zs + ((size_t)pb * BN + wn * 32) * 32;                         // wave-uniform
+  const unsigned zoff = (unsigned)((lane & 31) * 32 + (lane >> 5) * 16);
+  auto zld = [&](i4v& r, int ks, int j) { gbl_load_b128(r, zoff, zw + (j * strideZ + (size_t)ks * stepZ)); };
+
+  i16v acc[S][2][1];
+#pragma unroll
+  for (int g = 0; g < S; ++g)
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[g][a][0][r] = 0;
+  const bool work = wm * 64 < rows_real && wn * 32 < cols_real;  // wave-uniform
+  if (!work) {  // V units only: ND loads per stage
+#pragma unroll
+    for (int d = 0; d < P; ++d)
+#pragma unroll
+      for (int q = 0; q < ND; ++q) dma(min(d, nks - 1), d, q);
+    wait_vmcnt<(P - 1) * ND>();
+    __builtin_amdgcn_s_barrier();
+    int wr = NBUF - 1;  // buffer of stage ks - 1
+    for (int ks = 0; ks < nks; ++ks) {
+#pragma unroll
+      for (int q = 0; q < ND; ++q) dma(min(ks + P, nks - 1), wr, q);
+      wait_vmcnt<(P - 1) * ND>();
+      __builtin_amdgcn_s_barrier();
+      wr = wr + 1 >= NBUF ? 0 : wr + 1;
+    }
+    wait_vmcnt<0>();
+  } else {
+    i4v fb[P][S], fa[2][2];
+#pragma unroll
+    for (int d = 0; d < P; ++d)
+#pragma unroll
+      for (int j = 0; j < S; ++j) fb[d][j] = i4v{0, 0, 0, 0};
+    // the first P stages, in the order of the loop: DMA q in front of slice S-1-q, then the remaining slices
+#pragma unroll
+    for (int d = 0; d < P; ++d) {
+      const int kd = min(d, nks - 1);
+#pragma unroll
+      for (int i = 0; i < S; ++i) {
+        if (i < ND) dma(kd, d, i);
+        zld(fb[d][S - 1 - i], kd, S - 1 - i);
+      }
+    }
+    wait_vmcnt<(P - 1) * Q>(fb[0][0], fb[0][1], fb[0][2], fb[0][3]);
+    __builtin_amdgcn_s_barrier();
+    const int fragA = i8_lds_off(wm * 64 + (lane & 31), lane >> 5);
+    const unsigned a0 = (unsigned)(size_t)(lds_ptr_t)(lds) + fragA;
+    int cur = 0;
+    auto stage = [&]<int R>(std::integral_constant<int, R>, int ks) {
+      const int wr = cur == 0 ? NBUF - 1 : cur - 1;  // the buffer of stage ks - 1, free since the last barrier
+      const int kpre = min(ks + P, nks - 1);         // (clamped, always issued)
+      const unsigned aA = a0 + cur * STAGE;
+      fa[0][0] = lds_read_b128<0>(aA);
+      fa[0][1] = lds_read_b128<32 * I8_ROWB>(aA);
+      [&]<int... I>(std::integer_sequence<int, I...>) {
+        ([&] {
+          constexpr int i = I;
+          if constexpr (i + 1 < S) {
+            fa[(i + 1) & 1][0] = lds_read_b128<(i + 1) * SLICE>(aA);
+            fa[(i + 1) & 1][1] = lds_read_b128<(i + 1) * SLICE + 32 * I8_ROWB>(aA);
+          }
+          if constexpr (i < ND) dma(kpre, wr, i);
+          wait_lgkm<(i + 1 < S) ? 2 : 0>(fa[i & 1][0], fa[i & 1][1]);
+#pragma unroll
+          for (int j = S - 1 - i; j >= 0; --j) {
+            acc[i + j][0][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[i & 1][0], fb[R][j], acc[i + j][0][0], 0, 0, 0);
+            acc[i + j][1][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[i & 1][1], fb[R][j], acc[i + j][1][0], 0, 0, 0);
+          }
+          __builtin_amdgcn_sched_barrier(0);  // (the re-load below stays behind the last MFMA that reads the old fragment)
+          zld(fb[R][S - 1 - i], kpre, S - 1 - i);
+        }(), ...);
+      }(std::make_integer_sequence<int, S>{});
+      constexpr int R1 = (R + 1) % P;
+      wait_vmcnt<(P - 1) * Q>(fb[R1][0], fb[R1][1], fb[R1][2], fb[R1][3]);
+      __builtin_amdgcn_s_barrier();
+      cur = cur + 1 >= NBUF ? 0 : cur + 1;
+    };
+    for (int ks = 0; ks < nks; ks += P) {
+      bool more = true;
+      [&]<int... R>(std::integer_sequence<int, R...>) {
+        ((more = more && ks + R < nks, more ? stage(std::integral_constant<int, R>{}, ks + R) : (void)0), ...);
+      }(std::make_integer_sequence<int, P>{});
+    }
+#pragma unroll
+    for (int d = 0; d < P; ++d) wait_vmcnt<0>(fb[d][0], fb[d][1], fb[d][2], fb[d][3]);
+  }
+  i8_tile_epilogue<S, 1, BN, false>(acc, cb, pb, wm, wn, lane, epi);
+}
+
+template <int S, int WN, int TN, bool ZD = false>
+constexpr int i8_lds_bytes() {
+  if (ZD && i8_zdirect_tile(S, WN, TN)) return i8_zd_lds_bytes<S, I8_ZRING>();
+  return i8_nbuf<S, WN, TN>() * S * (I8_BM + 32 * TN * WN) * I8_ROWB;
+}
 
 // probe / unit-test form (tools/i8_gemm_probe.hip): C[row][col] = sum_g acc_g 2^(-8g)
-template <int S, int WN, int TN, int PIN>
+// ZP > 0: the ZDIRECT form with a ring of ZP stages
+template <int S, int WN, int TN, int PIN, int ZP = 0>
 __global__ __launch_bounds__(128 * WN) __attribute__((amdgpu_waves_per_eu(WN >= 2 ? WN / 2 : 1, WN >= 4 ? WN / 2 : 2))) void k_gemm_i8_probe(const int8_t* __restrict__ Vs, const int8_t* __restrict__ Zs, int nCp, int NPp, int nks,
                                                             int nC, int NP, double* __restrict__ C) {
   int cb, pb;
   if (!i8_tile_of_block(blockIdx.x, nCp / I8_BM, NPp / (32 * TN * WN), cb, pb)) return;
-  gemm_i8_tile<S, WN, TN, PIN>(Vs, Zs, nCp, NPp, nks, nks, cb, pb, nC - cb * I8_BM, NP - pb * 32 * TN * WN,
-                          [&](int row, int col, double val) {
+  auto epi = [&](int row, int col, double val) {
 #ifdef I8_PROBE_NOSTORE  // (timing only: the epilogue's conversions stay, its stores go)
-                            if (val == 1.2345e300)
+    if (val == 1.2345e300)
 #endif
-                            C[(size_t)row * NPp + col] = val; });
+    C[(size_t)row * NPp + col] = val; };
+  if constexpr (ZP > 0) gemm_i8_tile_zd<S, ZP>(Vs, Zs, nCp, NPp, nks, nks, cb, pb, nC - cb * I8_BM, NP - pb * 32 * TN * WN, epi);
+  else gemm_i8_tile<S, WN, TN, PIN>(Vs, Zs, nCp, NPp, nks, nks, cb, pb, nC - cb * I8_BM, NP - pb * 32 * TN * WN, epi);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -612,7 +777,7 @@ __device__ __forceinline__ bool I8Delta::skip() const {
 // Cholesky kernels never read above the diagonal; rmhmc_metric mirrors it on the host for G_out)
 // (waves per SIMD stated explicitly: with 4 waves per workgroup the compiler otherwise budgets 256 registers and shuttles
 // accumulators through AGPR copies)
-template <int S, int WN, int TN>
+template <int S, int WN, int TN, bool ZD = false>
 __device__ __forceinline__ void assemble_i8_body(const int8_t* __restrict__ Vs, const int8_t* __restrict__ Zs, int nCp, int nks_total,
                                                  int ks0, int nk, int accumulate, const I8Pairs& pr, int n_chains, const int* __restrict__ phase,
                                                  const int* __restrict__ vbad, int DP, double inv_alpha, double* __restrict__ Gq,
@@ -649,8 +814,7 @@ __device__ __forceinline__ void assemble_i8_body(const int8_t* __restrict__ Vs, 
     }
   }
   __syncthreads();
-  gemm_i8_tile<S, WN, TN, (WN == 4)>(Vs + (size_t)kb * nCp * 32, Zs + (size_t)kb * pr.NPp * 32, nCp, pr.NPp, nks_total, kn, cb, pb,
-                                     n_chains - cb * I8_BM, pr.NP - pb * 32 * TN * WN, [&](int c, int p, double val) {
+  auto epi = [&](int c, int p, double val) {
     const int ci = c - cb * I8_BM, pj = p - pb * BN;
     const int off = s_poff[pj];
     const double ps = s_pscale[pj];
@@ -663,15 +827,22 @@ __device__ __forceinline__ void assemble_i8_body(const int8_t* __restrict__ Vs, 
     else if ((accumulate & 2) && s_coff[ci] != 3) g += dl.Gbase ? dl.Gbase[(size_t)min(c, n_chains - 1) * DP * DP + max(off, 0)] : *gp;
     else if (ps < 0.0 && first) g += inv_alpha;
     if (ok) *gp = g;
-  });
+  };
+  if constexpr (ZD && i8_zdirect_tile(S, WN, TN))
+    gemm_i8_tile_zd<S, I8_ZRING>(Vs + (size_t)kb * nCp * 32, Zs + (size_t)kb * pr.NPp * 32, nCp, pr.NPp, nks_total, kn, cb, pb, n_chains - cb * I8_BM,
+                                 pr.NP - pb * 32 * TN * WN, epi);
+  else
+    gemm_i8_tile<S, WN, TN, (WN == 4)>(Vs + (size_t)kb * nCp * 32, Zs + (size_t)kb * pr.NPp * 32, nCp, pr.NPp, nks_total, kn, cb, pb,
+                                       n_chains - cb * I8_BM, pr.NP - pb * 32 * TN * WN, epi);
 }
-template <int S, int WN, int TN>
+// ZD (option i8_zdirect): the S = 4 tile in its ZDIRECT form (gemm_i8_tile_zd); every other slice count is the same code either way
+template <int S, int WN, int TN, bool ZD = false>
 __global__ __launch_bounds__(128 * WN) __attribute__((amdgpu_waves_per_eu(WN / 2, WN / 2))) void k_assemble_i8(const int8_t* __restrict__ Vs, const int8_t* __restrict__ Zs, int nCp, int nks_total,
                                                           int ks0, int nk, int accumulate, I8Pairs pr, int n_chains, const int* __restrict__ phase,
                                                           const int* __restrict__ vbad, int DP, double inv_alpha, double* __restrict__ Gq,
                                                           size_t plane_stride, const int* __restrict__ vexp, int npb, I8Delta dl) {
   if (dl.skip()) return;
-  assemble_i8_body<S, WN, TN>(Vs, Zs, nCp, nks_total, ks0, nk, accumulate, pr, n_chains, phase, vbad, DP, inv_alpha, Gq, plane_stride, vexp, npb, dl);
+  assemble_i8_body<S, WN, TN, ZD>(Vs, Zs, nCp, nks_total, ks0, nk, accumulate, pr, n_chains, phase, vbad, DP, inv_alpha, Gq, plane_stride, vexp, npb, dl);
 }
 // Delta assembly, ONE launch for whatever the difference needs (it used to be three - the 6-, 5- and 4-slice instantiations, two of which
 // looked at *dsel and returned: ~4.6 us each, twelve of them per leapfrog step with the tail kernels): the kernel reads the maximum the row
@@ -686,7 +857,7 @@ __device__ __forceinline__ int i8_delta_pick(const I8Delta& dl, int seff) {
 __device__ __forceinline__ void i8_delta_count(const I8Delta& dl, int seff, int Sp) {
   if (dl.count && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(dl.count + 3 * (6 - seff) + (Sp - 4), 1ull);
 }
-template <int WN, int TN>
+template <int WN, int TN, bool ZD = false>
 __global__ __launch_bounds__(128 * WN) __attribute__((amdgpu_waves_per_eu(WN / 2, WN / 2))) void k_assemble_i8_sel(const int8_t* __restrict__ Vs, size_t vplane, int seff, const int8_t* __restrict__ Zs, int nCp, int nks_total,
                                                           int ks0, int nk, int accumulate, I8Pairs pr, int n_chains, const int* __restrict__ phase,
                                                           const int* __restrict__ vbad, int DP, double inv_alpha, double* __restrict__ Gq,
@@ -697,7 +868,7 @@ __global__ __launch_bounds__(128 * WN) __attribute__((amdgpu_waves_per_eu(WN / 2
   Vs += (size_t)(seff - Sp) * vplane;
   if (Sp == 6) assemble_i8_body<6, WN, TN>(Vs, Zs, nCp, nks_total, ks0, nk, accumulate, pr, n_chains, phase, vbad, DP, inv_alpha, Gq, plane_stride, vexp, npb, dl);
   else if (Sp == 5) assemble_i8_body<5, WN, TN>(Vs, Zs, nCp, nks_total, ks0, nk, accumulate, pr, n_chains, phase, vbad, DP, inv_alpha, Gq, plane_stride, vexp, npb, dl);
-  else assemble_i8_body<4, WN, TN>(Vs, Zs, nCp, nks_total, ks0, nk, accumulate, pr, n_chains, phase, vbad, DP, inv_alpha, Gq, plane_stride, vexp, npb, dl);
+  else assemble_i8_body<4, WN, TN, ZD>(Vs, Zs, nCp, nks_total, ks0, nk, accumulate, pr, n_chains, phase, vbad, DP, inv_alpha, Gq, plane_stride, vexp, npb, dl);
 }
 
 // The pairs beyond the last FULL block of 32 WN pairs (D = 64: 2080 = 16 x 128 + 32) as tiles of their own.  In the main launch
@@ -929,7 +1100,7 @@ __global__ __launch_bounds__(256) void k_qsplit(const double* __restrict__ Ginv,
 }
 
 // R[c][n] = c_n (x_n' G^-1 x_n)   (mulc = 0: h_n alone, the large-D trace kernel multiplies by c_n itself)
-template <int S, int WN, int TN>
+template <int S, int WN, int TN, bool ZD = false>
 __global__ __launch_bounds__(128 * WN) __attribute__((amdgpu_waves_per_eu(WN / 2, WN / 2))) void k_leverage_i8(
     const int8_t* __restrict__ Qs, const int8_t* __restrict__ Zt, int nCp, int NRp, int nkp_total, int kp0, int nk, int accumulate, int mulc,
     int n_chains, int Mp, const int* __restrict__ phase, const double* __restrict__ qscale, const double* __restrict__ zscale,
@@ -955,8 +1126,7 @@ __global__ __launch_bounds__(128 * WN) __attribute__((amdgpu_waves_per_eu(WN / 2
     }
   }
   __syncthreads();
-  gemm_i8_tile<S, WN, TN, (WN == 4)>(Qs + (size_t)kb * nCp * 32, Zt + (size_t)kb * NRp * 32, nCp, NRp, nkp_total, kn, cb, rb,
-                                     n_chains - cb * I8_BM, Mp - rb * 32 * TN * WN, [&](int c, int n, double val) {
+  auto epi = [&](int c, int n, double val) {
     const int ci = c - cb * I8_BM;
     const bool ok = s_ok[ci] != 0 && n < Mp;
     const size_t o = (size_t)min(c, n_chains - 1) * Mp + min(n, Mp - 1);  // (always a valid address: the loads below are unconditional)
@@ -964,5 +1134,11 @@ __global__ __launch_bounds__(128 * WN) __attribute__((amdgpu_waves_per_eu(WN / 2
     if (mulc) r *= crow[o];
     if (accumulate) r += Rout[o];
     if (ok) Rout[o] = r;
-  });
+  };
+  if constexpr (ZD && i8_zdirect_tile(S, WN, TN))
+    gemm_i8_tile_zd<S, I8_ZRING>(Qs + (size_t)kb * nCp * 32, Zt + (size_t)kb * NRp * 32, nCp, NRp, nkp_total, kn, cb, rb, n_chains - cb * I8_BM,
+                                 Mp - rb * 32 * TN * WN, epi);
+  else
+    gemm_i8_tile<S, WN, TN, (WN == 4)>(Qs + (size_t)kb * nCp * 32, Zt + (size_t)kb * NRp * 32, nCp, NRp, nkp_total, kn, cb, rb,
+                                       n_chains - cb * I8_BM, Mp - rb * 32 * TN * WN, epi);
 }

@@ -104,7 +104,8 @@ struct rmhmc_ctx : Plan {
   int i8_inner_drop = 1;     // inner assemblies from S-1 slices (launch_assemble; RMHMC_FLAG_INT8_INNER_FULL: off)
   // (options i8_delta / i8_delta_inner: G at the end of a leapfrog step, and the second position iterate, as the previous iterate's G + the
   //  assembly of the v differences; i8_force_rebase: tests treat every chain as if its v exponent had changed; i8_tail: ragged last pair
-  //  block as tiles of its own: -1 when it pays (launch_assemble_i8_t), 0 never, 1 always)
+  //  block as tiles of its own: -1 when it pays (launch_assemble_i8_t), 0 never, 1 always; i8_zdirect: the 4-slice tiles in their
+  //  ZDIRECT form, chosen at launch - both forms are built)
   int8_t* d_Zs = nullptr;
   int* d_ze = nullptr;
   int8_t* d_Zt = nullptr;   // leverage pass: x_a x_b sliced per data row, [S][nkp][NRp][32]
@@ -293,14 +294,20 @@ void launch_assemble_i8_t(rmhmc_ctx* ctx, Group& g, const double* v, hipStream_t
                        ctx->D, ctx->DP, ctx->dd.inv_alpha, g.ch.Gq, g.vexp, VDelta{});
     return;
   }
-  constexpr int lds = i8_lds_bytes<S, WN, TN>();
   const I8Geometry t = i8_geometry(*ctx, g.nCp, WN, TN, WN == 4);  // (k_assemble_i8_tail pairs with the 8-wave tile)
+  // option i8_zdirect: the ZDIRECT form of the tile where there is one (S = 4); both forms are in the library
+  auto main_tiles = [&](dim3 grid, auto... args) {
+    if (i8_zdirect_tile(S, WN, TN) && ctx->opt.i8_zdirect)
+      hipLaunchKernelGGL((k_assemble_i8<S, WN, TN, true>), grid, dim3(128 * WN), (i8_lds_bytes<S, WN, TN, true>()), st, args...);
+    else
+      hipLaunchKernelGGL((k_assemble_i8<S, WN, TN>), grid, dim3(128 * WN), (i8_lds_bytes<S, WN, TN>()), st, args...);
+  };
   if (ctx->ksplit_a > 1) {  // small batch: too few tiles to fill the chip, so the k range is cut into planes that are summed afterwards
     // (a plan with k pieces has no tail accumulators: the main tiles are all pair blocks)
     const size_t plane = (size_t)g.n * ctx->DP * ctx->DP;
-    hipLaunchKernelGGL((k_assemble_i8<S, WN, TN>), dim3(t.nblk_main, (unsigned)ctx->ksplit_a), dim3(128 * WN), lds, st, g.Vs, ctx->d_Zs, g.nCp, ctx->i8_nks,
-                       0, ctx->i8_nks, 0, ctx->pairs, g.n, g.ch.phase, g.vbad, ctx->DP, ctx->dd.inv_alpha, g.Gpart, plane, g.vexp, t.npb,
-                       I8Delta{nullptr, nullptr, 1.0, 0, 0, nullptr});
+    main_tiles(dim3(t.nblk_main, (unsigned)ctx->ksplit_a), (const int8_t*)g.Vs, (const int8_t*)ctx->d_Zs, g.nCp, ctx->i8_nks,
+               0, ctx->i8_nks, 0, ctx->pairs, g.n, (const int*)g.ch.phase, (const int*)g.vbad, ctx->DP, ctx->dd.inv_alpha, g.Gpart, plane, (const int*)g.vexp, t.npb,
+               I8Delta{nullptr, nullptr, 1.0, 0, 0, nullptr});
     hipLaunchKernelGGL(k_sum_planes, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, st, g.ch.Gq, g.Gpart, ctx->ksplit_a, plane, plane);
     return;
   }
@@ -308,8 +315,8 @@ void launch_assemble_i8_t(rmhmc_ctx* ctx, Group& g, const double* v, hipStream_t
   for (int ks0 = 0; ks0 < ctx->i8_nks; ks0 += ctx->i8_chunk) {
     const int nk = std::min(ctx->i8_chunk, ctx->i8_nks - ks0);
     if (t.nblk_main)
-      hipLaunchKernelGGL((k_assemble_i8<S, WN, TN>), dim3(t.nblk_main), dim3(128 * WN), lds, st, Vs, ctx->d_Zs, g.nCp,
-                         ctx->i8_nks, ks0, nk, (ks0 > 0 ? 1 : 0) | acc0, ctx->pairs, g.n, g.ch.phase, g.vbad, ctx->DP, ctx->dd.inv_alpha, g.ch.Gq, (size_t)0, vexp, t.npb, dl);
+      main_tiles(dim3(t.nblk_main), Vs, (const int8_t*)ctx->d_Zs, g.nCp, ctx->i8_nks, ks0, nk, (ks0 > 0 ? 1 : 0) | acc0, ctx->pairs, g.n,
+                 (const int*)g.ch.phase, (const int*)g.vbad, ctx->DP, ctx->dd.inv_alpha, g.ch.Gq, (size_t)0, vexp, t.npb, dl);
     if (t.tail) {
       const int pieces = i8_tail_pieces(*ctx, t, nk);
       hipLaunchKernelGGL((k_assemble_i8_tail<S>), dim3((unsigned)(t.nCB * t.ntail), (unsigned)pieces), dim3(128), (i8_lds_bytes<S, 1, 1>()), st, Vs, ctx->d_Zs,
@@ -333,12 +340,17 @@ void launch_assemble_i8_delta(rmhmc_ctx* ctx, Group& g, hipStream_t st, int seff
   // the assembly is counted once (g.dcount): by the first k piece's main launch, or by its tail launch when there are no main tiles
   I8Delta dlc = dl;
   dlc.count = g.dcount;
+  // option i8_zdirect picks the kernel whose S' = 4 branch is the ZDIRECT form; the 5- and 6-slice branches are the same code in both
+  auto main_tiles = [&](dim3 grid, auto... args) {
+    if (ctx->opt.i8_zdirect) hipLaunchKernelGGL((k_assemble_i8_sel<WN, TN, true>), grid, dim3(128 * WN), lds, st, args...);
+    else hipLaunchKernelGGL((k_assemble_i8_sel<WN, TN>), grid, dim3(128 * WN), lds, st, args...);
+  };
   for (int ks0 = 0; ks0 < ctx->i8_nks; ks0 += ctx->i8_chunk) {
     const int nk = std::min(ctx->i8_chunk, ctx->i8_nks - ks0);
     if (t.nblk_main)
-      hipLaunchKernelGGL((k_assemble_i8_sel<WN, TN>), dim3(t.nblk_main), dim3(128 * WN), lds, st, g.Vs, vplane, seff, ctx->d_Zs, g.nCp, ctx->i8_nks, ks0, nk,
-                         (ks0 > 0 ? 1 : 0) | 2, ctx->pairs, g.n, g.ch.phase, g.vbad, ctx->DP, ctx->dd.inv_alpha, g.ch.Gq, (size_t)0, g.vexp_d, t.npb,
-                         ks0 == 0 ? dlc : dl);
+      main_tiles(dim3(t.nblk_main), (const int8_t*)g.Vs, vplane, seff, (const int8_t*)ctx->d_Zs, g.nCp, ctx->i8_nks, ks0, nk, (ks0 > 0 ? 1 : 0) | 2, ctx->pairs,
+                 g.n, (const int*)g.ch.phase, (const int*)g.vbad, ctx->DP, ctx->dd.inv_alpha, g.ch.Gq, (size_t)0, (const int*)g.vexp_d, t.npb,
+                 ks0 == 0 ? dlc : dl);
     if (t.tail) {
       const int pieces = i8_tail_pieces(*ctx, t, nk);
       hipLaunchKernelGGL(k_assemble_i8_tail_sel, dim3((unsigned)(t.nCB * t.ntail), (unsigned)pieces), dim3(128), lds_t, st, g.Vs, vplane, seff, ctx->d_Zs,
@@ -357,20 +369,26 @@ void launch_leverage_i8_t(rmhmc_ctx* ctx, Group& g, hipStream_t st, int part) {
     return;
   }
   const int nCB = g.nCp / I8_BM, nRB = ctx->i8_NRp / (32 * TN * WN);
-  constexpr int lds = i8_lds_bytes<S, WN, TN>();
   const unsigned nblk = (unsigned)(nCB < 8 ? nCB * nRB : (nCB + 7) / 8 * 8 * nRB);
+  auto tiles = [&](dim3 grid, auto... args) {  // (option i8_zdirect, as in launch_assemble_i8_t)
+    if (i8_zdirect_tile(S, WN, TN) && ctx->opt.i8_zdirect)
+      hipLaunchKernelGGL((k_leverage_i8<S, WN, TN, true>), grid, dim3(128 * WN), (i8_lds_bytes<S, WN, TN, true>()), st, args...);
+    else
+      hipLaunchKernelGGL((k_leverage_i8<S, WN, TN>), grid, dim3(128 * WN), (i8_lds_bytes<S, WN, TN>()), st, args...);
+  };
   if (ctx->ksplit_l > 1) {
     const size_t plane = (size_t)g.n * ctx->Mp;
-    hipLaunchKernelGGL((k_leverage_i8<S, WN, TN>), dim3(nblk, (unsigned)ctx->ksplit_l), dim3(128 * WN), lds, st, g.Qs, ctx->d_Zt, g.nCp, ctx->i8_NRp,
-                       ctx->i8_nkp, 0, ctx->i8_nkp, 0, (ctx->big || g.ctile) ? 0 : 1, g.n, ctx->Mp, g.ch.phase, g.qscale, ctx->d_zscale, g.ch.rv2, g.Rpart, plane);
+    tiles(dim3(nblk, (unsigned)ctx->ksplit_l), (const int8_t*)g.Qs, (const int8_t*)ctx->d_Zt, g.nCp, ctx->i8_NRp, ctx->i8_nkp, 0, ctx->i8_nkp, 0,
+          (ctx->big || g.ctile) ? 0 : 1, g.n, ctx->Mp, (const int*)g.ch.phase, (const double*)g.qscale, (const double*)ctx->d_zscale,
+          (const double*)g.ch.rv2, g.Rpart, plane);
     hipLaunchKernelGGL(k_sum_planes, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, st, g.ch.rv0, g.Rpart, ctx->ksplit_l, plane, plane);
     return;
   }
   for (int kp0 = 0; kp0 < ctx->i8_nkp; kp0 += ctx->i8_chunk) {
     const int nk = std::min(ctx->i8_chunk, ctx->i8_nkp - kp0);
-    hipLaunchKernelGGL((k_leverage_i8<S, WN, TN>), dim3(nblk), dim3(128 * WN), lds, st, g.Qs, ctx->d_Zt, g.nCp,
-                       ctx->i8_NRp, ctx->i8_nkp, kp0, nk, kp0 > 0 ? 1 : 0, (ctx->big || g.ctile) ? 0 : 1, g.n, ctx->Mp, g.ch.phase, g.qscale, ctx->d_zscale,
-                       g.ch.rv2, g.ch.rv0, (size_t)0);
+    tiles(dim3(nblk), (const int8_t*)g.Qs, (const int8_t*)ctx->d_Zt, g.nCp, ctx->i8_NRp, ctx->i8_nkp, kp0, nk, kp0 > 0 ? 1 : 0,
+          (ctx->big || g.ctile) ? 0 : 1, g.n, ctx->Mp, (const int*)g.ch.phase, (const double*)g.qscale, (const double*)ctx->d_zscale,
+          (const double*)g.ch.rv2, g.ch.rv0, (size_t)0);
   }
 }
 // inner: an assembly whose G only steers a fixed-point iterate (the position iterations before the last, rmhmc.py:116-122).  With
@@ -934,11 +952,16 @@ int rmhmc_create_opts(rmhmc_ctx** out, int32_t device_id, int64_t M, int32_t D, 
           // (the instantiation's own, fixed size: these kernels also hold a few KB of static LDS, and static + dynamic must stay within 160 KB)
           constexpr int lds = i8_lds_bytes<S_, WN_, TN_>();
           RC(raise_lds(ctx, k_assemble_i8<S_, WN_, TN_>, lds));
+          if constexpr (i8_zdirect_tile(S_, WN_, TN_)) {
+            RC(raise_lds(ctx, k_assemble_i8<S_, WN_, TN_, true>, (i8_lds_bytes<S_, WN_, TN_, true>())));
+            RC(raise_lds(ctx, k_leverage_i8<S_, WN_, TN_, true>, (i8_lds_bytes<S_, WN_, TN_, true>())));
+          }
           RC(raise_lds(ctx, k_leverage_i8<S_, WN_, TN_>, lds));
           RC(raise_lds(ctx, k_assemble_i8_tail<S_>, (i8_lds_bytes<S_, 1, 1>())));
         });
       if (ctx->i8S == 6) {  // the one-launch delta assembly (launch_assemble_i8_delta): dynamic LDS of its widest instantiation
         RC(raise_lds(ctx, k_assemble_i8_sel<4, 1>, std::max((i8_lds_bytes<6, 4, 1>()), (i8_lds_bytes<4, 4, 1>()))));
+        RC(raise_lds(ctx, k_assemble_i8_sel<4, 1, true>, std::max((i8_lds_bytes<6, 4, 1>()), (i8_lds_bytes<4, 4, 1, true>()))));
         RC(raise_lds(ctx, k_assemble_i8_tail_sel, std::max((i8_lds_bytes<6, 1, 1>()), (i8_lds_bytes<4, 1, 1>()))));
       }
     }

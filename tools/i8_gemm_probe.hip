@@ -16,7 +16,8 @@
 
 #include "../riemannhamiltonianmontecarlo_amd/csrc/metric_i8.hip.h"
 
-template <int S, int WN, int TN, int PIN = 1>
+// ZP > 0: the ZDIRECT form of the tile (B fragments straight from global memory) with a ring of ZP stages
+template <int S, int WN, int TN, int PIN = 1, int ZP = 0>
 static double run_case(int nC, int NP, int K, bool check, int reps) {
   constexpr int BM = 128, BN = 32 * TN * WN;
   const int nCp = (nC + BM - 1) / BM * BM, NPp = (NP + BN - 1) / BN * BN, nks = (K + 31) / 32;
@@ -31,9 +32,9 @@ static double run_case(int nC, int NP, int K, bool check, int reps) {
   CK(hipMemcpy(dV, hV.data(), szV, hipMemcpyHostToDevice)); CK(hipMemcpy(dZ, hZ.data(), szZ, hipMemcpyHostToDevice));
   const int nCB = nCp / BM, nPB = NPp / BN;
   const int grid = (nCB + 7) / 8 * 8 * nPB;
-  constexpr int lds = i8_lds_bytes<S, WN, TN>();
-  CK(hipFuncSetAttribute((const void*)k_gemm_i8_probe<S, WN, TN, PIN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  auto launch = [&]() { hipLaunchKernelGGL((k_gemm_i8_probe<S, WN, TN, PIN>), dim3(grid), dim3(128 * WN), lds, 0, dV, dZ, nCp, NPp, nks, nC, NP, dC); };
+  constexpr int lds = ZP > 0 ? i8_zd_lds_bytes<S, (ZP > 0 ? ZP : 2)>() : i8_lds_bytes<S, WN, TN>();
+  CK(hipFuncSetAttribute((const void*)k_gemm_i8_probe<S, WN, TN, PIN, ZP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  auto launch = [&]() { hipLaunchKernelGGL((k_gemm_i8_probe<S, WN, TN, PIN, ZP>), dim3(grid), dim3(128 * WN), lds, 0, dV, dZ, nCp, NPp, nks, nC, NP, dC); };
   launch(); CK(hipDeviceSynchronize());
   double maxerr = 0;
   if (check) {
@@ -54,7 +55,7 @@ static double run_case(int nC, int NP, int K, bool check, int reps) {
         }
         maxerr = fmax(maxerr, fabs(ref - hC[(size_t)c * NPp + p]));
       }
-    printf("check S=%d WN=%d TN=%d nC=%d NP=%d K=%d: max abs err %.3g\n", S, WN, TN, nC, NP, K, maxerr);
+    printf("check S=%d WN=%d TN=%d ZP=%d nC=%d NP=%d K=%d: max abs err %.3g\n", S, WN, TN, ZP, nC, NP, K, maxerr);
   }
   double ms = 0;
   if (reps > 0) {
@@ -66,7 +67,7 @@ static double run_case(int nC, int NP, int K, bool check, int reps) {
     float f; CK(hipEventElapsedTime(&f, e0, e1)); ms = f / reps;
     const double P = S * (S + 1) / 2.0;
     const double ops = 2.0 * P * nC * (double)NP * K;  // unpadded problem
-    printf("time S=%d WN=%d TN=%d PIN=%d nC=%d NP=%d(+pad %d) K=%d: %.3f ms  %.2f POPS int8 (%d blocks)\n", S, WN, TN, PIN, nC, NP, NPp, K, ms, ops / ms * 1e-12, grid);
+    printf("time S=%d WN=%d TN=%d PIN=%d ZP=%d nC=%d NP=%d(+pad %d) K=%d: %.3f ms  %.2f POPS int8 (%d blocks)\n", S, WN, TN, PIN, ZP, nC, NP, NPp, K, ms, ops / ms * 1e-12, grid);
   }
   CK(hipFree(dV)); CK(hipFree(dZ)); CK(hipFree(dC));
   return ms;
@@ -126,6 +127,23 @@ int main(int argc, char** argv) {
       run_case<4, 2, 1, 1>(8192, 2048, 10000, false, 8);
       run_case<4, 4, 1, 1>(8192, 2048, 10000, false, 8);
       run_case<4, 2, 1, 0>(8192, 2048, 10000, false, 8);
+      return 0;
+    }
+    if (S == 4) {  // 4 slices: the ZDIRECT form (ring of 2, 3, 4 stages) against the LDS form.  Checks against the CPU loop first: fewer
+                   // stages than the ring is deep, a ragged pair block and a partly filled chain block; then the forms alternate
+      run_case<4, 4, 1, 1, 3>(300, 300, 20, true, 0);
+      run_case<4, 4, 1, 1, 3>(130, 200, 40, true, 0);
+      run_case<4, 4, 1, 1, 3>(130, 200, 150, true, 0);
+      run_case<4, 4, 1, 1, 2>(300, 300, 1000, true, 0);
+      run_case<4, 4, 1, 1, 3>(300, 300, 1000, true, 0);
+      run_case<4, 4, 1, 1, 4>(300, 300, 1000, true, 0);
+      run_case<4, 4, 1, 1, 0>(300, 300, 1000, true, 0);
+      for (int rep = 0; rep < 3; ++rep) {
+        run_case<4, 4, 1, 1, 0>(8192, 2048, 10000, false, 8);
+        run_case<4, 4, 1, 1, 2>(8192, 2048, 10000, false, 8);
+        run_case<4, 4, 1, 1, 3>(8192, 2048, 10000, false, 8);
+        run_case<4, 4, 1, 1, 4>(8192, 2048, 10000, false, 8);
+      }
       return 0;
     }
     if (S == 5) run_case<5, 4, 1>(8192, 2080, 10000, false, 3);

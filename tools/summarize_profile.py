@@ -144,7 +144,9 @@ if "FETCH_SIZE" in summary and "WRITE_SIZE" in summary:
                         "Infinity-Cache hits included"}
     for S in (4, 5, 6, 7):
         f = w = 0.0
-        for part in ("k_assemble_i8<%d, 4, 1>" % S, "k_assemble_i8<%d, 2, 1>" % S, "k_assemble_i8_tail<%d>" % S, "k_assemble_i8_tailsum<%d>" % S):
+        # (the last template argument: the ZDIRECT form of the tile, option i8_zdirect - a run launches one of the two)
+        for part in ("k_assemble_i8<%d, 4, 1, false>" % S, "k_assemble_i8<%d, 4, 1, true>" % S, "k_assemble_i8<%d, 2, 1, false>" % S,
+                     "k_assemble_i8_tail<%d>" % S, "k_assemble_i8_tailsum<%d>" % S):
             f += summary["FETCH_SIZE"].get(part, {}).get("avg_raw_kib", 0.0)
             w += summary["WRITE_SIZE"].get(part, {}).get("avg_raw_kib", 0.0)
         if f > 0:
@@ -152,7 +154,7 @@ if "FETCH_SIZE" in summary and "WRITE_SIZE" in summary:
             tr["assemble_i8_x%d_bytes_per_launch" % S] = (2.0 * f + w) * 1024.0
     # the one-launch delta assembly (whatever slice count its launches picked: 4 at stationarity)
     f = w = 0.0
-    for part in ("k_assemble_i8_sel<4, 1>", "k_assemble_i8_tail_sel", "k_assemble_i8_tailsum_sel"):
+    for part in ("k_assemble_i8_sel<4, 1, false>", "k_assemble_i8_sel<4, 1, true>", "k_assemble_i8_tail_sel", "k_assemble_i8_tailsum_sel"):
         f += summary["FETCH_SIZE"].get(part, {}).get("avg_raw_kib", 0.0)
         w += summary["WRITE_SIZE"].get(part, {}).get("avg_raw_kib", 0.0)
     if f > 0:
