@@ -150,8 +150,10 @@ int rmhmc_create(rmhmc_ctx **out, int32_t device_id, int64_t M, int32_t D,
  *   i8_delta [create] 1        int8 path, 6 slices: the metric at the end of a leapfrog step as G(last iterate) + the assembly
  *                              of the v differences (4 slices)
  *   i8_delta_inner [create] 1  ... and the second position iterate from the first likewise
- *   i8_zdirect [create] 1      int8 path: the 4-slice tiles (4-slice contexts, and the delta assemblies above) take their data-side
- *                              fragments straight from global memory into registers instead of through LDS (bit-identical results)
+ *   i8_zdirect [create] 3      int8 path, a mask 0..3: the tiles of a slice count take their data-side fragments straight from global
+ *                              memory into registers instead of through LDS (bit-identical results).  Bit 0 (value 1): the 4-slice
+ *                              tiles (4-slice contexts, and the delta assemblies above); bit 1 (value 2): the 5-slice tiles (5-slice
+ *                              contexts; at 6 slices the first position iterate and the leverage pass)
  * The CPU oracle accepts every key and ignores the values. */
 typedef struct { const char *key; int64_t value; } rmhmc_option;
 int rmhmc_create_opts(rmhmc_ctx **out, int32_t device_id, int64_t M, int32_t D, int64_t n_chains, int32_t dtype,

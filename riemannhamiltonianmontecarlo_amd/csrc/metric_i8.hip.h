@@ -378,43 +378,61 @@ __device__ __forceinline__ void gemm_i8_tile(const int8_t* __restrict__ Vs, cons
 
 
 // ---------------------------------------------------------------------------------------------
-// ZDIRECT form of the 8-wave tile at S = 4 (option i8_zdirect; WN = 4, TN = 1): the Z (B) operand never touches LDS.
+// ZDIRECT form of the 8-wave tile at S = 4 and S = 5 (option i8_zdirect, one bit per slice count; WN = 4, TN = 1): the Z (B) operand
+// never touches LDS.
 // A wave's B fragments of one slice and stage - 32 pairs x 32 bytes - are 1 KB contiguous in the stage-major Zs and already in fragment
 // order (lane & 31 = pair, lane >> 5 = 16-byte half), so one global_load_dwordx4 per slice and stage brings them straight into the
-// fragment registers.  LDS then carries the V (A) part alone: a stage is S x 128 rows x 32 B = 16 KB of LDS-DMA and 64 KB of fragment
-// reads per workgroup, where the LDS form moves 32 + 96 KB for the same 20 MFMAs per wave.
-//   ring      P stages ahead for both operands (I8_ZRING): P + 1 LDS buffers of the V stage, P register sets fb[P][S] of 16 bytes per lane
-//             (the S' = 4 branch has the registers: 128 accumulators against the 192 of S = 6).  The loop is unrolled P times so
-//             that every ring index is a constant.
+// fragment registers.  LDS then carries the V (A) part alone: at S = 4 a stage is S x 128 rows x 32 B = 16 KB of LDS-DMA and 64 KB of
+// fragment reads per workgroup, where the LDS form moves 32 + 96 KB for the same 20 MFMAs per wave (S = 5: 20 + 80 KB against 40 + 120 KB
+// for 30 MFMAs).
+//   ring      P stages ahead for both operands (i8_zring<S>()): P + 1 LDS buffers of the V stage, P register sets fb[P][S] of 16 bytes per
+//             lane (the 4- and 5-slice tiles have the registers: 128 and 160 accumulators against the 192 of S = 6, where 192 + 2 x 24
+//             ring registers + 16 of A leave none for addresses).  The loop is unrolled P times so that every ring index is a constant.
 //   LDS-DMA   256 units of 16 bytes per slice and 512 threads: the waves 0-3 stage the even slices, the waves 4-7 the odd ones, every
 //             thread one unit of every second slice, unconditionally (ALLON above; past the end the last stage is fetched again).
+//             Odd S: the last slice has no partner, so all eight waves share it, 32 units each: one more DMA load per wave with the
+//             lanes 0-31 active (the LDS address of a unit is the wave's base + 16 x lane, so the 32 units land contiguously).  Every
+//             wave has those lanes, so the instruction is always issued and counts one in vmcnt like a full one: ND = (S + 1) / 2
+//             loads for every wave, and the count below is one compile-time number per S.  (Staging the slice twice instead - the
+//             waves 4-7 repeating the loads of the waves 0-3 - counted the same but took 2-3 % longer: profiles/i8_zdirect5_ab.txt.)
 //   issue     stage ks issues the loads of stage ks + P behind its MFMAs, one Z slice per product group: group i is the last to
-//             use fb[S-1-i], which is then re-loaded in place.  The S/2 DMA loads go in front of the first groups.  Per wave and
-//             stage that is Q = S + S/2 vector-memory instructions in a fixed order, DMA and register loads in ONE vmcnt queue that
-//             returns in order.
+//             use fb[S-1-i], which is then re-loaded in place.  The ND DMA loads go in front of the first groups.  Per wave and
+//             stage that is Q = S + ND vector-memory instructions (6 at S = 4, 8 at S = 5) in a fixed order, DMA and register loads in
+//             ONE vmcnt queue that returns in order.
 //   waits     at the end of stage ks: vmcnt((P-1) Q) - everything but the loads issued in the last P - 1 stages has landed, i.e. all
 //             of stage ks + 1: its fb registers (named on the wait, so that no MFMA is hoisted above it; the Z loads need no barrier)
 //             and this wave's share of its V stage, which is read after the barrier that follows (one barrier after the wait that
 //             retired it).  Buffer of stage ks + P = buffer of stage ks - 1: free since the barrier that ended that stage.
 //   the end   one vmcnt(0) named on every fb register: no LDS-DMA write outlives the workgroup and no register load the registers'
 //             last use.
-// Waves whose tile is all padding stage their V units and skip everything else.  The integer sums are those of gemm_i8_tile in
+// Waves whose tile is all padding stage their V units (the same ND loads per stage, counted the same way) and skip everything else.
+// The integer sums are those of gemm_i8_tile in
 // another association: bit-identical results.
 // ---------------------------------------------------------------------------------------------
 #ifndef I8_ZRING
 #define I8_ZRING 3   // stages ahead, as the LDS form at S = 4; 2, 3 and 4 time alike on the tile alone (tools/i8_gemm_probe 4, profiles/i8_zdirect_ab.txt)
 #endif
-constexpr bool i8_zdirect_tile(int S, int WN, int TN) { return S == 4 && WN == 4 && TN == 1; }
+#ifndef I8_ZRING5
+#define I8_ZRING5 3  // S = 5: 3 is 2 % faster than 2 at both shapes, more than the spread (tools/i8_gemm_probe 55, profiles/i8_zdirect5_ab.txt)
+#endif
+template <int S>
+constexpr int i8_zring() { return S == 5 ? I8_ZRING5 : I8_ZRING; }
+constexpr bool i8_zdirect_tile(int S, int WN, int TN) { return (S == 4 || S == 5) && WN == 4 && TN == 1; }
+// option i8_zdirect is a mask: bit 0 the 4-slice tiles, bit 1 the 5-slice tiles
+constexpr bool i8_zdirect_on(long long mask, int S) { return (S == 4 || S == 5) && ((mask >> (S - 4)) & 1) != 0; }
 template <int S, int P>
 constexpr int i8_zd_lds_bytes() { return (P + 1) * S * I8_BM * I8_ROWB; }
 
 __device__ __forceinline__ void gbl_load_b128(i4v& r, unsigned off, const void* base) {  // wave-uniform base + 32-bit lane offset
   asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(r) : "v"(off), "s"(base) : "memory");
 }
-template <int N>
-__device__ __forceinline__ void wait_vmcnt(i4v& a, i4v& b, i4v& c, i4v& d) {
+// s_waitcnt vmcnt(N) that names all S fragment registers of a ring slot
+template <int N, int S>
+__device__ __forceinline__ void wait_vmcnt_fb(i4v (&f)[S]) {
   static_assert(N >= 0 && N < 64, "vmcnt immediate");
-  asm volatile("s_waitcnt vmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N) : "memory");
+  static_assert(S == 4 || S == 5, "one asm statement per slice count");
+  if constexpr (S == 4) asm volatile("s_waitcnt vmcnt(%4)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]) : "n"(N) : "memory");
+  else asm volatile("s_waitcnt vmcnt(%5)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]) : "n"(N) : "memory");
 }
 
 template <int S, int P, class Epilogue>
@@ -422,8 +440,7 @@ __device__ __forceinline__ void gemm_i8_tile_zd(const int8_t* __restrict__ Vs, c
                                                 int cb, int pb, int rows_real, int cols_real, Epilogue&& epi) {
   constexpr int BM = I8_BM, BN = 128, NBUF = P + 1;
   constexpr int SLICE = BM * I8_ROWB, STAGE = S * SLICE;  // LDS bytes of one slice / one stage of V
-  constexpr int ND = S / 2, Q = S + ND;                    // LDS-DMA loads, all loads per wave and stage
-  static_assert(S == 4, "four fb registers per ring slot are named on the waits");
+  constexpr int ND = (S + 1) / 2, Q = S + ND;              // LDS-DMA loads, all loads per wave and stage
   static_assert(P >= 2 && (P - 1) * Q < 64, "vmcnt immediate");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -435,9 +452,18 @@ __device__ __forceinline__ void gemm_i8_tile_zd(const int8_t* __restrict__ Vs, c
   const int8_t* const va = Vs + ((size_t)cb * BM) * 32 + sp * strideV;                    // wave-uniform
   const unsigned goff = (unsigned)(urow * 32 + (((u & 1) ^ ((urow >> 3) & 1)) << 4));     // per lane
   const int lbase = sp * SLICE + (wave & 3) * 64 * 16;                                    // wave-uniform: (u & ~63) * 16 inside slice sp
+  // odd S: the last slice, 32 units per wave over all eight waves (lanes 0-31)
+  const int8_t* const vlast = Vs + ((size_t)cb * BM) * 32 + (S - 1) * strideV;            // wave-uniform
+  const int ul = wave * 32 + (lane & 31), ulrow = ul >> 1;
+  const unsigned goffl = (unsigned)(ulrow * 32 + (((ul & 1) ^ ((ulrow >> 3) & 1)) << 4)); // per lane
   auto dma = [&](int ks, int buf, int q) {  // slice sp + 2 q of stage ks
-    __builtin_amdgcn_global_load_lds((gbl_ptr_t)(va + (2 * q * strideV + (size_t)ks * stepV) + goff),
-                                     (lds_ptr_t)(lds + buf * STAGE + 2 * q * SLICE + lbase), 16, 0, 0);
+    if ((S & 1) && q == ND - 1) {
+      if (lane < 32)
+        __builtin_amdgcn_global_load_lds((gbl_ptr_t)(vlast + (size_t)ks * stepV + goffl),
+                                         (lds_ptr_t)(lds + buf * STAGE + (S - 1) * SLICE + wave * 32 * 16), 16, 0, 0);
+    } else
+      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(va + (2 * q * strideV + (size_t)ks * stepV) + goff),
+                                       (lds_ptr_t)(lds + buf * STAGE + 2 * q * SLICE + lbase), 16, 0, 0);
   };
   // Z: the wave's 32 pairs, slice j of stage ks, in fragment order
   const int8_t* const zw = Zs + ((size_t)pb * BN + wn * 32) * 32;                         // wave-uniform
@@ -484,7 +510,7 @@ __device__ __forceinline__ void gemm_i8_tile_zd(const int8_t* __restrict__ Vs, c
         zld(fb[d][S - 1 - i], kd, S - 1 - i);
       }
     }
-    wait_vmcnt<(P - 1) * Q>(fb[0][0], fb[0][1], fb[0][2], fb[0][3]);
+    wait_vmcnt_fb<(P - 1) * Q>(fb[0]);
     __builtin_amdgcn_s_barrier();
     const int fragA = i8_lds_off(wm * 64 + (lane & 31), lane >> 5);
     const unsigned a0 = (unsigned)(size_t)(lds_ptr_t)(lds) + fragA;
@@ -514,7 +540,7 @@ __device__ __forceinline__ void gemm_i8_tile_zd(const int8_t* __restrict__ Vs, c
         }(), ...);
       }(std::make_integer_sequence<int, S>{});
       constexpr int R1 = (R + 1) % P;
-      wait_vmcnt<(P - 1) * Q>(fb[R1][0], fb[R1][1], fb[R1][2], fb[R1][3]);
+      wait_vmcnt_fb<(P - 1) * Q>(fb[R1]);
       __builtin_amdgcn_s_barrier();
       cur = cur + 1 >= NBUF ? 0 : cur + 1;
     };
@@ -525,14 +551,14 @@ __device__ __forceinline__ void gemm_i8_tile_zd(const int8_t* __restrict__ Vs, c
       }(std::make_integer_sequence<int, P>{});
     }
 #pragma unroll
-    for (int d = 0; d < P; ++d) wait_vmcnt<0>(fb[d][0], fb[d][1], fb[d][2], fb[d][3]);
+    for (int d = 0; d < P; ++d) wait_vmcnt_fb<0>(fb[d]);
   }
   i8_tile_epilogue<S, 1, BN, false>(acc, cb, pb, wm, wn, lane, epi);
 }
 
 template <int S, int WN, int TN, bool ZD = false>
 constexpr int i8_lds_bytes() {
-  if (ZD && i8_zdirect_tile(S, WN, TN)) return i8_zd_lds_bytes<S, I8_ZRING>();
+  if (ZD && i8_zdirect_tile(S, WN, TN)) return i8_zd_lds_bytes<S, i8_zring<S>()>();
   return i8_nbuf<S, WN, TN>() * S * (I8_BM + 32 * TN * WN) * I8_ROWB;
 }
 
@@ -829,13 +855,14 @@ __device__ __forceinline__ void assemble_i8_body(const int8_t* __restrict__ Vs, 
     if (ok) *gp = g;
   };
   if constexpr (ZD && i8_zdirect_tile(S, WN, TN))
-    gemm_i8_tile_zd<S, I8_ZRING>(Vs + (size_t)kb * nCp * 32, Zs + (size_t)kb * pr.NPp * 32, nCp, pr.NPp, nks_total, kn, cb, pb, n_chains - cb * I8_BM,
+    gemm_i8_tile_zd<S, i8_zring<S>()>(Vs + (size_t)kb * nCp * 32, Zs + (size_t)kb * pr.NPp * 32, nCp, pr.NPp, nks_total, kn, cb, pb, n_chains - cb * I8_BM,
                                  pr.NP - pb * 32 * TN * WN, epi);
   else
     gemm_i8_tile<S, WN, TN, (WN == 4)>(Vs + (size_t)kb * nCp * 32, Zs + (size_t)kb * pr.NPp * 32, nCp, pr.NPp, nks_total, kn, cb, pb,
                                        n_chains - cb * I8_BM, pr.NP - pb * 32 * TN * WN, epi);
 }
-// ZD (option i8_zdirect): the S = 4 tile in its ZDIRECT form (gemm_i8_tile_zd); every other slice count is the same code either way
+// ZD (option i8_zdirect, the bit of this S): the S = 4 or S = 5 tile in its ZDIRECT form (gemm_i8_tile_zd); every other slice count is the
+// same code either way
 template <int S, int WN, int TN, bool ZD = false>
 __global__ __launch_bounds__(128 * WN) __attribute__((amdgpu_waves_per_eu(WN / 2, WN / 2))) void k_assemble_i8(const int8_t* __restrict__ Vs, const int8_t* __restrict__ Zs, int nCp, int nks_total,
                                                           int ks0, int nk, int accumulate, I8Pairs pr, int n_chains, const int* __restrict__ phase,
@@ -857,7 +884,8 @@ __device__ __forceinline__ int i8_delta_pick(const I8Delta& dl, int seff) {
 __device__ __forceinline__ void i8_delta_count(const I8Delta& dl, int seff, int Sp) {
   if (dl.count && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) atomicAdd(dl.count + 3 * (6 - seff) + (Sp - 4), 1ull);
 }
-template <int WN, int TN, bool ZD = false>
+// ZM: the value of option i8_zdirect (bit 0: the S' = 4 branch in its ZDIRECT form, bit 1: the S' = 5 branch)
+template <int WN, int TN, int ZM = 0>
 __global__ __launch_bounds__(128 * WN) __attribute__((amdgpu_waves_per_eu(WN / 2, WN / 2))) void k_assemble_i8_sel(const int8_t* __restrict__ Vs, size_t vplane, int seff, const int8_t* __restrict__ Zs, int nCp, int nks_total,
                                                           int ks0, int nk, int accumulate, I8Pairs pr, int n_chains, const int* __restrict__ phase,
                                                           const int* __restrict__ vbad, int DP, double inv_alpha, double* __restrict__ Gq,
@@ -867,8 +895,8 @@ __global__ __launch_bounds__(128 * WN) __attribute__((amdgpu_waves_per_eu(WN / 2
   dl.cscale = __builtin_ldexp(1.0, -8 * (seff - Sp));
   Vs += (size_t)(seff - Sp) * vplane;
   if (Sp == 6) assemble_i8_body<6, WN, TN>(Vs, Zs, nCp, nks_total, ks0, nk, accumulate, pr, n_chains, phase, vbad, DP, inv_alpha, Gq, plane_stride, vexp, npb, dl);
-  else if (Sp == 5) assemble_i8_body<5, WN, TN>(Vs, Zs, nCp, nks_total, ks0, nk, accumulate, pr, n_chains, phase, vbad, DP, inv_alpha, Gq, plane_stride, vexp, npb, dl);
-  else assemble_i8_body<4, WN, TN, ZD>(Vs, Zs, nCp, nks_total, ks0, nk, accumulate, pr, n_chains, phase, vbad, DP, inv_alpha, Gq, plane_stride, vexp, npb, dl);
+  else if (Sp == 5) assemble_i8_body<5, WN, TN, (ZM & 2) != 0>(Vs, Zs, nCp, nks_total, ks0, nk, accumulate, pr, n_chains, phase, vbad, DP, inv_alpha, Gq, plane_stride, vexp, npb, dl);
+  else assemble_i8_body<4, WN, TN, (ZM & 1) != 0>(Vs, Zs, nCp, nks_total, ks0, nk, accumulate, pr, n_chains, phase, vbad, DP, inv_alpha, Gq, plane_stride, vexp, npb, dl);
 }
 
 // The pairs beyond the last FULL block of 32 WN pairs (D = 64: 2080 = 16 x 128 + 32) as tiles of their own.  In the main launch
@@ -1136,7 +1164,7 @@ __global__ __launch_bounds__(128 * WN) __attribute__((amdgpu_waves_per_eu(WN / 2
     if (ok) Rout[o] = r;
   };
   if constexpr (ZD && i8_zdirect_tile(S, WN, TN))
-    gemm_i8_tile_zd<S, I8_ZRING>(Qs + (size_t)kb * nCp * 32, Zt + (size_t)kb * NRp * 32, nCp, NRp, nkp_total, kn, cb, rb, n_chains - cb * I8_BM,
+    gemm_i8_tile_zd<S, i8_zring<S>()>(Qs + (size_t)kb * nCp * 32, Zt + (size_t)kb * NRp * 32, nCp, NRp, nkp_total, kn, cb, rb, n_chains - cb * I8_BM,
                                  Mp - rb * 32 * TN * WN, epi);
   else
     gemm_i8_tile<S, WN, TN, (WN == 4)>(Qs + (size_t)kb * nCp * 32, Zt + (size_t)kb * NRp * 32, nCp, NRp, nkp_total, kn, cb, rb,

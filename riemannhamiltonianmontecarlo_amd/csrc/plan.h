@@ -43,7 +43,7 @@ constexpr int i8_tile_tn(int) { return 1; }
 struct Options {
   int64_t graph = 1, sorted = 1, inflight = 32, cdyn = 1, crestore = 1, i8_force_rebase = 0;                 // run time
   int64_t ccache = 1, medium = 1, fused = 1, hmc_traj_maxn = -1, fsplit = 0, nsplit_max = 64, nsplit_waves = -1, i8_tail = -1,   // create time
-          i8_delta = 1, i8_delta_inner = 1, i8_zdirect = 1;
+          i8_delta = 1, i8_delta_inner = 1, i8_zdirect = 3;
 };
 struct OptionDesc { const char* key; int64_t Options::*slot; bool create_only; int64_t lo, hi; };
 inline const OptionDesc kOptions[] = {
@@ -63,7 +63,7 @@ inline const OptionDesc kOptions[] = {
     {"i8_tail", &Options::i8_tail, true, -1, 1},
     {"i8_delta", &Options::i8_delta, true, 0, 1},
     {"i8_delta_inner", &Options::i8_delta_inner, true, 0, 1},
-    {"i8_zdirect", &Options::i8_zdirect, true, 0, 1},
+    {"i8_zdirect", &Options::i8_zdirect, true, 0, 3},  // mask: bit 0 the 4-slice tiles, bit 1 the 5-slice tiles
 };
 inline const OptionDesc* find_option(const char* key) {
   if (!key) return nullptr;

@@ -104,8 +104,8 @@ struct rmhmc_ctx : Plan {
   int i8_inner_drop = 1;     // inner assemblies from S-1 slices (launch_assemble; RMHMC_FLAG_INT8_INNER_FULL: off)
   // (options i8_delta / i8_delta_inner: G at the end of a leapfrog step, and the second position iterate, as the previous iterate's G + the
   //  assembly of the v differences; i8_force_rebase: tests treat every chain as if its v exponent had changed; i8_tail: ragged last pair
-  //  block as tiles of its own: -1 when it pays (launch_assemble_i8_t), 0 never, 1 always; i8_zdirect: the 4-slice tiles in their
-  //  ZDIRECT form, chosen at launch - both forms are built)
+  //  block as tiles of its own: -1 when it pays (launch_assemble_i8_t), 0 never, 1 always; i8_zdirect: the 4-slice (bit 0) and 5-slice (bit 1)
+  //  tiles in their ZDIRECT form, chosen at launch - both forms are built)
   int8_t* d_Zs = nullptr;
   int* d_ze = nullptr;
   int8_t* d_Zt = nullptr;   // leverage pass: x_a x_b sliced per data row, [S][nkp][NRp][32]
@@ -295,9 +295,10 @@ void launch_assemble_i8_t(rmhmc_ctx* ctx, Group& g, const double* v, hipStream_t
     return;
   }
   const I8Geometry t = i8_geometry(*ctx, g.nCp, WN, TN, WN == 4);  // (k_assemble_i8_tail pairs with the 8-wave tile)
-  // option i8_zdirect: the ZDIRECT form of the tile where there is one (S = 4); both forms are in the library
+  // option i8_zdirect: the ZDIRECT form of the tile where there is one (S = 4, 5: one bit of the option each); both forms are in the
+  // library, and each launches with the LDS size of its own instantiation
   auto main_tiles = [&](dim3 grid, auto... args) {
-    if (i8_zdirect_tile(S, WN, TN) && ctx->opt.i8_zdirect)
+    if (i8_zdirect_tile(S, WN, TN) && i8_zdirect_on(ctx->opt.i8_zdirect, S))
       hipLaunchKernelGGL((k_assemble_i8<S, WN, TN, true>), grid, dim3(128 * WN), (i8_lds_bytes<S, WN, TN, true>()), st, args...);
     else
       hipLaunchKernelGGL((k_assemble_i8<S, WN, TN>), grid, dim3(128 * WN), (i8_lds_bytes<S, WN, TN>()), st, args...);
@@ -340,10 +341,16 @@ void launch_assemble_i8_delta(rmhmc_ctx* ctx, Group& g, hipStream_t st, int seff
   // the assembly is counted once (g.dcount): by the first k piece's main launch, or by its tail launch when there are no main tiles
   I8Delta dlc = dl;
   dlc.count = g.dcount;
-  // option i8_zdirect picks the kernel whose S' = 4 branch is the ZDIRECT form; the 5- and 6-slice branches are the same code in both
+  // option i8_zdirect picks the kernel whose S' = 4 (bit 0) and S' = 5 (bit 1) branches are the ZDIRECT form; the 6-slice branch is the
+  // same code in all four.  lds: the 6-slice LDS form, wider than either ZDIRECT form
+  static_assert(lds >= (i8_lds_bytes<5, WN, TN, true>()) && lds >= (i8_lds_bytes<4, WN, TN, true>()), "dynamic LDS of the widest instantiation");
   auto main_tiles = [&](dim3 grid, auto... args) {
-    if (ctx->opt.i8_zdirect) hipLaunchKernelGGL((k_assemble_i8_sel<WN, TN, true>), grid, dim3(128 * WN), lds, st, args...);
-    else hipLaunchKernelGGL((k_assemble_i8_sel<WN, TN>), grid, dim3(128 * WN), lds, st, args...);
+    switch ((int)ctx->opt.i8_zdirect) {
+      case 3: hipLaunchKernelGGL((k_assemble_i8_sel<WN, TN, 3>), grid, dim3(128 * WN), lds, st, args...); break;
+      case 2: hipLaunchKernelGGL((k_assemble_i8_sel<WN, TN, 2>), grid, dim3(128 * WN), lds, st, args...); break;
+      case 1: hipLaunchKernelGGL((k_assemble_i8_sel<WN, TN, 1>), grid, dim3(128 * WN), lds, st, args...); break;
+      default: hipLaunchKernelGGL((k_assemble_i8_sel<WN, TN, 0>), grid, dim3(128 * WN), lds, st, args...);
+    }
   };
   for (int ks0 = 0; ks0 < ctx->i8_nks; ks0 += ctx->i8_chunk) {
     const int nk = std::min(ctx->i8_chunk, ctx->i8_nks - ks0);
@@ -371,7 +378,7 @@ void launch_leverage_i8_t(rmhmc_ctx* ctx, Group& g, hipStream_t st, int part) {
   const int nCB = g.nCp / I8_BM, nRB = ctx->i8_NRp / (32 * TN * WN);
   const unsigned nblk = (unsigned)(nCB < 8 ? nCB * nRB : (nCB + 7) / 8 * 8 * nRB);
   auto tiles = [&](dim3 grid, auto... args) {  // (option i8_zdirect, as in launch_assemble_i8_t)
-    if (i8_zdirect_tile(S, WN, TN) && ctx->opt.i8_zdirect)
+    if (i8_zdirect_tile(S, WN, TN) && i8_zdirect_on(ctx->opt.i8_zdirect, S))
       hipLaunchKernelGGL((k_leverage_i8<S, WN, TN, true>), grid, dim3(128 * WN), (i8_lds_bytes<S, WN, TN, true>()), st, args...);
     else
       hipLaunchKernelGGL((k_leverage_i8<S, WN, TN>), grid, dim3(128 * WN), (i8_lds_bytes<S, WN, TN>()), st, args...);
@@ -952,7 +959,7 @@ int rmhmc_create_opts(rmhmc_ctx** out, int32_t device_id, int64_t M, int32_t D, 
           // (the instantiation's own, fixed size: these kernels also hold a few KB of static LDS, and static + dynamic must stay within 160 KB)
           constexpr int lds = i8_lds_bytes<S_, WN_, TN_>();
           RC(raise_lds(ctx, k_assemble_i8<S_, WN_, TN_>, lds));
-          if constexpr (i8_zdirect_tile(S_, WN_, TN_)) {
+          if constexpr (i8_zdirect_tile(S_, WN_, TN_)) if (i8_zdirect_on(ctx->opt.i8_zdirect, S_)) {
             RC(raise_lds(ctx, k_assemble_i8<S_, WN_, TN_, true>, (i8_lds_bytes<S_, WN_, TN_, true>())));
             RC(raise_lds(ctx, k_leverage_i8<S_, WN_, TN_, true>, (i8_lds_bytes<S_, WN_, TN_, true>())));
           }
@@ -960,8 +967,11 @@ int rmhmc_create_opts(rmhmc_ctx** out, int32_t device_id, int64_t M, int32_t D, 
           RC(raise_lds(ctx, k_assemble_i8_tail<S_>, (i8_lds_bytes<S_, 1, 1>())));
         });
       if (ctx->i8S == 6) {  // the one-launch delta assembly (launch_assemble_i8_delta): dynamic LDS of its widest instantiation
-        RC(raise_lds(ctx, k_assemble_i8_sel<4, 1>, std::max((i8_lds_bytes<6, 4, 1>()), (i8_lds_bytes<4, 4, 1>()))));
-        RC(raise_lds(ctx, k_assemble_i8_sel<4, 1, true>, std::max((i8_lds_bytes<6, 4, 1>()), (i8_lds_bytes<4, 4, 1, true>()))));
+        constexpr int lds_sel = std::max({i8_lds_bytes<6, 4, 1>(), i8_lds_bytes<4, 4, 1>(), i8_lds_bytes<4, 4, 1, true>(), i8_lds_bytes<5, 4, 1, true>()});
+        RC(raise_lds(ctx, k_assemble_i8_sel<4, 1, 0>, lds_sel));
+        RC(raise_lds(ctx, k_assemble_i8_sel<4, 1, 1>, lds_sel));
+        RC(raise_lds(ctx, k_assemble_i8_sel<4, 1, 2>, lds_sel));
+        RC(raise_lds(ctx, k_assemble_i8_sel<4, 1, 3>, lds_sel));
         RC(raise_lds(ctx, k_assemble_i8_tail_sel, std::max((i8_lds_bytes<6, 1, 1>()), (i8_lds_bytes<4, 1, 1>()))));
       }
     }

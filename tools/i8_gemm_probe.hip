@@ -146,6 +146,29 @@ int main(int argc, char** argv) {
       }
       return 0;
     }
+    if (S == 55) {  // 5 slices: the ZDIRECT form (ring of 2 and 3 stages) against the LDS form, as mode 4; then the forms alternate at the
+                    // assembly shape (full pair blocks) and at the leverage shape (rows of the data set x pairs)
+      run_case<5, 4, 1, 1, 2>(300, 300, 20, true, 0);
+      run_case<5, 4, 1, 1, 3>(300, 300, 20, true, 0);
+      run_case<5, 4, 1, 1, 2>(130, 200, 40, true, 0);
+      run_case<5, 4, 1, 1, 3>(130, 200, 40, true, 0);
+      run_case<5, 4, 1, 1, 2>(130, 200, 150, true, 0);
+      run_case<5, 4, 1, 1, 3>(130, 200, 150, true, 0);
+      run_case<5, 4, 1, 1, 2>(300, 300, 1000, true, 0);
+      run_case<5, 4, 1, 1, 3>(300, 300, 1000, true, 0);
+      run_case<5, 4, 1, 1, 0>(300, 300, 1000, true, 0);
+      for (int rep = 0; rep < 3; ++rep) {
+        run_case<5, 4, 1, 1, 0>(8192, 2048, 10000, false, 8);
+        run_case<5, 4, 1, 1, 2>(8192, 2048, 10000, false, 8);
+        run_case<5, 4, 1, 1, 3>(8192, 2048, 10000, false, 8);
+      }
+      for (int rep = 0; rep < 3; ++rep) {
+        run_case<5, 4, 1, 1, 0>(8192, 10000, 2080, false, 8);
+        run_case<5, 4, 1, 1, 2>(8192, 10000, 2080, false, 8);
+        run_case<5, 4, 1, 1, 3>(8192, 10000, 2080, false, 8);
+      }
+      return 0;
+    }
     if (S == 5) run_case<5, 4, 1>(8192, 2080, 10000, false, 3);
     if (S == 6) run_case<6, 2, 1>(8192, 2080, 10000, false, 3);
     return 0;

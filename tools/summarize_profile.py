@@ -154,7 +154,8 @@ if "FETCH_SIZE" in summary and "WRITE_SIZE" in summary:
             tr["assemble_i8_x%d_bytes_per_launch" % S] = (2.0 * f + w) * 1024.0
     # the one-launch delta assembly (whatever slice count its launches picked: 4 at stationarity)
     f = w = 0.0
-    for part in ("k_assemble_i8_sel<4, 1, false>", "k_assemble_i8_sel<4, 1, true>", "k_assemble_i8_tail_sel", "k_assemble_i8_tailsum_sel"):
+    # (the last template argument of k_assemble_i8_sel: the value of option i8_zdirect, 0..3)
+    for part in tuple("k_assemble_i8_sel<4, 1, %d>" % zm for zm in range(4)) + ("k_assemble_i8_tail_sel", "k_assemble_i8_tailsum_sel"):
         f += summary["FETCH_SIZE"].get(part, {}).get("avg_raw_kib", 0.0)
         w += summary["WRITE_SIZE"].get(part, {}).get("avg_raw_kib", 0.0)
     if f > 0:
