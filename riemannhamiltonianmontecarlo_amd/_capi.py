@@ -127,6 +127,51 @@ GIBBS_SIGNATURES = {
 }
 
 
+# include/rmhmc_out.h: the output descriptor (every sampler to host or device memory, raw or reduced), HIP library only as well
+OUT_HOST, OUT_DEVICE = 0, 1
+
+
+class Out(C.Structure):
+    """rmhmc_out of include/rmhmc_out.h: every pointer in the memory space `where` names, NULL where an output is not wanted"""
+    _fields_ = [("where", C.c_int32), ("samples", C.c_void_p), ("mean", C.c_void_p), ("var", C.c_void_p), ("ess", C.c_void_p),
+                ("run_mean", C.c_void_p), ("run_ess", C.c_void_p)]
+
+
+_op = C.POINTER(Out)
+_vp = C.c_void_p   # a counter output: host or device memory, as Out.where says
+OUT_SIGNATURES = {
+    "rmhmc_sample_to": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_int32, C.c_uint64, C.c_int64, _dp, _op,
+                                  _vp, _vp, _dp]),
+    "rmhmc_hmc_sample_to": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_uint64, C.c_int64, _dp, _op, _vp, _vp,
+                                      _dp]),
+    "rmhmc_mmala_sample_to": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_uint64, C.c_int64, _dp, _op, _vp, _dp]),
+    "rmhmc_amh_sample_to": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_int64, _dp, _op, _vp, _vp, _dp]),
+    "rmhmc_iwls_sample_to": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_uint64, C.c_int64, _dp, _op, _vp, _vp, _dp]),
+    "rmhmc_gibbs_sample_to": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_int64, _op, _vp, _vp, _dp]),
+    "rmhmc_ess_dev": (C.c_int, [C.c_void_p, _vp, C.c_int64, C.c_int64, C.c_int32, _vp, _vp, _vp]),
+}
+# sampler -> (entry point, its per-chain counters in the order of its signature: (dict key, [n][D] doubles instead of [n] int64))
+SAMPLERS_TO = {
+    "rmhmc": ("rmhmc_sample_to", (("accepted", False), ("leapfrog_steps", False))),
+    "hmc": ("rmhmc_hmc_sample_to", (("accepted", False), ("leapfrog_steps", False))),
+    "mmala": ("rmhmc_mmala_sample_to", (("accepted", False),)),
+    "amh": ("rmhmc_amh_sample_to", (("accepted", False), ("sd", True))),
+    "iwls": ("rmhmc_iwls_sample_to", (("accepted", False), ("saturated", False))),
+    "gibbs": ("rmhmc_gibbs_sample_to", (("capped", False), ("stopped", False))),
+}
+# the run arguments a sampler has besides n_iter, burn_in, seed, chain_offset (Context.sample_to)
+SAMPLER_ARGS = {"rmhmc": ("L", "eps", "K", "theta0"), "hmc": ("L", "eps", "theta0"), "mmala": ("eps", "theta0"), "amh": ("theta0",),
+                "iwls": ("compat", "theta0"), "gibbs": ()}
+SUMMARY_KEYS = ("mean", "var", "ess", "run_mean", "run_ess")
+
+
+def ess_flags(ess_nfft):
+    """context flags of the FFT-length convention of the device ESS: "matlab" (no wrap, the default) or "python" (tools.py:23)"""
+    if ess_nfft not in ("matlab", "python"):
+        raise ValueError('ess_nfft must be "matlab" or "python"')
+    return FLAG_ESS_WRAP if ess_nfft == "python" else 0
+
+
 class RmhmcError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("rmhmc error %d: %s" % (code, msg))
@@ -171,6 +216,12 @@ class RmhmcLib:
         self.has_gibbs = all(hasattr(self.lib, name) for name in GIBBS_SIGNATURES)
         if self.has_gibbs:
             for name, (res, args) in GIBBS_SIGNATURES.items():
+                fn = getattr(self.lib, name)
+                fn.restype = res
+                fn.argtypes = args
+        self.has_out = all(hasattr(self.lib, name) for name in OUT_SIGNATURES)
+        if self.has_out:
+            for name, (res, args) in OUT_SIGNATURES.items():
                 fn = getattr(self.lib, name)
                 fn.restype = res
                 fn.argtypes = args
@@ -315,7 +366,10 @@ class Context:
         self._ck(self.lib.rmhmc_ess(self._h, _ptr(samples), n, S, P, _ptr(out)))
         return out
 
-    def sample_stats(self, n_iter, burn_in, L=6, eps=0.5, K=4, seed=0, chain_offset=0, theta0=None):
+    def sample_stats(self, n_iter, burn_in, L=6, eps=0.5, K=4, seed=0, chain_offset=0, theta0=None, run_mean=False):
+        if run_mean:  # (include/rmhmc_out.h)
+            return self.sample_to("rmhmc", n_iter, burn_in, stats=True, run_mean=True, L=L, eps=eps, K=K, seed=seed,
+                                  chain_offset=chain_offset, theta0=theta0)
         n, D = self.n, self.D
         if int(n_iter) - int(burn_in) <= 0:
             raise ValueError("BurnIn must be < NumOfIterations")
@@ -353,7 +407,10 @@ class Context:
                                            _ptr(th), smp.data_ptr(), acc.data_ptr(), steps.data_ptr(), C.cast(C.byref(secs), _dp)))
         return smp, acc, steps, secs.value
 
-    def sample_stats_dev(self, device, n_iter, burn_in, L=6, eps=0.5, K=4, seed=0, chain_offset=0, theta0=None):
+    def sample_stats_dev(self, device, n_iter, burn_in, L=6, eps=0.5, K=4, seed=0, chain_offset=0, theta0=None, run_mean=False):
+        if run_mean:  # (include/rmhmc_out.h)
+            return self.sample_to("rmhmc", n_iter, burn_in, where="device", device=device, stats=True, run_mean=True, L=L, eps=eps, K=K,
+                                  seed=seed, chain_offset=chain_offset, theta0=theta0)
         import torch
         n, D = self.n, self.D
         if int(n_iter) - int(burn_in) <= 0:
@@ -512,6 +569,161 @@ class Context:
         self._ck(self.lib.rmhmc_gibbs_replay(self._h, Tn, _ptr(u_init), _ptr(u_sweep), _ptr(T), _ptr(ks_draws), _ptr(ks_offset, _lp), total,
                                              _ptr(beta), _ptr(B), _ptr(att, _ip), _ptr(Z), _ptr(lam), _ptr(capped, _lp), _ptr(status, _ip)))
         return dict(beta=beta, B=B, attempts=att, Z=Z, lam=lam, capped=capped, status=status)
+
+    # ---- output descriptor: every sampler to host or device memory, raw or reduced (include/rmhmc_out.h) ----------
+    def _need_out(self):
+        if not self.rl.has_out:
+            raise RmhmcError(-4, "%s does not export the output descriptor (include/rmhmc_out.h)" % self.rl.path)
+
+    def sample_to(self, sampler, n_iter, burn_in, *, where="host", device=None, samples=False, stats=False, run_mean=False,
+                  L=None, eps=None, K=None, compat=None, seed=0, chain_offset=0, theta0=None):
+        """One run of `sampler` (a key of SAMPLERS_TO) written out as asked: samples [n][S][D]; stats: mean, var, ess [n][D]; run_mean:
+        run_mean [S][D] and run_ess [D].  where="host": NumPy arrays; "device": torch tensors on `device`, the samples written by the
+        sampler itself.  Returns a dict of the requested outputs, the sampler's counters (same memory space) and `seconds`.  The run
+        arguments are those of the sampler's own method, with its defaults (L, eps, K, compat where it has them); one the sampler does
+        not have (theta0 for Gibbs included) is a ValueError.  The library works on a stream of its own: torch's current stream on
+        `device` is synchronised before the call, and the library's is idle on return."""
+        self._need_out()
+        name, counters = SAMPLERS_TO[sampler]
+        given = dict(L=L, eps=eps, K=K, compat=compat, theta0=theta0)
+        extra = sorted(k for k, v in given.items() if v is not None and k not in SAMPLER_ARGS[sampler])
+        if extra:
+            raise ValueError("sampler %r has no run argument %s" % (sampler, ", ".join(extra)))
+        n, D = self.n, self.D
+        n_iter, burn_in = int(n_iter), int(burn_in)
+        S = n_iter - burn_in
+        if S <= 0 or burn_in < 0:
+            raise ValueError("need 0 <= burn_in < n_iter")
+        dev = where in ("device", OUT_DEVICE)
+        if dev:
+            import torch
+            if device is None:
+                raise ValueError('where="device" needs the torch device of the context\'s GPU')
+            device = torch.device(device)
+            if self.rl.on_gpu and device.type != "cuda":
+                raise ValueError("the HIP library writes through device pointers: %s is not a GPU" % device)
+
+        def buf(shape, dtype=np.float64):
+            if dev:
+                # (empty: the library writes every output and counter it is handed, and a fill would run on torch's stream)
+                b = torch.empty(shape, dtype=torch.int64 if dtype is np.int64 else torch.float64, device=device)
+                return b, b.data_ptr()
+            b = np.zeros(shape, dtype=dtype)
+            return b, b.ctypes.data
+
+        res = {}
+        o = Out(where={"host": OUT_HOST, "device": OUT_DEVICE}.get(where, where))
+        want = ([("samples", (n, S, D))] if samples else []) + ([(k, (n, D)) for k in ("mean", "var", "ess")] if stats else []) \
+            + ([("run_mean", (S, D)), ("run_ess", (D,))] if run_mean else [])
+        for key, shape in want:
+            res[key], ptr = buf(shape)
+            setattr(o, key, ptr)
+        cptr = []
+        for key, vec in counters:
+            res[key], ptr = buf((n, D) if vec else (n,), np.float64 if vec else np.int64)
+            cptr.append(ptr)
+        th = None if theta0 is None else _f64(np.broadcast_to(theta0, (n, D)))
+        tail = (int(seed), int(chain_offset)) + (() if sampler == "gibbs" else (_ptr(th),))
+        if sampler == "rmhmc":
+            front = (int(6 if L is None else L), float(0.5 if eps is None else eps), int(4 if K is None else K))
+        elif sampler == "hmc":
+            front = (int(100 if L is None else L), float(0.14 if eps is None else eps))
+        elif sampler == "mmala":
+            front = (float(1.0 if eps is None else eps),)
+        elif sampler == "iwls":
+            front = (1 if compat or compat is None else 0,)
+        else:
+            front = ()
+        secs = C.c_double(0.0)
+        if dev and device.type == "cuda":
+            torch.cuda.current_stream(device).synchronize()   # nothing of torch's is pending on the buffers the library is handed
+        self._ck(getattr(self.lib, name)(self._h, n_iter, burn_in, *front, *tail, C.byref(o), *cptr, C.cast(C.byref(secs), _dp)))
+        res["seconds"] = secs.value
+        return res
+
+    def ess_dev(self, samples):
+        """ESS, mean and population variance of a torch tensor [n][S][P] (or [S][P]) already on the context's GPU, reduced there: returns
+        (ess, mean, var) tensors [n][P] on the same device.  torch's current stream on that device is synchronised first: the
+        library reads the tensor at once on a stream of its own, so whatever produced it must have finished."""
+        import torch
+        self._need_out()
+        if self.rl.on_gpu and not samples.is_cuda:
+            raise ValueError("ess_dev: a tensor on the context's GPU is required")
+        x = samples.contiguous()
+        if x.dtype != torch.float64:
+            raise ValueError("ess_dev: float64 tensor required")
+        if x.dim() == 2:
+            x = x[None]
+        n, S, P = x.shape
+        ess, mean, var = self._out_tensors([((n, P), torch.float64)] * 3, x.device)
+        if x.is_cuda:
+            torch.cuda.current_stream(x.device).synchronize()
+        self._ck(self.lib.rmhmc_ess_dev(self._h, x.data_ptr(), n, S, P, ess.data_ptr(), mean.data_ptr(), var.data_ptr()))
+        return ess, mean, var
+
+    # the three output modes of RMHMC (sample_dev, sample_stats, sample_stats_dev above) for the other five samplers: *_sample_dev
+    # returns what *_sample returns with the arrays as tensors on `device`; *_sample_stats[_dev] return dict(mean, var, ess, the
+    # sampler's counters, seconds), run_mean=True adds run_mean and run_ess
+    def hmc_sample_dev(self, device, n_iter, burn_in, L=100, eps=0.14, seed=0, chain_offset=0, theta0=None):
+        r = self.sample_to("hmc", n_iter, burn_in, where="device", device=device, samples=True, L=L, eps=eps, seed=seed,
+                           chain_offset=chain_offset, theta0=theta0)
+        return r["samples"], r["accepted"], r["leapfrog_steps"], r["seconds"]
+
+    def hmc_sample_stats(self, n_iter, burn_in, L=100, eps=0.14, seed=0, chain_offset=0, theta0=None, run_mean=False):
+        return self.sample_to("hmc", n_iter, burn_in, stats=True, run_mean=run_mean, L=L, eps=eps, seed=seed, chain_offset=chain_offset,
+                              theta0=theta0)
+
+    def hmc_sample_stats_dev(self, device, n_iter, burn_in, L=100, eps=0.14, seed=0, chain_offset=0, theta0=None, run_mean=False):
+        return self.sample_to("hmc", n_iter, burn_in, where="device", device=device, stats=True, run_mean=run_mean, L=L, eps=eps,
+                              seed=seed, chain_offset=chain_offset, theta0=theta0)
+
+    def mmala_sample_dev(self, device, n_iter, burn_in, eps=1.0, seed=0, chain_offset=0, theta0=None):
+        r = self.sample_to("mmala", n_iter, burn_in, where="device", device=device, samples=True, eps=eps, seed=seed,
+                           chain_offset=chain_offset, theta0=theta0)
+        return r["samples"], r["accepted"], r["seconds"]
+
+    def mmala_sample_stats(self, n_iter, burn_in, eps=1.0, seed=0, chain_offset=0, theta0=None, run_mean=False):
+        return self.sample_to("mmala", n_iter, burn_in, stats=True, run_mean=run_mean, eps=eps, seed=seed, chain_offset=chain_offset,
+                              theta0=theta0)
+
+    def mmala_sample_stats_dev(self, device, n_iter, burn_in, eps=1.0, seed=0, chain_offset=0, theta0=None, run_mean=False):
+        return self.sample_to("mmala", n_iter, burn_in, where="device", device=device, stats=True, run_mean=run_mean, eps=eps, seed=seed,
+                              chain_offset=chain_offset, theta0=theta0)
+
+    def amh_sample_dev(self, device, n_iter, burn_in, seed=0, chain_offset=0, theta0=None):
+        r = self.sample_to("amh", n_iter, burn_in, where="device", device=device, samples=True, seed=seed, chain_offset=chain_offset,
+                           theta0=theta0)
+        return r["samples"], r["accepted"], r["sd"], r["seconds"]
+
+    def amh_sample_stats(self, n_iter, burn_in, seed=0, chain_offset=0, theta0=None, run_mean=False):
+        return self.sample_to("amh", n_iter, burn_in, stats=True, run_mean=run_mean, seed=seed, chain_offset=chain_offset, theta0=theta0)
+
+    def amh_sample_stats_dev(self, device, n_iter, burn_in, seed=0, chain_offset=0, theta0=None, run_mean=False):
+        return self.sample_to("amh", n_iter, burn_in, where="device", device=device, stats=True, run_mean=run_mean, seed=seed,
+                              chain_offset=chain_offset, theta0=theta0)
+
+    def iwls_sample_dev(self, device, n_iter, burn_in, compat=True, seed=0, chain_offset=0, theta0=None):
+        r = self.sample_to("iwls", n_iter, burn_in, where="device", device=device, samples=True, compat=compat, seed=seed,
+                           chain_offset=chain_offset, theta0=theta0)
+        return r["samples"], r["accepted"], r["saturated"], r["seconds"]
+
+    def iwls_sample_stats(self, n_iter, burn_in, compat=True, seed=0, chain_offset=0, theta0=None, run_mean=False):
+        return self.sample_to("iwls", n_iter, burn_in, stats=True, run_mean=run_mean, compat=compat, seed=seed, chain_offset=chain_offset,
+                              theta0=theta0)
+
+    def iwls_sample_stats_dev(self, device, n_iter, burn_in, compat=True, seed=0, chain_offset=0, theta0=None, run_mean=False):
+        return self.sample_to("iwls", n_iter, burn_in, where="device", device=device, stats=True, run_mean=run_mean, compat=compat,
+                              seed=seed, chain_offset=chain_offset, theta0=theta0)
+
+    def gibbs_sample_dev(self, device, n_iter, burn_in, seed=0, chain_offset=0):
+        return self.sample_to("gibbs", n_iter, burn_in, where="device", device=device, samples=True, seed=seed, chain_offset=chain_offset)
+
+    def gibbs_sample_stats(self, n_iter, burn_in, seed=0, chain_offset=0, run_mean=False):
+        return self.sample_to("gibbs", n_iter, burn_in, stats=True, run_mean=run_mean, seed=seed, chain_offset=chain_offset)
+
+    def gibbs_sample_stats_dev(self, device, n_iter, burn_in, seed=0, chain_offset=0, run_mean=False):
+        return self.sample_to("gibbs", n_iter, burn_in, where="device", device=device, stats=True, run_mean=run_mean, seed=seed,
+                              chain_offset=chain_offset)
 
     def chains_init(self, theta0=None, seed=0, chain_offset=0, L=6, eps=0.5, K=4):
         th = None if theta0 is None else _f64(np.broadcast_to(theta0, (self.n, self.D)))

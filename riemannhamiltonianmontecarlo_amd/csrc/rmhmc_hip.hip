@@ -9,6 +9,7 @@
 #include "../../include/rmhmc_amh.h"
 #include "../../include/rmhmc_iwls.h"
 #include "../../include/rmhmc_gibbs.h"
+#include "../../include/rmhmc_out.h"
 #include "plan.h"
 #include "kernels.hip.h"
 #include "fused_small.hip.h"
@@ -18,6 +19,7 @@
 #include "amh.hip.h"
 #include "iwls.hip.h"
 #include "gibbs.hip.h"
+#include "output.hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -127,6 +129,7 @@ struct rmhmc_ctx : Plan {
   void* progress_user = nullptr;
   long long progress_first = 0, progress_every = 0;
   // timing
+  double write_out_seconds = 0.0;  // host wall time of the last write_out (rmhmc_kernel_time "write_out", include/rmhmc_out.h)
   bool timing = false;
   std::map<std::string, std::vector<EvPair>> events;
   std::vector<EvPair> pool;
@@ -1692,6 +1695,29 @@ int rmhmc_hmc_transition(rmhmc_ctx* ctx, double* w, const double* z, const doubl
   return RMHMC_OK;
 }
 
+// Runs the plain HMC sampler; the saved states go to the device buffer d_samples ([n][S][D]).  It leaves the accepted proposals in
+// batch.ch.accepted and the leapfrog steps in batch.ch.steps_done, d_steps0 holding their value at the end of burn-in.
+static int hmc_sample_core(rmhmc_ctx* ctx, const Run& run, int64_t n_iter, int64_t burn_in, const double* theta0, double* d_samples, double* seconds_out) {
+  const long long S = n_iter - burn_in;
+  long long progress_next = ctx->progress_first;
+  RC(hmc_init_chains(ctx, theta0));
+  const IterBase ipA{burn_in + 1, burn_in, S, d_samples, false, true};
+  RC(run_phase(ctx, run, ipA, 0, &progress_next, false, true));
+  HIPCK(hipMemcpyAsync(ctx->d_steps0, ctx->batch.ch.steps_done, sizeof(long long) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
+  HIPCK(hipMemsetAsync(ctx->d_done, 0, sizeof(int), ctx->stream));
+  RC(sync(ctx));
+  if (ctx->progress_fn) RC(report_progress(ctx, RMHMC_EV_BURNIN_DONE, burn_in + 1));  // hmc.py:92-94
+  const auto t0 = std::chrono::steady_clock::now();
+  if (n_iter > burn_in + 1) {
+    // hmc.py:83-89 reports during burn-in only (`elif` of the save branch): no milestones, hence no cuts, inside TimeTaken
+    const IterBase ipB{n_iter, burn_in, S, d_samples, false, true};
+    RC(run_phase(ctx, run, ipB, burn_in + 1, nullptr));
+  }
+  RC(sync(ctx));
+  if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return RMHMC_OK;
+}
+
 int rmhmc_hmc_sample(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L, double eps, uint64_t seed, int64_t chain_offset,
                      const double* theta0, double* samples_out, int64_t* accept_out, int64_t* steps_out, double* seconds_out) {
   NEED_DATA(ctx);
@@ -1702,23 +1728,8 @@ int rmhmc_hmc_sample(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L,
   const long long S = n_iter - burn_in;
   double* d_samples = nullptr;
   HIPCK(hipMalloc((void**)&d_samples, sizeof(double) * (size_t)ctx->n * S * ctx->D));
-  long long progress_next = ctx->progress_first;
   int rc = [&]() -> int {
-    RC(hmc_init_chains(ctx, theta0));
-    const IterBase ipA{burn_in + 1, burn_in, S, d_samples, false, true};
-    RC(run_phase(ctx, run, ipA, 0, &progress_next, false, true));
-    HIPCK(hipMemcpyAsync(ctx->d_steps0, ctx->batch.ch.steps_done, sizeof(long long) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCK(hipMemsetAsync(ctx->d_done, 0, sizeof(int), ctx->stream));
-    RC(sync(ctx));
-    if (ctx->progress_fn) RC(report_progress(ctx, RMHMC_EV_BURNIN_DONE, burn_in + 1));  // hmc.py:92-94
-    const auto t0 = std::chrono::steady_clock::now();
-    if (n_iter > burn_in + 1) {
-      // hmc.py:83-89 reports during burn-in only (`elif` of the save branch): no milestones, hence no cuts, inside TimeTaken
-      const IterBase ipB{n_iter, burn_in, S, d_samples, false, true};
-      RC(run_phase(ctx, run, ipB, burn_in + 1, nullptr));
-    }
-    RC(sync(ctx));
-    if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    RC(hmc_sample_core(ctx, run, n_iter, burn_in, theta0, d_samples, seconds_out));
     HIPCK(hipMemcpyAsync(samples_out, d_samples, sizeof(double) * (size_t)ctx->n * S * ctx->D, hipMemcpyDeviceToHost, ctx->stream));
     std::vector<long long> a(ctx->n), s1(ctx->n), s0(ctx->n);
     RC(download(ctx, a.data(), ctx->batch.ch.accepted, ctx->n));
@@ -1774,6 +1785,20 @@ int rmhmc_mmala_transition(rmhmc_ctx* ctx, double* w, const double* z, const dou
   return RMHMC_OK;
 }
 
+// Runs the simplified mMALA sampler; the saved states go to the device buffer d_samples ([n][S][D]), the accepted proposals stay in
+// batch.ch.accepted.
+static int mmala_sample_core(rmhmc_ctx* ctx, const Run& run, int64_t n_iter, int64_t burn_in, const double* theta0, double* d_samples, double* seconds_out) {
+  RC(mmala_init(ctx, theta0));
+  const IterBase ib{n_iter, burn_in, n_iter - burn_in, d_samples, false, false};
+  for (int64_t it = 0; it <= burn_in; ++it) { launch_mmala_step(ctx, run, ctx->batch, ib); flow_tick(ctx); }
+  RC(sync(ctx));
+  const auto t0 = std::chrono::steady_clock::now();
+  for (int64_t it = burn_in + 1; it < n_iter; ++it) { launch_mmala_step(ctx, run, ctx->batch, ib); flow_tick(ctx); }
+  RC(sync(ctx));
+  if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return RMHMC_OK;
+}
+
 int rmhmc_mmala_sample(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, double eps, uint64_t seed, int64_t chain_offset,
                        const double* theta0, double* samples_out, int64_t* accept_out, double* seconds_out) {
   NEED_DATA(ctx);
@@ -1785,14 +1810,7 @@ int rmhmc_mmala_sample(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, double e
   double* d_samples = nullptr;
   HIPCK(hipMalloc((void**)&d_samples, sizeof(double) * (size_t)ctx->n * S * ctx->D));
   int rc = [&]() -> int {
-    RC(mmala_init(ctx, theta0));
-    const IterBase ib{n_iter, burn_in, S, d_samples, false, false};
-    for (int64_t it = 0; it <= burn_in; ++it) { launch_mmala_step(ctx, run, ctx->batch, ib); flow_tick(ctx); }
-    RC(sync(ctx));
-    const auto t0 = std::chrono::steady_clock::now();
-    for (int64_t it = burn_in + 1; it < n_iter; ++it) { launch_mmala_step(ctx, run, ctx->batch, ib); flow_tick(ctx); }
-    RC(sync(ctx));
-    if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    RC(mmala_sample_core(ctx, run, n_iter, burn_in, theta0, d_samples, seconds_out));
     HIPCK(hipMemcpyAsync(samples_out, d_samples, sizeof(double) * (size_t)ctx->n * S * ctx->D, hipMemcpyDeviceToHost, ctx->stream));
     if (accept_out) {
       static_assert(sizeof(long long) == sizeof(int64_t), "int64");
@@ -1882,6 +1900,11 @@ int rmhmc_kernel_time(rmhmc_ctx* ctx, const char* which, double* seconds_out, in
   if (launches_out) *launches_out = 0;
   if (w == "enable") { ctx->timing = true; return RMHMC_OK; }
   if (w == "disable") { ctx->timing = false; return RMHMC_OK; }
+  if (w == "write_out") {  // (include/rmhmc_out.h)
+    if (seconds_out) *seconds_out = ctx->write_out_seconds;
+    if (launches_out) *launches_out = 1;
+    return RMHMC_OK;
+  }
   if (w == "reset") {
     RC(sync(ctx));
     for (auto& kv : ctx->events) { for (auto& e : kv.second) ctx->pool.push_back(e); kv.second.clear(); }
@@ -2359,6 +2382,202 @@ int rmhmc_gibbs_replay(rmhmc_ctx* ctx, int64_t n_iter, const double* u_init, con
   for (void* q : {(void*)d_ui, (void*)d_us, (void*)d_T, (void*)d_ks, (void*)d_off, (void*)d_beta, (void*)d_B, (void*)d_att}) if (q) (void)hipFree(q);
   gibbs_free(s);
   return rc;
+}
+
+}  // extern "C"
+
+// ---- output descriptor: every sampler to host or device memory, raw or reduced (include/rmhmc_out.h, output.hip.h) ------------------
+namespace {
+
+hipMemcpyKind out_kind(const rmhmc_out& out) { return out.where == RMHMC_OUT_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost; }
+bool out_stats(const rmhmc_out& out) { return out.mean || out.var || out.ess || out.run_mean || out.run_ess; }
+
+// the refusals of a descriptor, before any sampling work; S: samples per chain of the call
+int out_check(rmhmc_ctx* ctx, const rmhmc_out* out, int64_t S) {
+  if (!out) return fail(ctx, RMHMC_ERR_INVALID, "sample_to: NULL output descriptor");
+  if (out->where != RMHMC_OUT_HOST && out->where != RMHMC_OUT_DEVICE)
+    return fail(ctx, RMHMC_ERR_INVALID, "sample_to: where must be RMHMC_OUT_HOST or RMHMC_OUT_DEVICE");
+  if (!out->samples && !out_stats(*out)) return fail(ctx, RMHMC_ERR_INVALID, "sample_to: the output descriptor requests no output");
+  if (out_stats(*out) && (S < 2 || S > 20000))
+    return fail(ctx, RMHMC_ERR_UNSUPPORTED, "sample_to: statistics need 2 <= n_iter - burn_in <= 20000 (the ESS kernel holds one series in LDS)");
+  return RMHMC_OK;
+}
+
+// The write-out of a call: d_samples [n][S][D] in device memory -> whatever `out` requests, copied or reduced.  Returns with the
+// stream idle and its own buffers freed.  Its wall time (the sampler has synchronised: the stream holds the counter copies at most) is
+// kept for rmhmc_kernel_time "write_out".
+int write_out(rmhmc_ctx* ctx, const double* d_samples, size_t n, size_t S, size_t D, const rmhmc_out& out) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const hipMemcpyKind kind = out_kind(out);
+  const size_t nd = n * D, sd = S * D;
+  double* d_st = nullptr;  // [3][n][D]: ess, mean, var
+  double* d_rm = nullptr;  // [S][D] run mean, then [D] its ess
+  const int rc = [&]() -> int {
+    if (out.samples && out.samples != d_samples) HIPCK(hipMemcpyAsync(out.samples, d_samples, sizeof(double) * n * sd, kind, ctx->stream));
+    if (out.mean || out.var || out.ess) {
+      HIPCK(hipMalloc((void**)&d_st, sizeof(double) * 3 * nd));
+      RC(launch_ess(ctx, d_samples, (long long)n, (long long)S, (int)D, d_st, d_st + nd, d_st + 2 * nd));
+      if (out.ess) HIPCK(hipMemcpyAsync(out.ess, d_st, sizeof(double) * nd, kind, ctx->stream));
+      if (out.mean) HIPCK(hipMemcpyAsync(out.mean, d_st + nd, sizeof(double) * nd, kind, ctx->stream));
+      if (out.var) HIPCK(hipMemcpyAsync(out.var, d_st + 2 * nd, sizeof(double) * nd, kind, ctx->stream));
+    }
+    if (out.run_mean || out.run_ess) {
+      HIPCK(hipMalloc((void**)&d_rm, sizeof(double) * (sd + D)));
+      hipLaunchKernelGGL(k_run_mean, dim3((unsigned)((sd + 255) / 256)), dim3(256), 0, ctx->stream, d_samples, n, sd, d_rm);
+      if (out.run_ess) RC(launch_ess(ctx, d_rm, 1, (long long)S, (int)D, d_rm + sd, nullptr, nullptr));
+      if (out.run_mean) HIPCK(hipMemcpyAsync(out.run_mean, d_rm, sizeof(double) * sd, kind, ctx->stream));
+      if (out.run_ess) HIPCK(hipMemcpyAsync(out.run_ess, d_rm + sd, sizeof(double) * D, kind, ctx->stream));
+    }
+    return sync(ctx);
+  }();
+  ctx->write_out_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  if (d_st) (void)hipFree(d_st);
+  if (d_rm) (void)hipFree(d_rm);
+  return rc;
+}
+
+// a per-chain counter to the memory space of the descriptor (dst may be NULL)
+template <typename T>
+int counter_out(rmhmc_ctx* ctx, const rmhmc_out& out, int64_t* dst, const T* src) {
+  static_assert(sizeof(T) == sizeof(int64_t), "int64");
+  if (dst) HIPCK(hipMemcpyAsync(dst, src, sizeof(int64_t) * ctx->n, out_kind(out), ctx->stream));
+  return RMHMC_OK;
+}
+
+// One *_sample_to call after its argument checks.  core(d_samples) runs the sampler into d_samples [n][S][D] and queues its counter
+// copies; the samples go straight into the caller's buffer where that is device memory, into a buffer of the call's otherwise.
+template <typename F>
+int sample_to(rmhmc_ctx* ctx, int64_t S, const rmhmc_out& out, F&& core) {
+  const size_t n = ctx->n, D = ctx->D;
+  const bool direct = out.where == RMHMC_OUT_DEVICE && out.samples;
+  double* d_samples = direct ? out.samples : nullptr;
+  if (!direct) HIPCK(hipMalloc((void**)&d_samples, sizeof(double) * n * (size_t)S * D));
+  const int rc = [&]() -> int {
+    RC(core(d_samples));
+    return write_out(ctx, d_samples, n, (size_t)S, D, out);
+  }();
+  if (!direct) (void)hipFree(d_samples);
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rmhmc_sample_to(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L, double eps, int32_t K, uint64_t seed, int64_t chain_offset,
+                    const double* theta0, const rmhmc_out* out, int64_t* accept_out, int64_t* steps_out, double* seconds_out) {
+  NEED_DATA(ctx);
+  if (burn_in < 0 || burn_in >= n_iter || L < 1 || K < 1)
+    return fail(ctx, RMHMC_ERR_INVALID, "sample_to: need 0 <= burn_in < n_iter, L >= 1, K >= 1");
+  RC(out_check(ctx, out, n_iter - burn_in));
+  ctx->chains_ready = false;
+  const Run run{RMHMC, L, K, eps, seed, chain_offset, nullptr};
+  return sample_to(ctx, n_iter - burn_in, *out, [&](double* d_samples) -> int {
+    Counters counters{};
+    RC(sample_core(ctx, run, n_iter, burn_in, theta0, d_samples, seconds_out, &counters));
+    return sample_counters(ctx, counters, accept_out, steps_out, out_kind(*out));
+  });
+}
+
+int rmhmc_hmc_sample_to(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L, double eps, uint64_t seed, int64_t chain_offset,
+                        const double* theta0, const rmhmc_out* out, int64_t* accept_out, int64_t* steps_out, double* seconds_out) {
+  NEED_DATA(ctx);
+  if (burn_in < 0 || burn_in >= n_iter || L < 1) return fail(ctx, RMHMC_ERR_INVALID, "hmc_sample_to: need 0 <= burn_in < n_iter, L >= 1");
+  RC(out_check(ctx, out, n_iter - burn_in));
+  ctx->chains_ready = false;
+  const Run run{HMC, L, 0, eps, seed, chain_offset, nullptr};  // (no fixed-point iterations: no K)
+  return sample_to(ctx, n_iter - burn_in, *out, [&](double* d_samples) -> int {
+    RC(hmc_sample_core(ctx, run, n_iter, burn_in, theta0, d_samples, seconds_out));
+    // d_steps0 = steps_done - d_steps0: the post-burn-in steps, the subtraction rmhmc_hmc_sample does on the host
+    hipLaunchKernelGGL(k_sub_ll, dim3((unsigned)((ctx->n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_steps0, ctx->batch.ch.steps_done, (size_t)ctx->n);
+    RC(counter_out(ctx, *out, accept_out, ctx->batch.ch.accepted));
+    return counter_out(ctx, *out, steps_out, ctx->d_steps0);
+  });
+}
+
+int rmhmc_mmala_sample_to(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, double eps, uint64_t seed, int64_t chain_offset,
+                          const double* theta0, const rmhmc_out* out, int64_t* accept_out, double* seconds_out) {
+  NEED_DATA(ctx);
+  if (burn_in < 0 || burn_in >= n_iter || !(eps > 0)) return fail(ctx, RMHMC_ERR_INVALID, "mmala_sample_to: need 0 <= burn_in < n_iter, eps > 0");
+  RC(out_check(ctx, out, n_iter - burn_in));
+  ctx->chains_ready = false;
+  const Run run{RMHMC, 0, 0, eps, seed, chain_offset, nullptr};
+  return sample_to(ctx, n_iter - burn_in, *out, [&](double* d_samples) -> int {
+    RC(mmala_sample_core(ctx, run, n_iter, burn_in, theta0, d_samples, seconds_out));
+    return counter_out(ctx, *out, accept_out, ctx->batch.ch.accepted);
+  });
+}
+
+int rmhmc_amh_sample_to(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, uint64_t seed, int64_t chain_offset, const double* theta0,
+                        const rmhmc_out* out, int64_t* accepted_out, double* sd_out, double* seconds_out) {
+  NEED_DATA(ctx);
+  if (!amh_iters_ok(n_iter, burn_in) || chain_offset < 0)
+    return fail(ctx, RMHMC_ERR_INVALID, "amh_sample_to: need 0 <= burn_in < n_iter < 2^32, chain_offset >= 0");
+  RC(out_check(ctx, out, n_iter - burn_in));
+  ctx->chains_ready = false;
+  return sample_to(ctx, n_iter - burn_in, *out, [&](double* d_samples) -> int {
+    AmhParams p{};
+    p.samples = d_samples; p.seed = seed; p.chain_offset = chain_offset; p.n_iter = n_iter; p.burn_in = burn_in;
+    RC(amh_run(ctx, p, theta0, seconds_out));
+    RC(counter_out(ctx, *out, accepted_out, ctx->batch.ch.accepted));
+    if (sd_out)  // [n][DP] -> [n][D]
+      HIPCK(hipMemcpy2DAsync(sd_out, ctx->D * sizeof(double), ctx->batch.ch.PM, ctx->DP * sizeof(double), ctx->D * sizeof(double), ctx->n,
+                             out_kind(*out), ctx->stream));
+    return RMHMC_OK;
+  });
+}
+
+int rmhmc_iwls_sample_to(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t compat, uint64_t seed, int64_t chain_offset,
+                         const double* theta0, const rmhmc_out* out, int64_t* accepted_out, int64_t* saturated_out, double* seconds_out) {
+  NEED_DATA(ctx);
+  if (!amh_iters_ok(n_iter, burn_in) || chain_offset < 0)
+    return fail(ctx, RMHMC_ERR_INVALID, "iwls_sample_to: need 0 <= burn_in < n_iter < 2^32, chain_offset >= 0");
+  RC(out_check(ctx, out, n_iter - burn_in));
+  if (ctx->D > 64) return fail(ctx, RMHMC_ERR_UNSUPPORTED, kIwlsDMsg);
+  ctx->chains_ready = false;
+  const int64_t S = n_iter - burn_in;
+  IwlsState s;
+  const int rc = sample_to(ctx, S, *out, [&](double* d_samples) -> int {
+    IwlsParams p{};
+    RC(iwls_alloc(ctx, s, p, compat));
+    p.seed = seed; p.chain_offset = chain_offset; p.burn_in = burn_in; p.S = S; p.samples = d_samples; p.T = n_iter;
+    RC(iwls_run(ctx, p, n_iter, true, theta0, seconds_out));
+    RC(counter_out(ctx, *out, accepted_out, ctx->batch.ch.accepted));
+    return counter_out(ctx, *out, saturated_out, s.nsat);
+  });
+  iwls_free(s);
+  return rc;
+}
+
+int rmhmc_gibbs_sample_to(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, uint64_t seed, int64_t chain_offset, const rmhmc_out* out,
+                          int64_t* capped_out, int64_t* stopped_out, double* seconds_out) {
+  NEED_DATA(ctx);
+  if (!amh_iters_ok(n_iter, burn_in) || chain_offset < 0 || chain_offset + ctx->n > (int64_t)1 << 32)
+    return fail(ctx, RMHMC_ERR_INVALID, "gibbs_sample_to: need 0 <= burn_in < n_iter < 2^32, 0 <= chain_offset, chain_offset + n <= 2^32");
+  RC(out_check(ctx, out, n_iter - burn_in));
+  if (ctx->D > 64) return fail(ctx, RMHMC_ERR_UNSUPPORTED, kGibbsDMsg);
+  ctx->chains_ready = false;
+  const int64_t S = n_iter - burn_in;
+  GibbsState s;
+  const int rc = sample_to(ctx, S, *out, [&](double* d_samples) -> int {
+    HIPCK(hipMemsetAsync(d_samples, 0xff, sizeof(double) * (size_t)ctx->n * (size_t)S * ctx->D, ctx->stream));  // NaN: the rows a stopped chain never writes
+    GibbsParams p{};
+    RC(gibbs_alloc(ctx, s, p));
+    p.seed = seed; p.chain_offset = chain_offset; p.burn_in = burn_in; p.S = S; p.samples = d_samples; p.T = n_iter;
+    RC(gibbs_run(ctx, p, n_iter, true, seconds_out));
+    RC(counter_out(ctx, *out, capped_out, s.capped));
+    return counter_out(ctx, *out, stopped_out, s.dead);
+  });
+  gibbs_free(s);
+  return rc;
+}
+
+int rmhmc_ess_dev(rmhmc_ctx* ctx, const double* samples_dev, int64_t n, int64_t S, int32_t P, double* ess_dev, double* mean_dev, double* var_dev) {
+  if (!ctx || !samples_dev || (!ess_dev && !mean_dev && !var_dev) || n < 1 || P < 1 || n * (int64_t)P > 0x7fffffffLL)
+    return fail(ctx, RMHMC_ERR_INVALID, "ess_dev: bad argument");
+  HIPCK(hipSetDevice(ctx->device));
+  RC(launch_ess(ctx, samples_dev, n, S, P, ess_dev, mean_dev, var_dev));
+  return sync(ctx);
 }
 
 }  // extern "C"

@@ -37,6 +37,11 @@ def summarize(results_beta, results_time, nfft="python"):
     S = avg_beta_posterior.shape[0]
     ESS = tools.CalculateESS(avg_beta_posterior, S - 1, nfft)                            # main.py:71
     per_run = np.stack([tools.CalculateESS(results_beta[i], S - 1, nfft).ravel() for i in range(results_beta.shape[0])])
+    return _summary(avg_beta_posterior, avg_time_taken, ESS, per_run)
+
+
+def _summary(avg_beta_posterior, avg_time_taken, ESS, per_run):
+    """the dict of ``summarize`` from the run-mean chain (S, D), its ESS (D, 1) and the per-run ESS (n_runs, D)"""
     return {
         "avg_beta_posterior": avg_beta_posterior, "avg_time_taken": avg_time_taken, "ESS": ESS,
         "Min": float(np.min(ESS)), "Median": float(np.median(ESS)), "Mean": float(np.mean(ESS)), "Max": float(np.max(ESS)),
@@ -49,13 +54,24 @@ def summarize(results_beta, results_time, nfft="python"):
     }
 
 
-def run_experiment(XX, t, sampler="RMHMC", n_experiments=10, batched=False, seed=None, verbose=False, nfft="python", **sampler_kwargs):
+def run_experiment(XX, t, sampler="RMHMC", n_experiments=10, batched=False, seed=None, verbose=False, nfft="python", summary=False,
+                   **sampler_kwargs):
     """main.py:43-79.  Returns a dict with ``results_beta`` (n_experiments, S, D), ``results_time`` (n_experiments,) and the summary of
     ``summarize``.  ``sampler_kwargs`` go to the sampler (NumOfIterations, BurnIn, StepSize, compat, device, ...); the defaults are the
-    samplers' own, i.e. S = 5000 rows per run as main.py:46 hard-codes."""
+    samplers' own, i.e. S = 5000 rows per run as main.py:46 hard-codes.
+
+    summary=True (needs batched=True): the same summary from the reductions of the device (include/rmhmc_out.h: the run-mean chain,
+    its ESS and the per-run ESS, ``nfft`` selecting the FFT length there) - no raw sample leaves the GPU and ``results_beta`` is omitted."""
+    if summary and not batched:
+        raise ValueError("summary=True reduces the runs of one batched sampler call on the device: it needs batched=True")
     fn = SAMPLERS[sampler] if isinstance(sampler, str) else sampler
     if seed is None:
         seed = int(np.random.randint(0, 2 ** 62))
+    if summary:
+        st, secs = fn(XX, t, n_chains=n_experiments, seed=seed, verbose=verbose, summary=True, ess_nfft=nfft, **sampler_kwargs)
+        out = {"results_time": np.full(n_experiments, secs), "seed": seed, "sampler": getattr(fn, "__name__", str(fn))}
+        out.update(_summary(st["run_mean"], float(np.mean(out["results_time"])), st["run_ess"].reshape(-1, 1), st["ess"]))
+        return out
     if batched:
         smp, secs = fn(XX, t, n_chains=n_experiments, seed=seed, verbose=verbose, **sampler_kwargs)
         results_beta = smp if n_experiments > 1 else smp[None]

@@ -8,7 +8,7 @@ MI355X through rmhmc_iwls_sample (include/rmhmc_iwls.h); the metric is assembled
 (int8_slices).  compat=True (the default) is the reference: its jittered log-determinant term and the rejection of every proposal with a
 saturated row (W_j = 0, the reference's 0/0), which truncates the posterior to states without a row f_j > 36.7 (DESIGN section 8c);
 compat=False is the corrected sampler.  Every row of beta_saved is written (:84-85).  n_chains > 1 returns (n_chains, S, D);
-return_info adds the accepted and saturated proposals per chain, the acceptance rate and the seed.  No CPU fallback.
+return_info adds the accepted and saturated proposals per chain, the acceptance rate and the seed; summary / ess_nfft as for RMHMC.  No CPU fallback.
 """
 import numpy as np
 
@@ -26,7 +26,7 @@ def iwls_progress_printer():
 
 
 def iwls(XX, t, alpha=100, max_iter=10000, burn_in=5000, *, n_chains=1, seed=None, theta0=None, compat=True, int8_slices=None,
-         device=0, chain_offset=0, verbose=True, return_info=False, _lib=None):
+         device=0, chain_offset=0, verbose=True, return_info=False, summary=False, ess_nfft="matlab", _lib=None):
     """ IWLS METROPOLIS-HASTINGS (Bayesian logistic regression, N(0, alpha I) prior) """
     XX = np.ascontiguousarray(XX, dtype=np.float64)
     if XX.ndim != 2:
@@ -37,24 +37,30 @@ def iwls(XX, t, alpha=100, max_iter=10000, burn_in=5000, *, n_chains=1, seed=Non
         raise ValueError("t must have N entries")
     if not 0 <= burn_in < max_iter:
         raise ValueError("need 0 <= burn_in < max_iter")  # NameError in the reference (`start` unbound, iwls.py:88)
+    ess = _capi.ess_flags(ess_nfft)
     if seed is None:
         seed = int(np.random.randint(0, 2 ** 62))
     if verbose:
         print("--- Initialization...")
     lib = _lib if _lib is not None else _capi.load_hip_library()
-    flags = _capi.auto_metric_flags(D, n_chains, int8_slices, M=N)
+    flags = _capi.auto_metric_flags(D, n_chains, int8_slices, M=N) | ess
     with lib.context(N, D, n_chains, flags=flags, device=device) as ctx:
         ctx.set_data(XX, t, float(alpha))
         if verbose:
             print("--- Iterating...")
             # (rmhmc_iwls_sample reports on the reference's own schedule, include/rmhmc_iwls.h: the context's first / every are not used)
             ctx.set_progress(iwls_progress_printer())
-        samples, acc, sat, seconds = ctx.iwls_sample(max_iter, burn_in, compat=compat, seed=seed, chain_offset=chain_offset,
-                                                     theta0=theta0)
+        if summary:
+            st = ctx.iwls_sample_stats(max_iter, burn_in, compat=compat, seed=seed, chain_offset=chain_offset, theta0=theta0,
+                                       run_mean=True)
+            samples, acc, sat, seconds = None, st["accepted"], st["saturated"], st["seconds"]
+        else:
+            samples, acc, sat, seconds = ctx.iwls_sample(max_iter, burn_in, compat=compat, seed=seed, chain_offset=chain_offset,
+                                                         theta0=theta0)
     if verbose:
         print("--- Iterating: done.")
         print("Number of accepted samples: ", int(acc.sum()))
-    beta_saved = samples[0] if n_chains == 1 else samples
+    beta_saved = {k: st[k] for k in _capi.SUMMARY_KEYS} if summary else samples[0] if n_chains == 1 else samples
     if return_info:
         return beta_saved, seconds, dict(accepted=acc, saturated=sat, acceptance=acc / float(max_iter), seed=seed)
     return beta_saved, seconds

@@ -8,12 +8,19 @@ global chain id (``chain_offset``), so the samples do not depend on the number o
 exchange is the gather at write-out (``torch.distributed``: RCCL over xGMI for the ``nccl`` backend, gloo
 in the CPU tests), fed from device memory: the sampler writes its outputs through the ``_dev`` entry points of
 include/rmhmc.h into torch tensors in HBM and those tensors are what RCCL sends.  One process per GPU, launched by ``torch.distributed.run``.
+The other five samplers shard the same way through the output descriptor of include/rmhmc_out.h (``sampler=``).
 """
 import os
 
 import numpy as np
 
 from . import _capi
+from .experiment import SAMPLERS
+
+# experiment.SAMPLERS key -> (sampler of _capi.SAMPLERS_TO, it assembles a metric: the int8 auto-flag rule applies)
+_SHARDED = {"RMHMC": ("rmhmc", True), "HMC": ("hmc", False), "mMALA": ("mmala", True), "AMH": ("amh", False), "IWLS": ("iwls", True),
+            "Gibbs": ("gibbs", False)}
+assert set(_SHARDED) == set(SAMPLERS)
 
 
 def shard_range(n_total, world, rank):
@@ -85,7 +92,8 @@ def nanmin_rows(ess):
 
 
 def sample_sharded(XX, t, n_chains, NumOfIterations=6000, BurnIn=1000, NumOfLeapFrogSteps=6, StepSize=0.5,
-                   NumOfNewtonSteps=4, *, seed=0, compat=True, theta0=None, alpha=100.0, gather="samples", lib=None, options=None):
+                   NumOfNewtonSteps=4, *, seed=0, compat=True, theta0=None, alpha=100.0, gather="samples", lib=None, options=None,
+                   sampler="RMHMC", sampler_args=None):
     """Run ``n_chains`` chains sharded over the ranks of the initialised process group.
 
     gather="samples": rank 0 returns (samples [n_chains,S,D], seconds, info); other ranks return None.
@@ -95,13 +103,35 @@ def sample_sharded(XX, t, n_chains, NumOfIterations=6000, BurnIn=1000, NumOfLeap
     XX, t may be None on ranks other than 0: they are broadcast once from rank 0.
     ``lib`` is the loaded C-ABI library (default: the HIP library; the CPU tests inject the oracle); ``options``: tuning options of
     include/rmhmc.h for the contexts.
+    ``sampler``: a key of experiment.SAMPLERS.  "RMHMC" (the default) runs as described above.  Any other runs NumOfIterations / BurnIn
+    iterations through its *_sample_to entry point (include/rmhmc_out.h; HIP library only); NumOfLeapFrogSteps, StepSize,
+    NumOfNewtonSteps and ``compat`` are RMHMC's and do not apply: ``sampler_args`` carries the sampler's own run arguments as
+    _capi.Context.sample_to takes them (L, eps for HMC; eps for mMALA; compat for IWLS), its defaults otherwise.  ``info`` then holds the
+    sampler's own counters.  The int8 metric assembly is chosen as for RMHMC where the sampler assembles a metric (mMALA, IWLS).
     """
+    if sampler not in _SHARDED:   # (before any collective: every rank raises on its own)
+        raise ValueError("unknown sampler %r: one of %s" % (sampler, sorted(_SHARDED)))
+    if sampler == "RMHMC" and sampler_args:
+        raise ValueError("RMHMC takes its run arguments by name (NumOfLeapFrogSteps, StepSize, NumOfNewtonSteps), not in sampler_args")
+    if sampler != "RMHMC":
+        # everything a rank could raise on its own later: a rank with an empty shard would otherwise wait in a collective for one that raised
+        key = _SHARDED[sampler][0]
+        if gather not in ("samples", "summary"):
+            raise ValueError('gather must be "samples" or "summary"')
+        allowed = [k for k in _capi.SAMPLER_ARGS[key] if k != "theta0"]
+        bad = sorted(set(sampler_args or {}) - set(allowed))
+        if bad:
+            raise ValueError("sampler_args of %s may hold %s, not %s" % (sampler, allowed or "nothing", bad))
+        if theta0 is not None and "theta0" not in _capi.SAMPLER_ARGS[key]:
+            raise ValueError("the %s sampler has no theta0" % sampler)
     import torch as _t
     dist = _dist()
     rank, world = dist.get_rank(), dist.get_world_size()
     backend = dist.get_backend()
     local_rank = int(os.environ.get("LOCAL_RANK", rank))
     lib = lib if lib is not None else _capi.load_hip_library()
+    if sampler != "RMHMC" and not lib.has_out:   # (before the first collective as well)
+        raise _capi.RmhmcError(-4, "%s does not export the output descriptor (include/rmhmc_out.h): only RMHMC can be sharded" % lib.path)
     # where the collective runs (HBM for RCCL, host memory for gloo) and where the sampler writes its outputs: the HIP library always
     # writes through device pointers of its own GPU, whatever the backend; with gloo those tensors take one hop to the host first
     cdev = _t.device("cuda", local_rank) if backend == "nccl" else _t.device("cpu")
@@ -113,6 +143,9 @@ def sample_sharded(XX, t, n_chains, NumOfIterations=6000, BurnIn=1000, NumOfLeap
     counts = [shard_range(n_chains, world, r)[1] - shard_range(n_chains, world, r)[0] for r in range(world)]
     n_local = end - start
     S = NumOfIterations - BurnIn
+    if sampler != "RMHMC":
+        return _sharded_to(sampler, dict(sampler_args or {}), XX, t, n_chains, NumOfIterations, BurnIn, seed, theta0, alpha, gather, lib,
+                           options, gpu, odev, cdev, start, end, counts)
     if n_local > 0:
         th = None if theta0 is None else np.broadcast_to(theta0, (n_chains, D))[start:end]
         with lib.context(N, D, n_local, flags=(_capi.COMPAT if compat else 0) | _capi.auto_metric_flags(D, n_local, M=N), device=gpu,
@@ -150,3 +183,46 @@ def sample_sharded(XX, t, n_chains, NumOfIterations=6000, BurnIn=1000, NumOfLeap
         payload = dict(mean=g[:, :D], var=g[:, D:2 * D], min_ess=g[:, 2 * D])
     info = dict(accepted=cnt_all[:, 0], leapfrog_steps=cnt_all[:, 1], world=world, counts=counts)
     return payload, seconds, info
+
+
+def _sharded_to(sampler, args, XX, t, n_chains, n_iter, burn_in, seed, theta0, alpha, gather, lib, options, gpu, odev, cdev, start, end,
+                counts):
+    """sample_sharded for the samplers that run through include/rmhmc_out.h: same shards, same gathers, the sampler's own counters"""
+    import torch as _t
+    dist = _dist()
+    rank, world = dist.get_rank(), dist.get_world_size()
+    key, has_metric = _SHARDED[sampler]
+    N, D = XX.shape
+    n_local, S = end - start, n_iter - burn_in
+    counters = _capi.SAMPLERS_TO[key][1]
+    if n_local > 0:
+        if theta0 is not None:
+            args["theta0"] = np.broadcast_to(theta0, (n_chains, D))[start:end]
+        flags = _capi.auto_metric_flags(D, n_local, M=N) if has_metric else 0
+        with lib.context(N, D, n_local, flags=flags, device=gpu, options=options) as ctx:
+            ctx.set_data(XX, t, alpha)
+            st = ctx.sample_to(key, n_iter, burn_in, where="device", device=odev, samples=gather == "samples", stats=gather == "summary",
+                               seed=seed, chain_offset=start, **args)
+        secs = st["seconds"]
+        payload = st["samples"] if gather == "samples" else _t.cat([st["mean"], st["var"], nanmin_rows(st["ess"])], dim=1)
+        cnt = {k: st[k] for k, _ in counters}
+    else:
+        secs = 0.0
+        payload = _t.zeros((0, S, D) if gather == "samples" else (0, 2 * D + 1), dtype=_t.float64, device=odev)
+        cnt = {k: _t.zeros((0, D) if vec else (0,), dtype=_t.float64 if vec else _t.int64, device=odev) for k, vec in counters}
+    tt = _t.tensor([secs], dtype=_t.float64, device=cdev)
+    dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+    ints = [k for k, vec in counters if not vec]
+    cnt_all = _gather_rows(_t.stack([cnt[k] for k in ints], dim=1).to(cdev), counts)
+    vecs = {k: _gather_rows(cnt[k].to(cdev), counts) for k, vec in counters if vec}   # (AMH's final ProposalSD)
+    payload = _gather_rows(payload.to(cdev), counts)
+    if rank != 0:
+        return None
+    cnt_all = cnt_all.cpu().numpy()
+    g = payload.cpu().numpy()
+    if gather == "summary":
+        g = dict(mean=g[:, :D], var=g[:, D:2 * D], min_ess=g[:, 2 * D])
+    info = {k: cnt_all[:, i] for i, k in enumerate(ints)}
+    info.update({k: v.cpu().numpy() for k, v in vecs.items()})
+    info.update(world=world, counts=counts)
+    return g, float(tt.item()), info

@@ -23,6 +23,9 @@ Keyword-only extensions (defaults preserve the one-chain contract):
              path applies (8 < D <= 256) and there is enough work for its tiles (n_chains * N * D^2 >= 1e9), else fp64
   options    dict of the library's tuning options (include/rmhmc.h, rmhmc_create_opts), e.g. {"graph": 0}
   return_info  also return a dict(accepted=..., leapfrog_steps=...)
+  summary    True: no raw sample leaves the GPU (include/rmhmc_out.h); the first return value is dict(mean, var, ess (n_chains, D),
+             run_mean (S, D), run_ess (D,)) reduced on the device, always with the leading chain axis
+  ess_nfft   FFT-length convention of that ESS: "matlab" (default) or "python" (tools.py:23)
 
 Documented deviations: row 0 of wSaved is undefined in the reference (np.empty,
 never written: rmhmc.py:28,190-191); here it holds the state after iteration
@@ -57,7 +60,7 @@ def progress_printer(n_chains, hmc_burn_in=None):
 
 def RMHMC(XX, t, NumOfIterations=6000, BurnIn=1000, NumOfLeapFrogSteps=6, StepSize=0.5, NumOfNewtonSteps=4, *,
           n_chains=1, seed=None, compat=True, theta0=None, alpha=100.0, device=0, chain_offset=0, verbose=True,
-          return_info=False, int8_slices=None, options=None, _lib=None):
+          return_info=False, int8_slices=None, options=None, summary=False, ess_nfft="matlab", _lib=None):
     """ RIEMANNIAN HAMILTONIAN MONTE CARLO (Bayesian logistic regression, N(0, alpha I) prior) """
     XX = np.ascontiguousarray(XX, dtype=np.float64)
     if XX.ndim != 2:
@@ -69,20 +72,26 @@ def RMHMC(XX, t, NumOfIterations=6000, BurnIn=1000, NumOfLeapFrogSteps=6, StepSi
     if not BurnIn < NumOfIterations:
         # the reference raises NameError here (`start` unbound, rmhmc.py:194-198)
         raise ValueError("BurnIn must be smaller than NumOfIterations")
+    ess = _capi.ess_flags(ess_nfft)
     if seed is None:
         seed = int(np.random.randint(0, 2 ** 62))
     lib = _lib if _lib is not None else _capi.load_hip_library()
-    flags = (_capi.COMPAT if compat else 0) | _capi.auto_metric_flags(D, n_chains, int8_slices, M=N)
+    flags = (_capi.COMPAT if compat else 0) | _capi.auto_metric_flags(D, n_chains, int8_slices, M=N) | ess
     with lib.context(N, D, n_chains, flags=flags, device=device, options=options) as ctx:
         ctx.set_data(XX, t, alpha)
         if verbose:
             ctx.set_progress(progress_printer(n_chains))
-        samples, acc, steps, seconds = ctx.sample(NumOfIterations, BurnIn, NumOfLeapFrogSteps, StepSize,
-                                                  NumOfNewtonSteps, seed=seed, chain_offset=chain_offset,
-                                                  theta0=theta0)
+        if summary:
+            st = ctx.sample_stats(NumOfIterations, BurnIn, NumOfLeapFrogSteps, StepSize, NumOfNewtonSteps, seed=seed,
+                                  chain_offset=chain_offset, theta0=theta0, run_mean=True)
+            samples, acc, steps, seconds = None, st["accepted"], st["leapfrog_steps"], st["seconds"]
+        else:
+            samples, acc, steps, seconds = ctx.sample(NumOfIterations, BurnIn, NumOfLeapFrogSteps, StepSize,
+                                                      NumOfNewtonSteps, seed=seed, chain_offset=chain_offset,
+                                                      theta0=theta0)
     if verbose:
         print('Time drawing posterior: {}'.format(seconds))
-    wSaved = samples[0] if n_chains == 1 else samples
+    wSaved = {k: st[k] for k in _capi.SUMMARY_KEYS} if summary else samples[0] if n_chains == 1 else samples
     if return_info:
         return wSaved, seconds, dict(accepted=acc, leapfrog_steps=steps, seed=seed)
     return wSaved, seconds
