@@ -164,6 +164,28 @@ SAMPLER_ARGS = {"rmhmc": ("L", "eps", "K", "theta0"), "hmc": ("L", "eps", "theta
                 "iwls": ("compat", "theta0"), "gibbs": ()}
 SUMMARY_KEYS = ("mean", "var", "ess", "run_mean", "run_ess")
 
+# include/rmhmc_diag.h: split R-hat and the pooled ESS across chains, HIP library only as well
+_dpp = C.POINTER(_dp)
+DIAG_SIGNATURES = {
+    "rmhmc_diag_partial_dev": (C.c_int, [C.c_void_p, _vp, C.c_int64, C.c_int64, C.c_int32, C.c_int64, _vp]),
+    "rmhmc_diag_finish": (C.c_int, [_dpp, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp, _lp, _lp]),
+}
+DIAG_KEYS = ("rhat", "ess_pooled", "pairs", "chains_used")   # what diag_finish returns, [P] each
+DIAG_S_MIN, DIAG_S_MAX = 4, 20000
+
+
+def diag_lags(S, max_lag=None):
+    """(H, T) of a diagnostics call on S samples per chain: H = S // 2 rows per half chain, T = max_lag + 1 lags; max_lag None or 0:
+    every lag, H - 1.  ValueError outside what rmhmc_diag_partial_dev accepts."""
+    S = int(S)
+    if not DIAG_S_MIN <= S <= DIAG_S_MAX:
+        raise ValueError("diagnostics need %d <= S <= %d samples per chain (the centred series is held in LDS)" % (DIAG_S_MIN, DIAG_S_MAX))
+    H = S // 2
+    max_lag = 0 if max_lag is None else int(max_lag)
+    if not 0 <= max_lag <= H - 1:
+        raise ValueError("max_lag must be None or 0 (every lag) or 1 .. S // 2 - 1")
+    return H, (max_lag if max_lag else H - 1) + 1
+
 
 def ess_flags(ess_nfft):
     """context flags of the FFT-length convention of the device ESS: "matlab" (no wrap, the default) or "python" (tools.py:23)"""
@@ -225,6 +247,12 @@ class RmhmcLib:
                 fn = getattr(self.lib, name)
                 fn.restype = res
                 fn.argtypes = args
+        self.has_diag = all(hasattr(self.lib, name) for name in DIAG_SIGNATURES)
+        if self.has_diag:
+            for name, (res, args) in DIAG_SIGNATURES.items():
+                fn = getattr(self.lib, name)
+                fn.restype = res
+                fn.argtypes = args
         # the HIP library writes its _dev outputs through device pointers of its own GPU; the CPU oracle's "device" is the host
         self.on_gpu = "gfx950" in self.version()
 
@@ -242,6 +270,7 @@ class Context:
     def __init__(self, rl, M, D, n_chains, flags, device, options=None):
         self.rl, self.lib = rl, rl.lib
         self.M, self.D, self.n, self.flags = int(M), int(D), int(n_chains), int(flags)
+        self.device = int(device)
         self._h = C.c_void_p()
         if options:
             arr = (Option * len(options))(*[Option(str(k).encode(), int(v)) for k, v in options.items()])
@@ -576,14 +605,23 @@ class Context:
             raise RmhmcError(-4, "%s does not export the output descriptor (include/rmhmc_out.h)" % self.rl.path)
 
     def sample_to(self, sampler, n_iter, burn_in, *, where="host", device=None, samples=False, stats=False, run_mean=False,
-                  L=None, eps=None, K=None, compat=None, seed=0, chain_offset=0, theta0=None):
+                  L=None, eps=None, K=None, compat=None, seed=0, chain_offset=0, theta0=None, diagnostics=False, max_lag=None):
         """One run of `sampler` (a key of SAMPLERS_TO) written out as asked: samples [n][S][D]; stats: mean, var, ess [n][D]; run_mean:
         run_mean [S][D] and run_ess [D].  where="host": NumPy arrays; "device": torch tensors on `device`, the samples written by the
         sampler itself.  Returns a dict of the requested outputs, the sampler's counters (same memory space) and `seconds`.  The run
         arguments are those of the sampler's own method, with its defaults (L, eps, K, compat where it has them); one the sampler does
         not have (theta0 for Gibbs included) is a ValueError.  The library works on a stream of its own: torch's current stream on
-        `device` is synchronised before the call, and the library's is idle on return."""
+        `device` is synchronised before the call, and the library's is idle on return.
+
+        diagnostics=True adds the cross-chain diagnostics of the call's samples (include/rmhmc_diag.h; max_lag as in diag_partial): rhat,
+        ess_pooled, pairs, chains_used as host NumPy arrays [D], and diag_partial, the device tensor a sharded job merges.  The sampler
+        then writes its samples to a device tensor whatever `where` and `samples` say (they are returned only if asked, and outputs
+        asked on the host are copied there); samples and counters are those of the same call without the keyword, bit for bit."""
         self._need_out()
+        if diagnostics:
+            return self._sample_to_diag(sampler, n_iter, burn_in, where, device, samples, max_lag,
+                                        dict(stats=stats, run_mean=run_mean, L=L, eps=eps, K=K, compat=compat, seed=seed,
+                                             chain_offset=chain_offset, theta0=theta0))
         name, counters = SAMPLERS_TO[sampler]
         given = dict(L=L, eps=eps, K=K, compat=compat, theta0=theta0)
         extra = sorted(k for k, v in given.items() if v is not None and k not in SAMPLER_ARGS[sampler])
@@ -660,6 +698,57 @@ class Context:
             torch.cuda.current_stream(x.device).synchronize()
         self._ck(self.lib.rmhmc_ess_dev(self._h, x.data_ptr(), n, S, P, ess.data_ptr(), mean.data_ptr(), var.data_ptr()))
         return ess, mean, var
+
+    # ---- cross-chain diagnostics: split R-hat and the pooled ESS (include/rmhmc_diag.h) ----------
+    def _need_diag(self):
+        if not self.rl.has_diag:
+            raise RmhmcError(-4, "%s does not export the cross-chain diagnostics (include/rmhmc_diag.h)" % self.rl.path)
+
+    def diag_partial(self, samples, max_lag=None):
+        """The mergeable partial [(4 + T), P] (include/rmhmc_diag.h) of a float64 torch tensor [n][S][P] already on the context's GPU,
+        reduced there; T = max_lag + 1, max_lag None or 0: every lag, S // 2 - 1.  torch's current stream is synchronised first, as in
+        ess_dev."""
+        import torch
+        self._need_diag()
+        if self.rl.on_gpu and not samples.is_cuda:
+            raise ValueError("diag_partial: a tensor on the context's GPU is required")
+        x = samples.contiguous()
+        if x.dtype != torch.float64 or x.dim() != 3:
+            raise ValueError("diag_partial: float64 tensor [n][S][P] required")
+        n, S, P = x.shape
+        max_lag = 0 if max_lag is None else int(max_lag)
+        H = S // 2
+        T = (max_lag if max_lag else H - 1) + 1 if 0 <= max_lag < H else 1   # (out of range: the library refuses the call)
+        part = torch.empty((4 + T, P), dtype=torch.float64, device=x.device)
+        if x.is_cuda:
+            torch.cuda.current_stream(x.device).synchronize()
+        self._ck(self.lib.rmhmc_diag_partial_dev(self._h, x.data_ptr(), n, S, P, max_lag, part.data_ptr()))
+        return part
+
+    def diagnose(self, samples, max_lag=None):
+        """split R-hat and pooled ESS of the chains of samples [n][S][P] on the context's GPU: dict(rhat, ess_pooled, pairs, chains_used:
+        host NumPy arrays [P]; partial: the device tensor of diag_partial).  2 * pairs + 1 >= T marks an ESS that is an upper bound."""
+        part = self.diag_partial(samples, max_lag)
+        out = diag_finish([part], samples.shape[1] // 2, lib=self.rl)
+        out["partial"] = part
+        return out
+
+    def _sample_to_diag(self, sampler, n_iter, burn_in, where, device, samples, max_lag, kw):
+        import torch
+        self._need_diag()
+        diag_lags(int(n_iter) - int(burn_in), max_lag)   # refused before any sampling work
+        host = where in ("host", OUT_HOST)
+        if host:
+            device = torch.device("cuda", self.device) if self.rl.on_gpu else torch.device("cpu")
+        r = self.sample_to(sampler, n_iter, burn_in, where="device" if host else where, device=device, samples=True, **kw)
+        dg = self.diagnose(r["samples"], max_lag)
+        if not samples:
+            del r["samples"]
+        if host:
+            r = {k: v.cpu().numpy() if isinstance(v, torch.Tensor) else v for k, v in r.items()}
+        r.update({k: dg[k] for k in DIAG_KEYS})
+        r["diag_partial"] = dg["partial"]
+        return r
 
     # the three output modes of RMHMC (sample_dev, sample_stats, sample_stats_dev above) for the other five samplers: *_sample_dev
     # returns what *_sample returns with the arrays as tensors on `device`; *_sample_stats[_dev] return dict(mean, var, ess, the
@@ -769,6 +858,36 @@ class Context:
         s = C.c_double(0.0); k = C.c_int64(0)
         self._ck(self.lib.rmhmc_kernel_time(self._h, which.encode(), C.cast(C.byref(s), _dp), C.cast(C.byref(k), _lp)))
         return s.value, k.value
+
+
+def diag_finish(partials, H, lib=None):
+    """rmhmc_diag_finish (include/rmhmc_diag.h): the partials ([(4 + T), P] each: torch tensors on any device or NumPy arrays, all of the
+    same shape, from series of H rows) merged in the order given and finished on the host.  Returns dict(rhat, ess_pooled, pairs,
+    chains_used: NumPy arrays [P]; merged: the merged partial [(4 + T), P])."""
+    lib = lib if lib is not None else load_hip_library()
+    if not lib.has_diag:
+        raise RmhmcError(-4, "%s does not export the cross-chain diagnostics (include/rmhmc_diag.h)" % lib.path)
+    parts = [_f64(p if isinstance(p, np.ndarray) else p.detach().cpu().numpy()) for p in partials]
+    if not parts or parts[0].ndim != 2 or any(p.shape != parts[0].shape for p in parts):
+        raise ValueError("diag_finish: partials of one shape [(4 + T), P] required")
+    T, P = parts[0].shape[0] - 4, parts[0].shape[1]
+    ptrs = (_dp * len(parts))(*[_ptr(p) for p in parts])
+    merged = np.empty((4 + T, P)); rhat = np.empty(P); ess = np.empty(P)
+    pairs = np.zeros(P, dtype=np.int64); used = np.zeros(P, dtype=np.int64)
+    rc = lib.lib.rmhmc_diag_finish(ptrs, len(parts), int(H), T, P, _ptr(merged), _ptr(rhat), _ptr(ess), _ptr(pairs, _lp), _ptr(used, _lp))
+    if rc != 0:
+        raise RmhmcError(rc, lib.lib.rmhmc_last_error(None).decode())
+    return dict(rhat=rhat, ess_pooled=ess, pairs=pairs, chains_used=used, merged=merged)
+
+
+def diag_info(st, diagnostics):
+    """what a shim adds to its info dict: {"diagnostics": the DIAG_KEYS of a sample_to result} when asked, else nothing"""
+    return {"diagnostics": {k: st[k] for k in DIAG_KEYS}} if diagnostics else {}
+
+
+def diag_identity(T, P):
+    """the partial of no series at all (an empty shard): the identity of the merge"""
+    return np.zeros((4 + int(T), int(P)))
 
 
 _hip = None

@@ -10,6 +10,7 @@
 #include "../../include/rmhmc_iwls.h"
 #include "../../include/rmhmc_gibbs.h"
 #include "../../include/rmhmc_out.h"
+#include "../../include/rmhmc_diag.h"
 #include "plan.h"
 #include "kernels.hip.h"
 #include "fused_small.hip.h"
@@ -20,6 +21,7 @@
 #include "iwls.hip.h"
 #include "gibbs.hip.h"
 #include "output.hip.h"
+#include "diag.hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -2578,6 +2580,79 @@ int rmhmc_ess_dev(rmhmc_ctx* ctx, const double* samples_dev, int64_t n, int64_t 
   HIPCK(hipSetDevice(ctx->device));
   RC(launch_ess(ctx, samples_dev, n, S, P, ess_dev, mean_dev, var_dev));
   return sync(ctx);
+}
+
+}  // extern "C"
+
+// ---- cross-chain diagnostics: split R-hat and the pooled ESS (include/rmhmc_diag.h, diag.h, diag.hip.h) ----------------------------
+namespace {
+
+template <int TW, int NQ>
+int launch_diag_acov(rmhmc_ctx* ctx, dim3 grid, size_t lds, const double* d_samples, long long n, long long S, int P, int H, int T, int rows,
+                     double* d_blk, double* d_means) {
+  RC(raise_lds(ctx, (k_diag_acov<TW, NQ>), MAX_LDS));  // per device: set where it is used
+  hipLaunchKernelGGL((k_diag_acov<TW, NQ>), grid, dim3(DIAG_THREADS), lds, ctx->stream, d_samples, n, S, P, H, T, rows, d_blk, d_means);
+  return RMHMC_OK;
+}
+
+// samples [n][S][P] -> the partial [(4 + T)][P], all in device memory; queued on the stream, its two scratch buffers returned for the
+// caller to free once the stream is idle
+int launch_diag(rmhmc_ctx* ctx, const double* d_samples, long long n, long long S, int P, long long T, double* d_partial, double** d_blk,
+                double** d_means) {
+  const long long H = S / 2;
+  const int tw = diag_tile_width(H, P);
+  const long long nblocks = (n + DIAG_CHAINS - 1) / DIAG_CHAINS;
+  if (tw < 1) return fail(ctx, RMHMC_ERR_UNSUPPORTED, "diag: the half series does not fit the LDS");
+  const int nq = diag_lag_sets(T, tw);
+  const long long ntiles = ((long long)P + tw - 1) / tw;
+  if (T > nq * diag_lags_per_block(tw)) return fail(ctx, RMHMC_ERR_UNSUPPORTED, "diag: more lags than a workgroup holds");  // (never: diag.h)
+  if (nblocks > 65535 || ntiles > 0x7fffffffLL) return fail(ctx, RMHMC_ERR_UNSUPPORTED, "diag: at most 65535 * 32 chains per call");
+  const size_t rowlen = (size_t)(2 + T) * P;
+  HIPCK(hipMalloc((void**)d_blk, sizeof(double) * (size_t)nblocks * rowlen));
+  HIPCK(hipMalloc((void**)d_means, sizeof(double) * 2 * (size_t)n * P));
+  const dim3 grid((unsigned)ntiles, (unsigned)nblocks);
+  const size_t lds = (size_t)diag_lds_bytes(H, tw);
+  const int rows = (int)diag_lds_rows(H);
+#define DIAG_CASE(TW)                                                                                                      \
+  case TW:                                                                                                                 \
+    if (nq == 1) RC((launch_diag_acov<TW, 1>(ctx, grid, lds, d_samples, n, S, P, (int)H, (int)T, rows, *d_blk, *d_means)));   \
+    else RC((launch_diag_acov<TW, DIAG_NQ>(ctx, grid, lds, d_samples, n, S, P, (int)H, (int)T, rows, *d_blk, *d_means)));     \
+    break
+  switch (tw) {
+    DIAG_CASE(1); DIAG_CASE(2); DIAG_CASE(4); DIAG_CASE(8); DIAG_CASE(16); DIAG_CASE(32); DIAG_CASE(64);
+    default: return fail(ctx, RMHMC_ERR_RUNTIME, "diag: no kernel for this tile width");
+  }
+#undef DIAG_CASE
+  hipLaunchKernelGGL(k_diag_reduce, dim3((unsigned)((rowlen + 255) / 256)), dim3(256), 0, ctx->stream, *d_blk, nblocks, P, (int)H, (int)T, d_partial);
+  hipLaunchKernelGGL(k_diag_m2, dim3((unsigned)((P + 15) / 16)), dim3(1024), 0, ctx->stream, *d_means, 2 * n, P, d_partial);
+  HIPCK(hipGetLastError());
+  return RMHMC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rmhmc_diag_partial_dev(rmhmc_ctx* ctx, const double* samples_dev, int64_t n, int64_t S, int32_t P, int64_t max_lag, double* partial_dev) {
+  if (!ctx || !samples_dev || !partial_dev || n < 1 || P < 1 || max_lag < 0) return fail(ctx, RMHMC_ERR_INVALID, "diag_partial_dev: bad argument");
+  if (S < 4 || S > 20000) return fail(ctx, RMHMC_ERR_UNSUPPORTED, "diag: 4 <= S <= 20000 samples per chain (the centred series is held in LDS)");
+  const int64_t H = S / 2;
+  if (max_lag > H - 1) return fail(ctx, RMHMC_ERR_INVALID, "diag_partial_dev: max_lag must be 0 (every lag) or 1 .. S/2 - 1");
+  const int64_t T = (max_lag ? max_lag : H - 1) + 1;
+  HIPCK(hipSetDevice(ctx->device));
+  double *d_blk = nullptr, *d_means = nullptr;
+  int rc = launch_diag(ctx, samples_dev, n, S, P, T, partial_dev, &d_blk, &d_means);
+  const int rs = sync(ctx);
+  if (d_blk) (void)hipFree(d_blk);
+  if (d_means) (void)hipFree(d_means);
+  return rc != RMHMC_OK ? rc : rs;
+}
+
+int rmhmc_diag_finish(const double* const* partials, int32_t k, int64_t H, int64_t T, int32_t P, double* merged, double* rhat, double* ess,
+                      int64_t* pairs, int64_t* chains_used) {
+  const int rc = diag_finish(partials, k, H, T, P, merged, rhat, ess, pairs, chains_used);
+  return rc == RMHMC_OK ? rc : fail(nullptr, rc, rc == RMHMC_ERR_NOMEM ? "diag_finish: out of memory"
+                                                                       : "diag_finish: need k >= 1, H >= 2, 2 <= T <= H, P >= 1 and no NULL partial");
 }
 
 }  // extern "C"

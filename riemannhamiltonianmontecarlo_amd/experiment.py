@@ -55,25 +55,34 @@ def _summary(avg_beta_posterior, avg_time_taken, ESS, per_run):
 
 
 def run_experiment(XX, t, sampler="RMHMC", n_experiments=10, batched=False, seed=None, verbose=False, nfft="python", summary=False,
-                   **sampler_kwargs):
+                   diagnostics=False, max_lag=None, **sampler_kwargs):
     """main.py:43-79.  Returns a dict with ``results_beta`` (n_experiments, S, D), ``results_time`` (n_experiments,) and the summary of
     ``summarize``.  ``sampler_kwargs`` go to the sampler (NumOfIterations, BurnIn, StepSize, compat, device, ...); the defaults are the
     samplers' own, i.e. S = 5000 rows per run as main.py:46 hard-codes.
 
     summary=True (needs batched=True): the same summary from the reductions of the device (include/rmhmc_out.h: the run-mean chain,
-    its ESS and the per-run ESS, ``nfft`` selecting the FFT length there) - no raw sample leaves the GPU and ``results_beta`` is omitted."""
+    its ESS and the per-run ESS, ``nfft`` selecting the FFT length there) - no raw sample leaves the GPU and ``results_beta`` is omitted.
+
+    diagnostics=True (needs batched=True): the result also carries ``rhat`` and ``ess_pooled`` (D,), the split R-hat and the pooled ESS
+    across the runs (include/rmhmc_diag.h; ``max_lag`` as there), with ``pairs`` and ``chains_used``; the other entries are unchanged."""
     if summary and not batched:
         raise ValueError("summary=True reduces the runs of one batched sampler call on the device: it needs batched=True")
+    if diagnostics and not batched:
+        raise ValueError("diagnostics=True compares the runs of one batched sampler call on the device: it needs batched=True")
+    if diagnostics:   # the shims return the diagnostics in their info dict
+        sampler_kwargs = dict(sampler_kwargs, diagnostics=True, max_lag=max_lag, return_info=True)
     fn = SAMPLERS[sampler] if isinstance(sampler, str) else sampler
     if seed is None:
         seed = int(np.random.randint(0, 2 ** 62))
     if summary:
-        st, secs = fn(XX, t, n_chains=n_experiments, seed=seed, verbose=verbose, summary=True, ess_nfft=nfft, **sampler_kwargs)
+        st, secs, *info = fn(XX, t, n_chains=n_experiments, seed=seed, verbose=verbose, summary=True, ess_nfft=nfft, **sampler_kwargs)
         out = {"results_time": np.full(n_experiments, secs), "seed": seed, "sampler": getattr(fn, "__name__", str(fn))}
+        if diagnostics:
+            out.update(info[0]["diagnostics"])
         out.update(_summary(st["run_mean"], float(np.mean(out["results_time"])), st["run_ess"].reshape(-1, 1), st["ess"]))
         return out
     if batched:
-        smp, secs = fn(XX, t, n_chains=n_experiments, seed=seed, verbose=verbose, **sampler_kwargs)
+        smp, secs, *info = fn(XX, t, n_chains=n_experiments, seed=seed, verbose=verbose, **sampler_kwargs)
         results_beta = smp if n_experiments > 1 else smp[None]
         results_time = np.full(n_experiments, secs)
     else:
@@ -85,6 +94,8 @@ def run_experiment(XX, t, sampler="RMHMC", n_experiments=10, batched=False, seed
         results_beta = np.stack(runs); results_time = np.asarray(times)
     out = {"results_beta": results_beta, "results_time": results_time, "seed": seed, "sampler": getattr(fn, "__name__", str(fn))}
     out.update(summarize(results_beta, results_time, nfft))
+    if diagnostics:
+        out.update(info[0]["diagnostics"])
     return out
 
 
@@ -94,3 +105,6 @@ def report(res, file=None):
     for k in ('Min', 'Median', 'Mean', 'Max', 'Time'):
         print(k, res[k], file=file)
     print('Time per Min ESS:', res['Time per Min ESS'], file=file)
+    if 'rhat' in res:   # run_experiment(diagnostics=True): across the runs
+        print('Max split R-hat:', float(np.nanmax(res['rhat'])), file=file)
+        print('Min pooled ESS:', float(np.nanmin(res['ess_pooled'])), file=file)

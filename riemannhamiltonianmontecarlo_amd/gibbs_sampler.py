@@ -11,7 +11,7 @@ sampler, expected 0), the seed, and `stopped`: -1, or the iteration at which a c
 formula (about 3e-9 of all draws of a lam_j: N * max_iter * 3e-9 per chain and run, i.e. about 2 % of the chains of a default run on
 australian, 690 rows x 10 000 iterations, and about a quarter of them at 10 000 rows x 10 000 iterations).  The reference ends in a
 ValueError there; here that chain stops, its later rows of beta_saved are NaN (check `stopped`), the other chains go on.  summary / ess_nfft as
-for RMHMC; the statistics of a stopped chain are NaN, and so are the rows of run_mean it did not reach.  No CPU fallback.
+for RMHMC; the statistics of a stopped chain are NaN, and so are the rows of run_mean it did not reach; diagnostics / max_lag as for RMHMC.  No CPU fallback.
 """
 import numpy as np
 
@@ -26,7 +26,7 @@ def gibbs_progress_printer():
 
 
 def auxiliary_gibbs(XX, t, v=100, max_iter=10000, burn_in=5000, *, n_chains=1, seed=None, device=0, chain_offset=0, verbose=True,
-                    return_info=False, summary=False, ess_nfft="matlab", _lib=None):
+                    return_info=False, summary=False, ess_nfft="matlab", diagnostics=False, max_lag=None, _lib=None):
     """ AUXILIARY VARIABLE GIBBS SAMPLER (Bayesian logistic regression, N(0, v I) prior) """
     XX = np.ascontiguousarray(XX, dtype=np.float64)
     if XX.ndim != 2:
@@ -37,6 +37,10 @@ def auxiliary_gibbs(XX, t, v=100, max_iter=10000, burn_in=5000, *, n_chains=1, s
         raise ValueError("t must have N entries")
     if not 0 <= burn_in < max_iter:
         raise ValueError("need 0 <= burn_in < max_iter")  # NameError in the reference (`start` unbound, gibbs_sampler.py:137)
+    if diagnostics and not return_info:
+        raise ValueError("diagnostics=True returns its result in the info dict: it needs return_info=True")
+    if diagnostics:
+        _capi.diag_lags(max_iter - burn_in, max_lag)
     ess = _capi.ess_flags(ess_nfft)
     if seed is None:
         seed = int(np.random.randint(0, 2 ** 62))
@@ -48,7 +52,12 @@ def auxiliary_gibbs(XX, t, v=100, max_iter=10000, burn_in=5000, *, n_chains=1, s
         if verbose:
             print("--- Initialization: done. Iterating...")
             ctx.set_progress(gibbs_progress_printer())
-        if summary:
+        st = None
+        if diagnostics:   # (include/rmhmc_diag.h; as RMHMC.  A stopped chain has NaN rows: it is left out, see chains_used)
+            st = ctx.sample_to("gibbs", max_iter, burn_in, samples=not summary, stats=summary, run_mean=summary, diagnostics=True,
+                               max_lag=max_lag, seed=seed, chain_offset=chain_offset)
+            samples, capped, stopped, seconds = st.get("samples"), st["capped"], st["stopped"], st["seconds"]
+        elif summary:
             st = ctx.gibbs_sample_stats(max_iter, burn_in, seed=seed, chain_offset=chain_offset, run_mean=True)
             samples, capped, stopped, seconds = None, st["capped"], st["stopped"], st["seconds"]
         else:
@@ -59,5 +68,5 @@ def auxiliary_gibbs(XX, t, v=100, max_iter=10000, burn_in=5000, *, n_chains=1, s
         print("--- Auxiliary Variable Gibbs Sampler finished in {}".format(seconds))
     beta_saved = {k: st[k] for k in _capi.SUMMARY_KEYS} if summary else samples[0] if n_chains == 1 else samples
     if return_info:
-        return beta_saved, seconds, dict(capped=capped, stopped=stopped, seed=seed)
+        return beta_saved, seconds, dict(capped=capped, stopped=stopped, seed=seed, **_capi.diag_info(st, diagnostics))
     return beta_saved, seconds

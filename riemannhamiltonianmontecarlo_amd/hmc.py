@@ -5,7 +5,7 @@ unchanged code/main.py actually calls at main.py:53).
 
 Identity mass, theta0 = 0 (hmc.py:21,27), trajectory length ceil(rand*NumOfLeapFrogSteps) (hmc.py:48).  Runs on
 the MI355X through rmhmc_hmc_sample (include/rmhmc.h); same keyword-only extensions and the same row-0
-convention as riemannhamiltonianmontecarlo_amd.rmhmc.RMHMC, summary / ess_nfft included.  No CPU fallback.
+convention as riemannhamiltonianmontecarlo_amd.rmhmc.RMHMC, summary / ess_nfft and diagnostics / max_lag included.  No CPU fallback.
 """
 import numpy as np
 
@@ -13,7 +13,8 @@ from . import _capi
 
 
 def HMC(XX, t, NumOfIterations=6000, BurnIn=1000, NumOfLeapFrogSteps=100, StepSize=0.14, *, n_chains=1, seed=None,
-        theta0=None, alpha=100.0, device=0, chain_offset=0, verbose=True, return_info=False, options=None, summary=False, ess_nfft="matlab", _lib=None):
+        theta0=None, alpha=100.0, device=0, chain_offset=0, verbose=True, return_info=False, options=None, summary=False, ess_nfft="matlab",
+        diagnostics=False, max_lag=None, _lib=None):
     """ HAMILTONIAN MONTE CARLO (Bayesian logistic regression, N(0, alpha I) prior) """
     XX = np.ascontiguousarray(XX, dtype=np.float64)
     if XX.ndim != 2:
@@ -24,6 +25,10 @@ def HMC(XX, t, NumOfIterations=6000, BurnIn=1000, NumOfLeapFrogSteps=100, StepSi
         raise ValueError("t must have N entries")
     if not BurnIn < NumOfIterations:
         raise ValueError("BurnIn must be smaller than NumOfIterations")  # NameError in the reference (hmc.py:92-96)
+    if diagnostics and not return_info:
+        raise ValueError("diagnostics=True returns its result in the info dict: it needs return_info=True")
+    if diagnostics:
+        _capi.diag_lags(NumOfIterations - BurnIn, max_lag)
     ess = _capi.ess_flags(ess_nfft)
     if seed is None:
         seed = int(np.random.randint(0, 2 ** 62))
@@ -33,7 +38,12 @@ def HMC(XX, t, NumOfIterations=6000, BurnIn=1000, NumOfLeapFrogSteps=100, StepSi
         if verbose:  # the reference's stdout, hmc.py:85-89,92-94
             from .rmhmc import progress_printer
             ctx.set_progress(progress_printer(n_chains, hmc_burn_in=BurnIn), first=1, every=50)
-        if summary:
+        st = None
+        if diagnostics:   # (include/rmhmc_diag.h; as RMHMC)
+            st = ctx.sample_to("hmc", NumOfIterations, BurnIn, samples=not summary, stats=summary, run_mean=summary, diagnostics=True,
+                               max_lag=max_lag, L=NumOfLeapFrogSteps, eps=StepSize, seed=seed, chain_offset=chain_offset, theta0=theta0)
+            samples, acc, steps, seconds = st.get("samples"), st["accepted"], st["leapfrog_steps"], st["seconds"]
+        elif summary:
             st = ctx.hmc_sample_stats(NumOfIterations, BurnIn, NumOfLeapFrogSteps, StepSize, seed=seed, chain_offset=chain_offset,
                                       theta0=theta0, run_mean=True)
             samples, acc, steps, seconds = None, st["accepted"], st["leapfrog_steps"], st["seconds"]
@@ -44,5 +54,5 @@ def HMC(XX, t, NumOfIterations=6000, BurnIn=1000, NumOfLeapFrogSteps=100, StepSi
         print('Time drawing posterior: {}'.format(seconds))
     wSaved = {k: st[k] for k in _capi.SUMMARY_KEYS} if summary else samples[0] if n_chains == 1 else samples
     if return_info:
-        return wSaved, seconds, dict(accepted=acc, leapfrog_steps=steps, seed=seed)
+        return wSaved, seconds, dict(accepted=acc, leapfrog_steps=steps, seed=seed, **_capi.diag_info(st, diagnostics))
     return wSaved, seconds

@@ -8,7 +8,7 @@ MI355X through rmhmc_iwls_sample (include/rmhmc_iwls.h); the metric is assembled
 (int8_slices).  compat=True (the default) is the reference: its jittered log-determinant term and the rejection of every proposal with a
 saturated row (W_j = 0, the reference's 0/0), which truncates the posterior to states without a row f_j > 36.7 (DESIGN section 8c);
 compat=False is the corrected sampler.  Every row of beta_saved is written (:84-85).  n_chains > 1 returns (n_chains, S, D);
-return_info adds the accepted and saturated proposals per chain, the acceptance rate and the seed; summary / ess_nfft as for RMHMC.  No CPU fallback.
+return_info adds the accepted and saturated proposals per chain, the acceptance rate and the seed; summary / ess_nfft and diagnostics / max_lag as for RMHMC.  No CPU fallback.
 """
 import numpy as np
 
@@ -26,7 +26,8 @@ def iwls_progress_printer():
 
 
 def iwls(XX, t, alpha=100, max_iter=10000, burn_in=5000, *, n_chains=1, seed=None, theta0=None, compat=True, int8_slices=None,
-         device=0, chain_offset=0, verbose=True, return_info=False, summary=False, ess_nfft="matlab", _lib=None):
+         device=0, chain_offset=0, verbose=True, return_info=False, summary=False, ess_nfft="matlab", diagnostics=False,
+         max_lag=None, _lib=None):
     """ IWLS METROPOLIS-HASTINGS (Bayesian logistic regression, N(0, alpha I) prior) """
     XX = np.ascontiguousarray(XX, dtype=np.float64)
     if XX.ndim != 2:
@@ -37,6 +38,10 @@ def iwls(XX, t, alpha=100, max_iter=10000, burn_in=5000, *, n_chains=1, seed=Non
         raise ValueError("t must have N entries")
     if not 0 <= burn_in < max_iter:
         raise ValueError("need 0 <= burn_in < max_iter")  # NameError in the reference (`start` unbound, iwls.py:88)
+    if diagnostics and not return_info:
+        raise ValueError("diagnostics=True returns its result in the info dict: it needs return_info=True")
+    if diagnostics:
+        _capi.diag_lags(max_iter - burn_in, max_lag)
     ess = _capi.ess_flags(ess_nfft)
     if seed is None:
         seed = int(np.random.randint(0, 2 ** 62))
@@ -50,7 +55,12 @@ def iwls(XX, t, alpha=100, max_iter=10000, burn_in=5000, *, n_chains=1, seed=Non
             print("--- Iterating...")
             # (rmhmc_iwls_sample reports on the reference's own schedule, include/rmhmc_iwls.h: the context's first / every are not used)
             ctx.set_progress(iwls_progress_printer())
-        if summary:
+        st = None
+        if diagnostics:   # (include/rmhmc_diag.h; as RMHMC)
+            st = ctx.sample_to("iwls", max_iter, burn_in, samples=not summary, stats=summary, run_mean=summary, diagnostics=True,
+                               max_lag=max_lag, compat=compat, seed=seed, chain_offset=chain_offset, theta0=theta0)
+            samples, acc, sat, seconds = st.get("samples"), st["accepted"], st["saturated"], st["seconds"]
+        elif summary:
             st = ctx.iwls_sample_stats(max_iter, burn_in, compat=compat, seed=seed, chain_offset=chain_offset, theta0=theta0,
                                        run_mean=True)
             samples, acc, sat, seconds = None, st["accepted"], st["saturated"], st["seconds"]
@@ -62,5 +72,5 @@ def iwls(XX, t, alpha=100, max_iter=10000, burn_in=5000, *, n_chains=1, seed=Non
         print("Number of accepted samples: ", int(acc.sum()))
     beta_saved = {k: st[k] for k in _capi.SUMMARY_KEYS} if summary else samples[0] if n_chains == 1 else samples
     if return_info:
-        return beta_saved, seconds, dict(accepted=acc, saturated=sat, acceptance=acc / float(max_iter), seed=seed)
+        return beta_saved, seconds, dict(accepted=acc, saturated=sat, acceptance=acc / float(max_iter), seed=seed, **_capi.diag_info(st, diagnostics))
     return beta_saved, seconds

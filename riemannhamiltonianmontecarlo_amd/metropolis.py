@@ -6,7 +6,7 @@ paper's comparison tables).
 w = 0, ProposalSD = 1 (metropolis.py:24-29), one Gaussian proposal per coordinate per iteration, SD adapted every 100 iterations of
 the burn-in (iteration 0 included).  Runs on the MI355X through rmhmc_amh_sample (include/rmhmc_amh.h); same keyword-only extensions
 and the same row-0 convention as riemannhamiltonianmontecarlo_amd.hmc.HMC (row 0 = state after iteration BurnIn; the reference never
-writes it).  return_info adds the per-chain acceptance rate over the whole run and the final ProposalSD; summary / ess_nfft as for RMHMC.  No CPU fallback.
+writes it).  return_info adds the per-chain acceptance rate over the whole run and the final ProposalSD; summary / ess_nfft and diagnostics / max_lag as for RMHMC.  No CPU fallback.
 """
 import numpy as np
 
@@ -24,7 +24,7 @@ def amh_progress_printer():
 
 
 def AMH(XX, t, NumOfIterations=10000, BurnIn=5000, *, n_chains=1, seed=None, theta0=None, alpha=100.0, device=0, chain_offset=0,
-        verbose=True, return_info=False, summary=False, ess_nfft="matlab", _lib=None):
+        verbose=True, return_info=False, summary=False, ess_nfft="matlab", diagnostics=False, max_lag=None, _lib=None):
     """ ADAPTIVE METROPOLIS HASTING (Bayesian logistic regression, N(0, alpha I) prior) """
     XX = np.ascontiguousarray(XX, dtype=np.float64)
     if XX.ndim != 2:
@@ -35,6 +35,10 @@ def AMH(XX, t, NumOfIterations=10000, BurnIn=5000, *, n_chains=1, seed=None, the
         raise ValueError("t must have N entries")
     if not 0 <= BurnIn < NumOfIterations:
         raise ValueError("BurnIn must be smaller than NumOfIterations")  # NameError in the reference (metropolis.py:93)
+    if diagnostics and not return_info:
+        raise ValueError("diagnostics=True returns its result in the info dict: it needs return_info=True")
+    if diagnostics:
+        _capi.diag_lags(NumOfIterations - BurnIn, max_lag)
     ess = _capi.ess_flags(ess_nfft)
     if seed is None:
         seed = int(np.random.randint(0, 2 ** 62))
@@ -44,7 +48,12 @@ def AMH(XX, t, NumOfIterations=10000, BurnIn=5000, *, n_chains=1, seed=None, the
         if verbose:
             # (rmhmc_amh_sample reports on the reference's own schedule, include/rmhmc_amh.h: the context's first / every are not used)
             ctx.set_progress(amh_progress_printer())
-        if summary:
+        st = None
+        if diagnostics:   # (include/rmhmc_diag.h; as RMHMC)
+            st = ctx.sample_to("amh", NumOfIterations, BurnIn, samples=not summary, stats=summary, run_mean=summary, diagnostics=True,
+                               max_lag=max_lag, seed=seed, chain_offset=chain_offset, theta0=theta0)
+            samples, acc, sd, seconds = st.get("samples"), st["accepted"], st["sd"], st["seconds"]
+        elif summary:
             st = ctx.amh_sample_stats(NumOfIterations, BurnIn, seed=seed, chain_offset=chain_offset, theta0=theta0, run_mean=True)
             samples, acc, sd, seconds = None, st["accepted"], st["sd"], st["seconds"]
         else:
@@ -53,5 +62,5 @@ def AMH(XX, t, NumOfIterations=10000, BurnIn=5000, *, n_chains=1, seed=None, the
         print('Time drawing posterior: {}'.format(seconds))
     wSaved = {k: st[k] for k in _capi.SUMMARY_KEYS} if summary else samples[0] if n_chains == 1 else samples
     if return_info:
-        return wSaved, seconds, dict(acceptance=acc / float(NumOfIterations * D), accepted=acc, ProposalSD=sd, seed=seed)
+        return wSaved, seconds, dict(acceptance=acc / float(NumOfIterations * D), accepted=acc, ProposalSD=sd, seed=seed, **_capi.diag_info(st, diagnostics))
     return wSaved, seconds

@@ -93,7 +93,7 @@ def nanmin_rows(ess):
 
 def sample_sharded(XX, t, n_chains, NumOfIterations=6000, BurnIn=1000, NumOfLeapFrogSteps=6, StepSize=0.5,
                    NumOfNewtonSteps=4, *, seed=0, compat=True, theta0=None, alpha=100.0, gather="samples", lib=None, options=None,
-                   sampler="RMHMC", sampler_args=None):
+                   sampler="RMHMC", sampler_args=None, diagnostics=False, max_lag=None):
     """Run ``n_chains`` chains sharded over the ranks of the initialised process group.
 
     gather="samples": rank 0 returns (samples [n_chains,S,D], seconds, info); other ranks return None.
@@ -108,11 +108,21 @@ def sample_sharded(XX, t, n_chains, NumOfIterations=6000, BurnIn=1000, NumOfLeap
     NumOfNewtonSteps and ``compat`` are RMHMC's and do not apply: ``sampler_args`` carries the sampler's own run arguments as
     _capi.Context.sample_to takes them (L, eps for HMC; eps for mMALA; compat for IWLS), its defaults otherwise.  ``info`` then holds the
     sampler's own counters.  The int8 metric assembly is chosen as for RMHMC where the sampler assembles a metric (mMALA, IWLS).
+    ``diagnostics=True`` (every sampler, both gather modes; HIP library only): ``info`` gains rhat, ess_pooled, pairs and chains_used (D,),
+    the split R-hat and the pooled ESS across ALL n_chains chains (include/rmhmc_diag.h; ``max_lag`` as there).  Every rank reduces the
+    samples of its shard to a partial on its GPU - an empty shard contributes the identity - and the partials, a few KB each, are
+    gathered to rank 0 and merged there in rank order.  "RMHMC" then runs through rmhmc_sample_to as the other samplers do, which by the
+    contract of include/rmhmc_out.h gives the same samples and counters.  The result does not depend on the number of ranks beyond
+    rounding (the merge is exact arithmetic only for the counts).
     """
     if sampler not in _SHARDED:   # (before any collective: every rank raises on its own)
         raise ValueError("unknown sampler %r: one of %s" % (sampler, sorted(_SHARDED)))
     if sampler == "RMHMC" and sampler_args:
         raise ValueError("RMHMC takes its run arguments by name (NumOfLeapFrogSteps, StepSize, NumOfNewtonSteps), not in sampler_args")
+    if diagnostics:
+        _capi.diag_lags(NumOfIterations - BurnIn, max_lag)
+        if gather not in ("samples", "summary"):
+            raise ValueError('gather must be "samples" or "summary"')
     if sampler != "RMHMC":
         # everything a rank could raise on its own later: a rank with an empty shard would otherwise wait in a collective for one that raised
         key = _SHARDED[sampler][0]
@@ -132,6 +142,8 @@ def sample_sharded(XX, t, n_chains, NumOfIterations=6000, BurnIn=1000, NumOfLeap
     lib = lib if lib is not None else _capi.load_hip_library()
     if sampler != "RMHMC" and not lib.has_out:   # (before the first collective as well)
         raise _capi.RmhmcError(-4, "%s does not export the output descriptor (include/rmhmc_out.h): only RMHMC can be sharded" % lib.path)
+    if diagnostics and not (lib.has_out and lib.has_diag):
+        raise _capi.RmhmcError(-4, "%s does not export the cross-chain diagnostics (include/rmhmc_diag.h, include/rmhmc_out.h)" % lib.path)
     # where the collective runs (HBM for RCCL, host memory for gloo) and where the sampler writes its outputs: the HIP library always
     # writes through device pointers of its own GPU, whatever the backend; with gloo those tensors take one hop to the host first
     cdev = _t.device("cuda", local_rank) if backend == "nccl" else _t.device("cpu")
@@ -145,7 +157,11 @@ def sample_sharded(XX, t, n_chains, NumOfIterations=6000, BurnIn=1000, NumOfLeap
     S = NumOfIterations - BurnIn
     if sampler != "RMHMC":
         return _sharded_to(sampler, dict(sampler_args or {}), XX, t, n_chains, NumOfIterations, BurnIn, seed, theta0, alpha, gather, lib,
-                           options, gpu, odev, cdev, start, end, counts)
+                           options, gpu, odev, cdev, start, end, counts, diagnostics=diagnostics, max_lag=max_lag)
+    if diagnostics:   # the same run through rmhmc_sample_to: its samples stay where the partial is computed
+        args = dict(L=NumOfLeapFrogSteps, eps=StepSize, K=NumOfNewtonSteps)
+        return _sharded_to(sampler, args, XX, t, n_chains, NumOfIterations, BurnIn, seed, theta0, alpha, gather, lib, options, gpu, odev,
+                           cdev, start, end, counts, diagnostics=True, max_lag=max_lag, flags=_capi.COMPAT if compat else 0)
     if n_local > 0:
         th = None if theta0 is None else np.broadcast_to(theta0, (n_chains, D))[start:end]
         with lib.context(N, D, n_local, flags=(_capi.COMPAT if compat else 0) | _capi.auto_metric_flags(D, n_local, M=N), device=gpu,
@@ -186,8 +202,9 @@ def sample_sharded(XX, t, n_chains, NumOfIterations=6000, BurnIn=1000, NumOfLeap
 
 
 def _sharded_to(sampler, args, XX, t, n_chains, n_iter, burn_in, seed, theta0, alpha, gather, lib, options, gpu, odev, cdev, start, end,
-                counts):
-    """sample_sharded for the samplers that run through include/rmhmc_out.h: same shards, same gathers, the sampler's own counters"""
+                counts, diagnostics=False, max_lag=None, flags=0):
+    """sample_sharded for the samplers that run through include/rmhmc_out.h: same shards, same gathers, the sampler's own counters;
+    diagnostics: one more gather, of every rank's partial (include/rmhmc_diag.h).  flags: context flags besides the metric's"""
     import torch as _t
     dist = _dist()
     rank, world = dist.get_rank(), dist.get_world_size()
@@ -198,11 +215,12 @@ def _sharded_to(sampler, args, XX, t, n_chains, n_iter, burn_in, seed, theta0, a
     if n_local > 0:
         if theta0 is not None:
             args["theta0"] = np.broadcast_to(theta0, (n_chains, D))[start:end]
-        flags = _capi.auto_metric_flags(D, n_local, M=N) if has_metric else 0
+        flags |= _capi.auto_metric_flags(D, n_local, M=N) if has_metric else 0
         with lib.context(N, D, n_local, flags=flags, device=gpu, options=options) as ctx:
             ctx.set_data(XX, t, alpha)
             st = ctx.sample_to(key, n_iter, burn_in, where="device", device=odev, samples=gather == "samples", stats=gather == "summary",
-                               seed=seed, chain_offset=start, **args)
+                               seed=seed, chain_offset=start, diagnostics=diagnostics, max_lag=max_lag, **args)
+        part = st["diag_partial"] if diagnostics else None
         secs = st["seconds"]
         payload = st["samples"] if gather == "samples" else _t.cat([st["mean"], st["var"], nanmin_rows(st["ess"])], dim=1)
         cnt = {k: st[k] for k, _ in counters}
@@ -210,12 +228,14 @@ def _sharded_to(sampler, args, XX, t, n_chains, n_iter, burn_in, seed, theta0, a
         secs = 0.0
         payload = _t.zeros((0, S, D) if gather == "samples" else (0, 2 * D + 1), dtype=_t.float64, device=odev)
         cnt = {k: _t.zeros((0, D) if vec else (0,), dtype=_t.float64 if vec else _t.int64, device=odev) for k, vec in counters}
+        part = _t.from_numpy(_capi.diag_identity(_capi.diag_lags(S, max_lag)[1], D)).to(odev) if diagnostics else None
     tt = _t.tensor([secs], dtype=_t.float64, device=cdev)
     dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     ints = [k for k, vec in counters if not vec]
     cnt_all = _gather_rows(_t.stack([cnt[k] for k in ints], dim=1).to(cdev), counts)
     vecs = {k: _gather_rows(cnt[k].to(cdev), counts) for k, vec in counters if vec}   # (AMH's final ProposalSD)
     payload = _gather_rows(payload.to(cdev), counts)
+    parts = _gather_rows(part[None].to(cdev), [1] * world) if diagnostics else None   # [world][4 + T][D], in rank order
     if rank != 0:
         return None
     cnt_all = cnt_all.cpu().numpy()
@@ -225,4 +245,7 @@ def _sharded_to(sampler, args, XX, t, n_chains, n_iter, burn_in, seed, theta0, a
     info = {k: cnt_all[:, i] for i, k in enumerate(ints)}
     info.update({k: v.cpu().numpy() for k, v in vecs.items()})
     info.update(world=world, counts=counts)
+    if diagnostics:
+        dg = _capi.diag_finish(list(parts.cpu().numpy()), S // 2, lib=lib)
+        info.update({k: dg[k] for k in _capi.DIAG_KEYS})
     return g, float(tt.item()), info

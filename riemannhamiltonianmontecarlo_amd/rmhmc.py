@@ -26,6 +26,10 @@ Keyword-only extensions (defaults preserve the one-chain contract):
   summary    True: no raw sample leaves the GPU (include/rmhmc_out.h); the first return value is dict(mean, var, ess (n_chains, D),
              run_mean (S, D), run_ess (D,)) reduced on the device, always with the leading chain axis
   ess_nfft   FFT-length convention of that ESS: "matlab" (default) or "python" (tools.py:23)
+  diagnostics  True (needs return_info=True): the info dict gains `diagnostics`, dict(rhat, ess_pooled, pairs, chains_used) with one
+             entry per dimension: split R-hat and the pooled ESS across the n_chains chains, computed on the device
+             (include/rmhmc_diag.h); samples and counters are unchanged
+  max_lag    lags of that ESS: None = every lag, S // 2 - 1
 
 Documented deviations: row 0 of wSaved is undefined in the reference (np.empty,
 never written: rmhmc.py:28,190-191); here it holds the state after iteration
@@ -60,7 +64,7 @@ def progress_printer(n_chains, hmc_burn_in=None):
 
 def RMHMC(XX, t, NumOfIterations=6000, BurnIn=1000, NumOfLeapFrogSteps=6, StepSize=0.5, NumOfNewtonSteps=4, *,
           n_chains=1, seed=None, compat=True, theta0=None, alpha=100.0, device=0, chain_offset=0, verbose=True,
-          return_info=False, int8_slices=None, options=None, summary=False, ess_nfft="matlab", _lib=None):
+          return_info=False, int8_slices=None, options=None, summary=False, ess_nfft="matlab", diagnostics=False, max_lag=None, _lib=None):
     """ RIEMANNIAN HAMILTONIAN MONTE CARLO (Bayesian logistic regression, N(0, alpha I) prior) """
     XX = np.ascontiguousarray(XX, dtype=np.float64)
     if XX.ndim != 2:
@@ -72,6 +76,10 @@ def RMHMC(XX, t, NumOfIterations=6000, BurnIn=1000, NumOfLeapFrogSteps=6, StepSi
     if not BurnIn < NumOfIterations:
         # the reference raises NameError here (`start` unbound, rmhmc.py:194-198)
         raise ValueError("BurnIn must be smaller than NumOfIterations")
+    if diagnostics and not return_info:
+        raise ValueError("diagnostics=True returns its result in the info dict: it needs return_info=True")
+    if diagnostics:
+        _capi.diag_lags(NumOfIterations - BurnIn, max_lag)
     ess = _capi.ess_flags(ess_nfft)
     if seed is None:
         seed = int(np.random.randint(0, 2 ** 62))
@@ -81,7 +89,13 @@ def RMHMC(XX, t, NumOfIterations=6000, BurnIn=1000, NumOfLeapFrogSteps=6, StepSi
         ctx.set_data(XX, t, alpha)
         if verbose:
             ctx.set_progress(progress_printer(n_chains))
-        if summary:
+        st = None
+        if diagnostics:   # (include/rmhmc_diag.h: the same run through the output descriptor, its samples kept on the device)
+            st = ctx.sample_to("rmhmc", NumOfIterations, BurnIn, samples=not summary, stats=summary, run_mean=summary, diagnostics=True,
+                               max_lag=max_lag, L=NumOfLeapFrogSteps, eps=StepSize, K=NumOfNewtonSteps, seed=seed,
+                               chain_offset=chain_offset, theta0=theta0)
+            samples, acc, steps, seconds = st.get("samples"), st["accepted"], st["leapfrog_steps"], st["seconds"]
+        elif summary:
             st = ctx.sample_stats(NumOfIterations, BurnIn, NumOfLeapFrogSteps, StepSize, NumOfNewtonSteps, seed=seed,
                                   chain_offset=chain_offset, theta0=theta0, run_mean=True)
             samples, acc, steps, seconds = None, st["accepted"], st["leapfrog_steps"], st["seconds"]
@@ -93,5 +107,5 @@ def RMHMC(XX, t, NumOfIterations=6000, BurnIn=1000, NumOfLeapFrogSteps=6, StepSi
         print('Time drawing posterior: {}'.format(seconds))
     wSaved = {k: st[k] for k in _capi.SUMMARY_KEYS} if summary else samples[0] if n_chains == 1 else samples
     if return_info:
-        return wSaved, seconds, dict(accepted=acc, leapfrog_steps=steps, seed=seed)
+        return wSaved, seconds, dict(accepted=acc, leapfrog_steps=steps, seed=seed, **_capi.diag_info(st, diagnostics))
     return wSaved, seconds
