@@ -81,7 +81,12 @@ typedef struct rmhmc_ctx rmhmc_ctx;
                                           trace term tr(G^-1 dG/dw_d) (rmhmc.py:64-77,142-156: it only enters the momentum updates).  The
                                           last iterate and every evaluation point (G, log det, gradient: everything that enters the
                                           Hamiltonian and rmhmc_metric) always use all 6.  Effect on theta / p after a step: < 1e-11
-                                          relative (tests/test_gpu_int8_metric.py). */
+                                          relative (tests/test_gpu_int8_metric.py).  Data sets with fewer than 4 rows per column
+                                          (M < 4 D: the prior dominates the metric, and the grid of G^-1 is relative to its largest
+                                          entry) keep all 6 slices for the leverages whatever this flag says.  That is a heuristic
+                                          on the shape, standing in for cond(G): the 5-slice trace term is off by about
+                                          3e-11 cond(G), so ill-conditioned data with M >= 4 D (a strong prior, near-collinear
+                                          columns) should set this flag. */
 #define RMHMC_FLAG_MMALA_FULL (1u << 6)  /* rmhmc_mmala_*: the full manifold MALA of BLR_mMALA.m (drift with the metric-
                                           derivative terms) instead of the simplified one of BLR_mMALA_Simp.m */
 #define RMHMC_FLAG_ESS_WRAP (1u << 9)     /* rmhmc_ess / rmhmc_sample_stats: autocorrelations exactly as the reference's PYTHON

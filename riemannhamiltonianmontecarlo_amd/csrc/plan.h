@@ -120,6 +120,7 @@ struct Plan {
   bool tail_always = false;  // option i8_tail = 1: the tail kernel runs whenever there is a ragged block (-1: when it pays)
   int tail_pieces = 1, tail_blocks = 0;  // k pieces the accumulators have room for; 32-pair blocks of the ragged rest
   bool gbase = false;        // large-D path: a copy of the G a delta assembly adds to
+  bool i8_lev_full = false;  // the leverage GEMM sums all S slices whatever the inner-iterate rule says (M < 4 D, see make_plan)
   // the stepping path
   bool fused = false;        // small-problem path: D <= 8 and X fits in LDS (fused_small.hip.h)
   size_t fused_lds = 0;
@@ -184,6 +185,13 @@ inline Plan make_plan(int64_t M, int32_t D, int64_t n_chains, uint32_t flags, co
     p.i8_NRp = (p.Mp + p.i8_bn - 1) / p.i8_bn * p.i8_bn;
     p.nCp = (int)((n_chains + I8_BM - 1) / I8_BM * I8_BM);
     p.gbase = p.big && opt.i8_delta && S == 6;
+    // Leverages h_n = x_n' G^-1 x_n: G^-1 is cut on a grid relative to its LARGEST entry (k_qsplit).  With fewer than a few rows per
+    // column the prior's alpha enters G^-1 at full size while h_n sees the data directions only, so the grid step is amplified by
+    // cond(G): measured on an MI355X from the 5 most significant of 6 slices, trace term against the fp64 oracle 3e-11 cond(G) - 4e-11
+    // at M = 4.8 D (cond 7), 1e-10 at 2.5 D (18), 1.4e-9 at 1.2 D (400), 1.6e-7 at M = 31 < D = 70 (4400), and momentum after one
+    // step 3e-9 there.  Below 4 rows per column the leverage GEMM therefore keeps every slice (7e-10 at cond 4700).  A heuristic on the shape:
+    // cond(G) depends on alpha and the data too, and ill-conditioned data with M >= 4 D still gets 5 slices (RMHMC_FLAG_INT8_INNER_FULL).
+    p.i8_lev_full = M < 4 * (int64_t)D;
     // small batches: cut the k range so that about 256 workgroups exist (at least 8 stages per piece, at most 16 pieces; only
     // when the whole range fits one overflow-safe launch)
     auto pieces = [&](long long tiles, int stages) {

@@ -501,8 +501,9 @@ void launch_leverage(rmhmc_ctx* ctx, Group& g, int part = 0) {
     launch(ctx, "qsplit", [&](hipStream_t st) { I8_SWITCH(ctx, (launch_leverage_i8_t<S_, WN_, TN_>(ctx, g, st, 0))); });
     // The leverages h_n = x_n' G^-1 x_n enter the trace term only, which steers the momentum and appears in no Hamiltonian: like the metric
     // of an inner position iterate they are summed from the S - 1 most significant slices of the same operands (15 slice products
-    // instead of 21; h to ~3e-12 norm-wise, theta / p after a step move by < 1e-11; RMHMC_FLAG_INT8_INNER_FULL: all S)
-    const int suse = (ctx->i8_inner_drop && ctx->i8S == 6) ? 5 : ctx->i8S;
+    // instead of 21; h to ~3e-12 norm-wise, theta / p after a step move by < 1e-11; RMHMC_FLAG_INT8_INNER_FULL: all S) - unless the
+    // data set has so few rows per column that the metric is ill-conditioned (Plan::i8_lev_full)
+    const int suse = (ctx->i8_inner_drop && ctx->i8S == 6 && !ctx->i8_lev_full) ? 5 : ctx->i8S;
     launch(ctx, "leverage_i8", [&](hipStream_t st) { I8_SWITCH_S(suse, (launch_leverage_i8_t<S_, WN_, TN_>(ctx, g, st, 1))); });
     if (part == 1) return;
     launch(ctx, "trvec", [&](hipStream_t st) {

@@ -48,9 +48,9 @@ int main() {
                 (long long)p.M, p.D, (long long)p.n, p.NB, p.DP, p.Mp, p.nblk, (int)p.big, p.nbk, p.npairs, p.nsplit, p.fsplit, p.gpart_planes,
                 (int)p.hpart_at_create);
     std::printf("\"i8_requested\": %d, \"i8S\": %d, \"i8_chunk\": %d, \"i8_bn\": %d, \"i8_nks\": %d, \"NP\": %d, \"NPp\": %d, \"i8_nkp\": %d, \"i8_NRp\": %d, "
-                "\"nCp\": %d, \"ksplit_a\": %d, \"ksplit_l\": %d, \"tail_acc\": %d, \"tail_always\": %d, \"tail_pieces\": %d, \"tail_blocks\": %d, \"gbase\": %d, ",
+                "\"nCp\": %d, \"ksplit_a\": %d, \"ksplit_l\": %d, \"tail_acc\": %d, \"tail_always\": %d, \"tail_pieces\": %d, \"tail_blocks\": %d, \"gbase\": %d, \"i8_lev_full\": %d, ",
                 (int)p.i8_requested, p.i8S, p.i8_chunk, p.i8_bn, p.i8_nks, p.NP, p.NPp, p.i8_nkp, p.i8_NRp, p.nCp, p.ksplit_a, p.ksplit_l, (int)p.tail_acc,
-                (int)p.tail_always, p.tail_pieces, p.tail_blocks, (int)p.gbase);
+                (int)p.tail_always, p.tail_pieces, p.tail_blocks, (int)p.gbase, (int)p.i8_lev_full);
     std::printf("\"fused\": %d, \"fused_lds\": %zu, \"medium\": %d, \"medium_lds\": %zu, \"hmc_traj\": %d}", (int)p.fused, p.fused_lds, (int)p.medium,
                 p.medium_lds, (int)p.hmc_traj);
     if (p.i8_requested) {
