@@ -233,7 +233,8 @@ int rmhmc_transition(rmhmc_ctx *ctx, double *w, const double *z,
  *     accept_out[n] | NULL : accepted proposals over all n_iter iterations.
  *     steps_out[n]  | NULL : leapfrog steps executed after burn-in.
  *     seconds_out   | NULL : wall seconds of the post-burn-in phase
- *                            (TimeTaken, rmhmc.py:194-198).                  */
+ *                            (TimeTaken, rmhmc.py:194-198).
+ *     In librmhmc_hip.so: rmhmc_sample_to (rmhmc_out.h) with {RMHMC_OUT_HOST, samples_out}. */
 int rmhmc_sample(rmhmc_ctx *ctx, int64_t n_iter, int64_t burn_in, int32_t L,
                  double eps, int32_t K, uint64_t seed, int64_t chain_offset,
                  const double *theta0, double *samples_out,
@@ -285,7 +286,8 @@ int rmhmc_hmc_transition(rmhmc_ctx *ctx, double *w, const double *z, const doubl
                          double *w_prop_out, double *p_prop_out);
 
 /* HMC(XX, t, n_iter, burn_in, L, eps) for all chains; arguments as rmhmc_sample
- * (theta0 NULL: zeros, hmc.py:27).                                                                     */
+ * (theta0 NULL: zeros, hmc.py:27).  In librmhmc_hip.so: rmhmc_hmc_sample_to (rmhmc_out.h) with
+ * {RMHMC_OUT_HOST, samples_out}.                                                                       */
 int rmhmc_hmc_sample(rmhmc_ctx *ctx, int64_t n_iter, int64_t burn_in, int32_t L, double eps,
                      uint64_t seed, int64_t chain_offset, const double *theta0,
                      double *samples_out, int64_t *accept_out, int64_t *steps_out,
@@ -304,7 +306,11 @@ int rmhmc_ess(rmhmc_ctx *ctx, const double *samples, int64_t n, int64_t S, int32
 
 /* rmhmc_sample without the sample transfer: per-chain posterior mean / population variance / ESS of every
  * dimension over the S = n_iter-burn_in saved states, reduced on the device (config 4 at S = 5000 would be
- * 168 GB of raw samples).  mean_out, var_out, ess_out: [n*D], each optional.                            */
+ * 168 GB of raw samples).  mean_out, var_out, ess_out: [n*D], each optional (all three NULL: the sampler
+ * runs, the counters and seconds_out are returned).  2 <= n_iter-burn_in <= 20000, the limit of rmhmc_ess:
+ * otherwise RMHMC_ERR_UNSUPPORTED, and from librmhmc_hip.so before any sampling work, whatever is requested
+ * (it used to run the whole sampler first and fail in the reduction, with the same code).  In librmhmc_hip.so:
+ * rmhmc_sample_to (rmhmc_out.h) with {RMHMC_OUT_HOST, NULL, mean_out, var_out, ess_out}.                  */
 int rmhmc_sample_stats(rmhmc_ctx *ctx, int64_t n_iter, int64_t burn_in, int32_t L, double eps, int32_t K,
                        uint64_t seed, int64_t chain_offset, const double *theta0, double *mean_out,
                        double *var_out, double *ess_out, int64_t *accept_out, int64_t *steps_out,
@@ -346,7 +352,9 @@ int rmhmc_int8_certificate(rmhmc_ctx *ctx, double *bound_out, int32_t *active_ou
  * contiguous; each may be NULL).  Nothing crosses PCIe: the sampler saves straight into samples_dev, so that the multi-GPU
  * driver can hand the buffers to RCCL (ncclGather / all_gather over xGMI) without a host bounce.  Inputs (theta0) and the
  * scalar seconds_out stay host memory.  The calls are synchronous: the library's stream is idle on return, so any other
- * stream may read the buffers afterwards.  In the CPU oracle "device" memory is host memory.                              */
+ * stream may read the buffers afterwards.  In the CPU oracle "device" memory is host memory.  In librmhmc_hip.so
+ * rmhmc_sample_dev is rmhmc_sample_to (rmhmc_out.h) with {RMHMC_OUT_DEVICE, samples_dev}, and rmhmc_sample_stats_dev is
+ * rmhmc_sample_to with {RMHMC_OUT_DEVICE, NULL, mean_dev, var_dev, ess_dev}: the limit of rmhmc_sample_stats, refused as there. */
 int rmhmc_chains_state_dev(rmhmc_ctx *ctx, double *w_dev, int64_t *iters_dev, int64_t *accept_dev);
 int rmhmc_sample_dev(rmhmc_ctx *ctx, int64_t n_iter, int64_t burn_in, int32_t L, double eps, int32_t K, uint64_t seed,
                      int64_t chain_offset, const double *theta0, double *samples_dev, int64_t *accept_dev,
@@ -365,6 +373,7 @@ int rmhmc_sample_stats_dev(rmhmc_ctx *ctx, int64_t n_iter, int64_t burn_in, int3
  * Uses the metric / gradient / Cholesky kernels of the RMHMC path; one point evaluation per transition.   */
 int rmhmc_mmala_transition(rmhmc_ctx *ctx, double *w, const double *z, const double *u_acc, double eps,
                            int32_t *accepted_out, double *ratio_out, double *w_prop_out);
+/* In librmhmc_hip.so: rmhmc_mmala_sample_to (rmhmc_out.h) with {RMHMC_OUT_HOST, samples_out}. */
 int rmhmc_mmala_sample(rmhmc_ctx *ctx, int64_t n_iter, int64_t burn_in, double eps, uint64_t seed,
                        int64_t chain_offset, const double *theta0, double *samples_out,
                        int64_t *accept_out, double *seconds_out);

@@ -31,7 +31,8 @@ extern "C" {
  * after burn_in (metropolis.py:93-96).  A progress callback (rmhmc_set_progress) is called with
  * RMHMC_EV_PROGRESS and i after iteration i for i % 1000 == 0, i < burn_in, and with
  * RMHMC_EV_BURNIN_DONE and burn_in after iteration burn_in.  theta0 [n][D], accepted_out, sd_out and
- * seconds_out may be NULL.  0 <= burn_in < n_iter < 2^32. */
+ * seconds_out may be NULL.  0 <= burn_in < n_iter < 2^32.
+ * Equivalent to rmhmc_amh_sample_to (rmhmc_out.h) with the descriptor {RMHMC_OUT_HOST, samples_out}. */
 int rmhmc_amh_sample(rmhmc_ctx *ctx, int64_t n_iter, int64_t burn_in, uint64_t seed, int64_t chain_offset,
                      const double *theta0, double *samples_out, int64_t *accepted_out, double *sd_out,
                      double *seconds_out);

@@ -35,7 +35,8 @@ extern "C" {
  * iteration burn_in to the end of the last iteration (:100-101,137).  A progress callback (rmhmc_set_progress; its first / every are
  * not used) is called with RMHMC_EV_PROGRESS and i before every iteration i % 100 == 0 (:97-98); the timer starts after the call
  * at burn_in.  Z_out and lam_out [n][N]: the state after the last iteration (of a stopped chain: the state it stopped in).  capped_out,
- * stopped_out, Z_out, lam_out and seconds_out may be NULL.  0 <= burn_in < n_iter < 2^32. */
+ * stopped_out, Z_out, lam_out and seconds_out may be NULL.  0 <= burn_in < n_iter < 2^32.
+ * Equivalent to rmhmc_gibbs_sample_to (rmhmc_out.h) with the descriptor {RMHMC_OUT_HOST, samples_out}, plus Z_out and lam_out. */
 int rmhmc_gibbs_sample(rmhmc_ctx *ctx, int64_t n_iter, int64_t burn_in, uint64_t seed, int64_t chain_offset, double *samples_out,
                        int64_t *capped_out, int64_t *stopped_out, double *Z_out, double *lam_out, double *seconds_out);
 

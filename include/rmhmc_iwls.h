@@ -29,7 +29,8 @@ extern "C" {
  * (rmhmc_set_progress; its first / every are not used) is called with RMHMC_EV_PROGRESS and i before iteration i for every
  * i % 1000 == 0, then with RMHMC_EV_BURNIN_DONE and burn_in before iteration burn_in (accepted_total: summed over the chains);
  * the timer starts after those calls.  theta0 [n][D], accepted_out, saturated_out and seconds_out may be NULL.
- * 0 <= burn_in < n_iter < 2^32. */
+ * 0 <= burn_in < n_iter < 2^32.
+ * Equivalent to rmhmc_iwls_sample_to (rmhmc_out.h) with the descriptor {RMHMC_OUT_HOST, samples_out}. */
 int rmhmc_iwls_sample(rmhmc_ctx *ctx, int64_t n_iter, int64_t burn_in, int32_t compat, uint64_t seed, int64_t chain_offset,
                       const double *theta0, double *samples_out, int64_t *accepted_out, int64_t *saturated_out,
                       double *seconds_out);

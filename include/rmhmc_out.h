@@ -16,7 +16,9 @@
  * stream of its own that is not ordered against any other: work of the caller that writes a device
  * buffer handed to these functions (an input of rmhmc_ess_dev, or a fill of an output) must have finished
  * before the call.  rmhmc_kernel_time(ctx, "write_out", &s, NULL) returns the host wall time of the last
- * call's write-out (copies and reductions, from the end of the sampling to the idle stream).
+ * call's write-out (copies and reductions, from the end of the sampling to the idle stream).  The older
+ * *_sample, *_sample_dev and *_sample_stats[_dev] entry points write out the same way (each is the
+ * *_sample_to call with a descriptor of its own, named at its declaration), so the figure reflects them too.
  */
 #ifndef RMHMC_OUT_H
 #define RMHMC_OUT_H

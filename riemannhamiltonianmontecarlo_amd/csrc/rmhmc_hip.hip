@@ -1485,13 +1485,112 @@ static int run_sorted_phase(rmhmc_ctx* ctx, const Run& run, const IterBase& ib, 
   return RMHMC_OK;
 }
 
-// per-chain counters of a sampler run, on the device in the caller's order: accepted proposals and post-burn-in leapfrog steps
-struct Counters { const long long *accepted, *steps; };
+}  // extern "C"
 
-// Runs the RMHMC sampler; the saved states go to the device buffer d_samples ([n][S][D], caller-provided) and `counters` says where
-// the run left its counters.  asked: the call's parameters in the caller's order (orig == nullptr); a work-sorted run steps with a
-// copy that carries the map.
-static int sample_core(rmhmc_ctx* ctx, const Run& asked, int64_t n_iter, int64_t burn_in, const double* theta0, double* d_samples, double* seconds_out, Counters* counters) {
+// ---- the write-out of a sampling call: to host or device memory, raw or reduced (include/rmhmc_out.h, output.hip.h) ------------------
+// Every sampler has one body (sample_body, hmc_sample_body, ...) behind its two C entry points: the sampler's argument check, the
+// statistics limit, the sample_to frame below and the counters.  <name>_sample_to checks its descriptor (out_check) and calls the body;
+// the older <name>_sample[_dev|_stats|_stats_dev] checks what only it requires and calls the body with a descriptor of its own.  `who`
+// is the entry point that was called, for the error text.
+namespace {
+
+// ESS / posterior summaries on the device (tools.py:32-74)
+int launch_ess(rmhmc_ctx* ctx, const double* d_samples, long long nblocks, long long S, int P, double* d_ess, double* d_mean, double* d_var) {
+  if (S < 2 || S > 20000) return fail(ctx, RMHMC_ERR_UNSUPPORTED, "ess: 2 <= S <= 20000 samples per chain (the centred series is held in LDS)");
+  HIPCK(hipFuncSetAttribute((const void*)k_ess, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS));  // per device: set where it is used
+  long long nfft = 0;
+  if (ctx->flags & RMHMC_FLAG_ESS_WRAP) { nfft = 1; while (nfft < S) nfft *= 2; nfft += 1; }  // tools.py:16-23
+  hipLaunchKernelGGL(k_ess, dim3((unsigned)(nblocks * P)), dim3(64), (size_t)S * sizeof(double), ctx->stream, d_samples, S, P, d_ess, d_mean, d_var, nfft);
+  return RMHMC_OK;
+}
+
+hipMemcpyKind out_kind(const rmhmc_out& out) { return out.where == RMHMC_OUT_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost; }
+bool out_stats(const rmhmc_out& out) { return out.mean || out.var || out.ess || out.run_mean || out.run_ess; }
+
+// the refusals of a caller's descriptor (the *_sample_to entry points only: the older ones build theirs, and rmhmc_sample_stats may
+// ask for nothing but the counters)
+int out_check(rmhmc_ctx* ctx, const char* who, const rmhmc_out* out) {
+  if (!out) return fail(ctx, RMHMC_ERR_INVALID, std::string(who) + ": NULL output descriptor");
+  if (out->where != RMHMC_OUT_HOST && out->where != RMHMC_OUT_DEVICE)
+    return fail(ctx, RMHMC_ERR_INVALID, std::string(who) + ": where must be RMHMC_OUT_HOST or RMHMC_OUT_DEVICE");
+  if (!out->samples && !out_stats(*out)) return fail(ctx, RMHMC_ERR_INVALID, std::string(who) + ": the output descriptor requests no output");
+  return RMHMC_OK;
+}
+
+// The statistics limit, in every body after its argument check and before any sampling work.  A descriptor without raw samples is a
+// statistics call even where every statistic is NULL (legal for rmhmc_sample_stats[_dev]): the limit holds for it all the same.
+int stats_limit(rmhmc_ctx* ctx, const char* who, const rmhmc_out& out, int64_t S) {
+  if ((!out.samples || out_stats(out)) && (S < 2 || S > 20000))
+    return fail(ctx, RMHMC_ERR_UNSUPPORTED, std::string(who) + ": statistics need 2 <= n_iter - burn_in <= 20000 (the ESS kernel holds one series in LDS)");
+  return RMHMC_OK;
+}
+
+// The write-out of a call: d_samples [n][S][D] in device memory -> whatever `out` requests, copied or reduced.  Returns with the
+// stream idle and its own buffers freed.  Its wall time (the sampler has synchronised: the stream holds the counter copies at most) is
+// kept for rmhmc_kernel_time "write_out".
+int write_out(rmhmc_ctx* ctx, const double* d_samples, size_t n, size_t S, size_t D, const rmhmc_out& out) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const hipMemcpyKind kind = out_kind(out);
+  const size_t nd = n * D, sd = S * D;
+  double* d_st = nullptr;  // [3][n][D]: ess, mean, var
+  double* d_rm = nullptr;  // [S][D] run mean, then [D] its ess
+  const int rc = [&]() -> int {
+    if (out.samples && out.samples != d_samples) HIPCK(hipMemcpyAsync(out.samples, d_samples, sizeof(double) * n * sd, kind, ctx->stream));
+    if (out.mean || out.var || out.ess) {
+      HIPCK(hipMalloc((void**)&d_st, sizeof(double) * 3 * nd));
+      RC(launch_ess(ctx, d_samples, (long long)n, (long long)S, (int)D, d_st, d_st + nd, d_st + 2 * nd));
+      if (out.ess) HIPCK(hipMemcpyAsync(out.ess, d_st, sizeof(double) * nd, kind, ctx->stream));
+      if (out.mean) HIPCK(hipMemcpyAsync(out.mean, d_st + nd, sizeof(double) * nd, kind, ctx->stream));
+      if (out.var) HIPCK(hipMemcpyAsync(out.var, d_st + 2 * nd, sizeof(double) * nd, kind, ctx->stream));
+    }
+    if (out.run_mean || out.run_ess) {
+      HIPCK(hipMalloc((void**)&d_rm, sizeof(double) * (sd + D)));
+      hipLaunchKernelGGL(k_run_mean, dim3((unsigned)((sd + 255) / 256)), dim3(256), 0, ctx->stream, d_samples, n, sd, d_rm);
+      if (out.run_ess) RC(launch_ess(ctx, d_rm, 1, (long long)S, (int)D, d_rm + sd, nullptr, nullptr));
+      if (out.run_mean) HIPCK(hipMemcpyAsync(out.run_mean, d_rm, sizeof(double) * sd, kind, ctx->stream));
+      if (out.run_ess) HIPCK(hipMemcpyAsync(out.run_ess, d_rm + sd, sizeof(double) * D, kind, ctx->stream));
+    }
+    return sync(ctx);
+  }();
+  ctx->write_out_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  if (d_st) (void)hipFree(d_st);
+  if (d_rm) (void)hipFree(d_rm);
+  return rc;
+}
+
+// a per-chain counter to the memory space of the descriptor (dst may be NULL)
+template <typename T>
+int counter_out(rmhmc_ctx* ctx, const rmhmc_out& out, int64_t* dst, const T* src) {
+  static_assert(sizeof(T) == sizeof(int64_t), "int64");
+  if (dst) HIPCK(hipMemcpyAsync(dst, src, sizeof(int64_t) * ctx->n, out_kind(out), ctx->stream));
+  return RMHMC_OK;
+}
+
+// One sampling call after its checks.  core(d_samples) runs the sampler into d_samples [n][S][D] and queues its counter copies; the
+// samples go straight into the caller's buffer where that is device memory, into a buffer of the call's otherwise.
+template <typename F>
+int sample_to(rmhmc_ctx* ctx, int64_t S, const rmhmc_out& out, F&& core) {
+  const size_t n = ctx->n, D = ctx->D;
+  const bool direct = out.where == RMHMC_OUT_DEVICE && out.samples;
+  double* d_samples = direct ? out.samples : nullptr;
+  if (!direct) HIPCK(hipMalloc((void**)&d_samples, sizeof(double) * n * (size_t)S * D));
+  const int rc = [&]() -> int {
+    RC(core(d_samples));
+    return write_out(ctx, d_samples, n, (size_t)S, D, out);
+  }();
+  if (!direct) (void)hipFree(d_samples);
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Runs the RMHMC sampler; the saved states go to the device buffer d_samples ([n][S][D], caller-provided).  *accepted and *steps say
+// where the run left its per-chain counters, on the device in the caller's order: accepted proposals and post-burn-in leapfrog
+// steps.  asked: the call's parameters in the caller's order (orig == nullptr); a work-sorted run steps with a copy that carries the map.
+static int sample_core(rmhmc_ctx* ctx, const Run& asked, int64_t n_iter, int64_t burn_in, const double* theta0, double* d_samples, double* seconds_out,
+                       const long long** accepted, const long long** steps) {
   const long long S = n_iter - burn_in;
   const int n = (int)ctx->n;
   // work-sorted layout (see run_sorted_phase): generic and one-launch stepping paths
@@ -1537,65 +1636,72 @@ static int sample_core(rmhmc_ctx* ctx, const Run& asked, int64_t n_iter, int64_t
   RC(sync(ctx));
   if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   hipLaunchKernelGGL(k_sub_ll, dim3((unsigned)((ctx->n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_steps0, ctx->batch.ch.steps_done, (size_t)ctx->n);
-  *counters = Counters{ctx->batch.ch.accepted, ctx->d_steps0};
+  *accepted = ctx->batch.ch.accepted; *steps = ctx->d_steps0;
   if (sorted) {  // counters back into the caller's order: d_T[0..n) accepted, d_T[n..2n) post-burn-in steps
     const dim3 grid((unsigned)((n + 255) / 256));
     hipLaunchKernelGGL(k_scatter_ll, grid, dim3(256), 0, ctx->stream, ctx->d_T, ctx->batch.ch.accepted, ctx->d_orig, (size_t)n);
     hipLaunchKernelGGL(k_scatter_ll, grid, dim3(256), 0, ctx->stream, ctx->d_T + n, ctx->d_steps0, ctx->d_orig, (size_t)n);
-    *counters = Counters{ctx->d_T, ctx->d_T + n};
+    *accepted = ctx->d_T; *steps = ctx->d_T + n;
   }
   return RMHMC_OK;
 }
-// the counters of sample_core to host or device int64 arrays (either may be NULL)
-static int sample_counters(rmhmc_ctx* ctx, const Counters& c, int64_t* accept_out, int64_t* steps_out, hipMemcpyKind kind) {
-  static_assert(sizeof(long long) == sizeof(int64_t), "int64");
-  if (accept_out) HIPCK(hipMemcpyAsync(accept_out, c.accepted, sizeof(int64_t) * ctx->n, kind, ctx->stream));
-  if (steps_out) HIPCK(hipMemcpyAsync(steps_out, c.steps, sizeof(int64_t) * ctx->n, kind, ctx->stream));
-  return RMHMC_OK;
-}
 
-static int sample_impl(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L, double eps, int32_t K, uint64_t seed, int64_t chain_offset,
-                       const double* theta0, double* samples_out, int64_t* accept_out, int64_t* steps_out, double* seconds_out, bool dev) {
-  NEED_DATA(ctx);
-  if (!samples_out || burn_in < 0 || burn_in >= n_iter || L < 1 || K < 1)
-    return fail(ctx, RMHMC_ERR_INVALID, "sample: need samples_out, 0 <= burn_in < n_iter, L >= 1, K >= 1");
+static int sample_body(rmhmc_ctx* ctx, const char* who, int64_t n_iter, int64_t burn_in, int32_t L, double eps, int32_t K, uint64_t seed,
+                       int64_t chain_offset, const double* theta0, const rmhmc_out& out, int64_t* accept_out, int64_t* steps_out,
+                       double* seconds_out) {
+  if (burn_in < 0 || burn_in >= n_iter || L < 1 || K < 1)
+    return fail(ctx, RMHMC_ERR_INVALID, std::string(who) + ": need 0 <= burn_in < n_iter, L >= 1, K >= 1");
+  RC(stats_limit(ctx, who, out, n_iter - burn_in));
   ctx->chains_ready = false;
   const Run run{RMHMC, L, K, eps, seed, chain_offset, nullptr};
-  const size_t count = (size_t)ctx->n * (n_iter - burn_in) * ctx->D;
-  double* d_samples = dev ? samples_out : nullptr;  // device-resident write-out: the sampler saves straight into the caller's HBM buffer
-  if (!dev) HIPCK(hipMalloc((void**)&d_samples, sizeof(double) * count));
-  int rc = [&]() -> int {
-    Counters counters{};
-    RC(sample_core(ctx, run, n_iter, burn_in, theta0, d_samples, seconds_out, &counters));
-    if (!dev) HIPCK(hipMemcpyAsync(samples_out, d_samples, sizeof(double) * count, hipMemcpyDeviceToHost, ctx->stream));
-    RC(sample_counters(ctx, counters, accept_out, steps_out, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
-    return sync(ctx);
-  }();
-  if (!dev && d_samples) (void)hipFree(d_samples);
-  return rc;
+  return sample_to(ctx, n_iter - burn_in, out, [&](double* d_samples) -> int {
+    const long long *accepted = nullptr, *steps = nullptr;
+    RC(sample_core(ctx, run, n_iter, burn_in, theta0, d_samples, seconds_out, &accepted, &steps));
+    RC(counter_out(ctx, out, accept_out, accepted));
+    return counter_out(ctx, out, steps_out, steps);
+  });
 }
 
 int rmhmc_sample(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L, double eps, int32_t K, uint64_t seed,
                  int64_t chain_offset, const double* theta0, double* samples_out, int64_t* accept_out, int64_t* steps_out,
                  double* seconds_out) {
-  return sample_impl(ctx, n_iter, burn_in, L, eps, K, seed, chain_offset, theta0, samples_out, accept_out, steps_out, seconds_out, false);
+  NEED_DATA(ctx);
+  if (!samples_out) return fail(ctx, RMHMC_ERR_INVALID, "sample: need samples_out");
+  return sample_body(ctx, "sample", n_iter, burn_in, L, eps, K, seed, chain_offset, theta0, {RMHMC_OUT_HOST, samples_out}, accept_out,
+                     steps_out, seconds_out);
 }
+// (the sampler saves straight into the caller's HBM buffer: sample_to)
 int rmhmc_sample_dev(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L, double eps, int32_t K, uint64_t seed,
                      int64_t chain_offset, const double* theta0, double* samples_dev, int64_t* accept_dev, int64_t* steps_dev,
                      double* seconds_out) {
-  return sample_impl(ctx, n_iter, burn_in, L, eps, K, seed, chain_offset, theta0, samples_dev, accept_dev, steps_dev, seconds_out, true);
+  NEED_DATA(ctx);
+  if (!samples_dev) return fail(ctx, RMHMC_ERR_INVALID, "sample_dev: need samples_dev");
+  return sample_body(ctx, "sample_dev", n_iter, burn_in, L, eps, K, seed, chain_offset, theta0, {RMHMC_OUT_DEVICE, samples_dev}, accept_dev,
+                     steps_dev, seconds_out);
+}
+// (all three statistics may be NULL: the descriptor then asks for nothing, and the call returns the counters and the time)
+int rmhmc_sample_stats(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L, double eps, int32_t K, uint64_t seed,
+                       int64_t chain_offset, const double* theta0, double* mean_out, double* var_out, double* ess_out,
+                       int64_t* accept_out, int64_t* steps_out, double* seconds_out) {
+  NEED_DATA(ctx);
+  return sample_body(ctx, "sample_stats", n_iter, burn_in, L, eps, K, seed, chain_offset, theta0,
+                     {RMHMC_OUT_HOST, nullptr, mean_out, var_out, ess_out}, accept_out, steps_out, seconds_out);
+}
+int rmhmc_sample_stats_dev(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L, double eps, int32_t K, uint64_t seed,
+                           int64_t chain_offset, const double* theta0, double* mean_dev, double* var_dev, double* ess_dev,
+                           int64_t* accept_dev, int64_t* steps_dev, double* seconds_out) {
+  NEED_DATA(ctx);
+  return sample_body(ctx, "sample_stats_dev", n_iter, burn_in, L, eps, K, seed, chain_offset, theta0,
+                     {RMHMC_OUT_DEVICE, nullptr, mean_dev, var_dev, ess_dev}, accept_dev, steps_dev, seconds_out);
+}
+int rmhmc_sample_to(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L, double eps, int32_t K, uint64_t seed, int64_t chain_offset,
+                    const double* theta0, const rmhmc_out* out, int64_t* accept_out, int64_t* steps_out, double* seconds_out) {
+  NEED_DATA(ctx);
+  RC(out_check(ctx, "sample_to", out));
+  return sample_body(ctx, "sample_to", n_iter, burn_in, L, eps, K, seed, chain_offset, theta0, *out, accept_out, steps_out, seconds_out);
 }
 
-// ---- ESS / posterior summaries on the device (tools.py:32-74) -------------------------------------------
-static int launch_ess(rmhmc_ctx* ctx, const double* d_samples, long long nblocks, long long S, int P, double* d_ess, double* d_mean, double* d_var) {
-  if (S < 2 || S > 20000) return fail(ctx, RMHMC_ERR_UNSUPPORTED, "ess: 2 <= S <= 20000 samples per chain (the centred series is held in LDS)");
-  HIPCK(hipFuncSetAttribute((const void*)k_ess, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS));  // per device: set where it is used
-  long long nfft = 0;
-  if (ctx->flags & RMHMC_FLAG_ESS_WRAP) { nfft = 1; while (nfft < S) nfft *= 2; nfft += 1; }  // tools.py:16-23
-  hipLaunchKernelGGL(k_ess, dim3((unsigned)(nblocks * P)), dim3(64), (size_t)S * sizeof(double), ctx->stream, d_samples, S, P, d_ess, d_mean, d_var, nfft);
-  return RMHMC_OK;
-}
-
+// ---- ESS of given samples (tools.py:32-74; launch_ess above) -------------------------------------------
 int rmhmc_ess(rmhmc_ctx* ctx, const double* samples, int64_t n, int64_t S, int32_t P, double* ess_out) {
   if (!ctx || !samples || !ess_out || n < 1 || P < 1 || n * (int64_t)P > 0x7fffffffLL) return fail(ctx, RMHMC_ERR_INVALID, "ess: bad argument");
   HIPCK(hipSetDevice(ctx->device));
@@ -1613,46 +1719,12 @@ int rmhmc_ess(rmhmc_ctx* ctx, const double* samples, int64_t n, int64_t S, int32
   return rc;
 }
 
-static int sample_stats_impl(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L, double eps, int32_t K, uint64_t seed,
-                             int64_t chain_offset, const double* theta0, double* mean_out, double* var_out, double* ess_out,
-                             int64_t* accept_out, int64_t* steps_out, double* seconds_out, bool dev) {
-  NEED_DATA(ctx);
-  if (burn_in < 0 || burn_in >= n_iter || L < 1 || K < 1)
-    return fail(ctx, RMHMC_ERR_INVALID, "sample_stats: need 0 <= burn_in < n_iter, L >= 1, K >= 1");
-  ctx->chains_ready = false;
-  const Run run{RMHMC, L, K, eps, seed, chain_offset, nullptr};
-  const long long S = n_iter - burn_in;
-  double* d_samples = nullptr;
-  double* d_out = nullptr;  // [3][n][D]: ess, mean, var
-  HIPCK(hipMalloc((void**)&d_samples, sizeof(double) * (size_t)ctx->n * S * ctx->D));
-  int rc = [&]() -> int {
-    Counters counters{};
-    RC(sample_core(ctx, run, n_iter, burn_in, theta0, d_samples, seconds_out, &counters));
-    const size_t nd = (size_t)ctx->n * ctx->D;
-    HIPCK(hipMalloc((void**)&d_out, sizeof(double) * 3 * nd));
-    RC(launch_ess(ctx, d_samples, ctx->n, S, ctx->D, d_out, d_out + nd, d_out + 2 * nd));
-    const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (ess_out) HIPCK(hipMemcpyAsync(ess_out, d_out, sizeof(double) * nd, kind, ctx->stream));
-    if (mean_out) HIPCK(hipMemcpyAsync(mean_out, d_out + nd, sizeof(double) * nd, kind, ctx->stream));
-    if (var_out) HIPCK(hipMemcpyAsync(var_out, d_out + 2 * nd, sizeof(double) * nd, kind, ctx->stream));
-    RC(sample_counters(ctx, counters, accept_out, steps_out, kind));
-    return sync(ctx);
-  }();
-  if (d_samples) (void)hipFree(d_samples);
-  if (d_out) (void)hipFree(d_out);
-  return rc;
-}
-int rmhmc_sample_stats(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L, double eps, int32_t K, uint64_t seed,
-                       int64_t chain_offset, const double* theta0, double* mean_out, double* var_out, double* ess_out,
-                       int64_t* accept_out, int64_t* steps_out, double* seconds_out) {
-  return sample_stats_impl(ctx, n_iter, burn_in, L, eps, K, seed, chain_offset, theta0, mean_out, var_out, ess_out, accept_out, steps_out,
-                           seconds_out, false);
-}
-int rmhmc_sample_stats_dev(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L, double eps, int32_t K, uint64_t seed,
-                           int64_t chain_offset, const double* theta0, double* mean_dev, double* var_dev, double* ess_dev,
-                           int64_t* accept_dev, int64_t* steps_dev, double* seconds_out) {
-  return sample_stats_impl(ctx, n_iter, burn_in, L, eps, K, seed, chain_offset, theta0, mean_dev, var_dev, ess_dev, accept_dev, steps_dev,
-                           seconds_out, true);
+int rmhmc_ess_dev(rmhmc_ctx* ctx, const double* samples_dev, int64_t n, int64_t S, int32_t P, double* ess_dev, double* mean_dev, double* var_dev) {
+  if (!ctx || !samples_dev || (!ess_dev && !mean_dev && !var_dev) || n < 1 || P < 1 || n * (int64_t)P > 0x7fffffffLL)
+    return fail(ctx, RMHMC_ERR_INVALID, "ess_dev: bad argument");
+  HIPCK(hipSetDevice(ctx->device));
+  RC(launch_ess(ctx, samples_dev, n, S, P, ess_dev, mean_dev, var_dev));
+  return sync(ctx);
 }
 
 // ---- plain HMC (code/hmc.py) -------------------------------------------------------------------------
@@ -1699,7 +1771,7 @@ int rmhmc_hmc_transition(rmhmc_ctx* ctx, double* w, const double* z, const doubl
 }
 
 // Runs the plain HMC sampler; the saved states go to the device buffer d_samples ([n][S][D]).  It leaves the accepted proposals in
-// batch.ch.accepted and the leapfrog steps in batch.ch.steps_done, d_steps0 holding their value at the end of burn-in.
+// batch.ch.accepted and, as sample_core, the post-burn-in leapfrog steps in d_steps0.
 static int hmc_sample_core(rmhmc_ctx* ctx, const Run& run, int64_t n_iter, int64_t burn_in, const double* theta0, double* d_samples, double* seconds_out) {
   const long long S = n_iter - burn_in;
   long long progress_next = ctx->progress_first;
@@ -1718,35 +1790,36 @@ static int hmc_sample_core(rmhmc_ctx* ctx, const Run& run, int64_t n_iter, int64
   }
   RC(sync(ctx));
   if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  hipLaunchKernelGGL(k_sub_ll, dim3((unsigned)((ctx->n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_steps0, ctx->batch.ch.steps_done, (size_t)ctx->n);
   return RMHMC_OK;
+}
+
+static int hmc_sample_body(rmhmc_ctx* ctx, const char* who, int64_t n_iter, int64_t burn_in, int32_t L, double eps, uint64_t seed,
+                           int64_t chain_offset, const double* theta0, const rmhmc_out& out, int64_t* accept_out, int64_t* steps_out,
+                           double* seconds_out) {
+  if (burn_in < 0 || burn_in >= n_iter || L < 1) return fail(ctx, RMHMC_ERR_INVALID, std::string(who) + ": need 0 <= burn_in < n_iter, L >= 1");
+  RC(stats_limit(ctx, who, out, n_iter - burn_in));
+  ctx->chains_ready = false;
+  const Run run{HMC, L, 0, eps, seed, chain_offset, nullptr};  // (no fixed-point iterations: no K)
+  return sample_to(ctx, n_iter - burn_in, out, [&](double* d_samples) -> int {
+    RC(hmc_sample_core(ctx, run, n_iter, burn_in, theta0, d_samples, seconds_out));
+    RC(counter_out(ctx, out, accept_out, ctx->batch.ch.accepted));
+    return counter_out(ctx, out, steps_out, ctx->d_steps0);
+  });
 }
 
 int rmhmc_hmc_sample(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L, double eps, uint64_t seed, int64_t chain_offset,
                      const double* theta0, double* samples_out, int64_t* accept_out, int64_t* steps_out, double* seconds_out) {
   NEED_DATA(ctx);
-  if (!samples_out || burn_in < 0 || burn_in >= n_iter || L < 1)
-    return fail(ctx, RMHMC_ERR_INVALID, "hmc_sample: need samples_out, 0 <= burn_in < n_iter, L >= 1");
-  ctx->chains_ready = false;
-  const Run run{HMC, L, 0, eps, seed, chain_offset, nullptr};  // (no fixed-point iterations: no K)
-  const long long S = n_iter - burn_in;
-  double* d_samples = nullptr;
-  HIPCK(hipMalloc((void**)&d_samples, sizeof(double) * (size_t)ctx->n * S * ctx->D));
-  int rc = [&]() -> int {
-    RC(hmc_sample_core(ctx, run, n_iter, burn_in, theta0, d_samples, seconds_out));
-    HIPCK(hipMemcpyAsync(samples_out, d_samples, sizeof(double) * (size_t)ctx->n * S * ctx->D, hipMemcpyDeviceToHost, ctx->stream));
-    std::vector<long long> a(ctx->n), s1(ctx->n), s0(ctx->n);
-    RC(download(ctx, a.data(), ctx->batch.ch.accepted, ctx->n));
-    RC(download(ctx, s1.data(), ctx->batch.ch.steps_done, ctx->n));
-    RC(download(ctx, s0.data(), ctx->d_steps0, ctx->n));
-    RC(sync(ctx));
-    for (int64_t c = 0; c < ctx->n; ++c) {
-      if (accept_out) accept_out[c] = a[c];
-      if (steps_out) steps_out[c] = s1[c] - s0[c];
-    }
-    return RMHMC_OK;
-  }();
-  (void)hipFree(d_samples);
-  return rc;
+  if (!samples_out) return fail(ctx, RMHMC_ERR_INVALID, "hmc_sample: need samples_out");
+  return hmc_sample_body(ctx, "hmc_sample", n_iter, burn_in, L, eps, seed, chain_offset, theta0, {RMHMC_OUT_HOST, samples_out}, accept_out,
+                         steps_out, seconds_out);
+}
+int rmhmc_hmc_sample_to(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L, double eps, uint64_t seed, int64_t chain_offset,
+                        const double* theta0, const rmhmc_out* out, int64_t* accept_out, int64_t* steps_out, double* seconds_out) {
+  NEED_DATA(ctx);
+  RC(out_check(ctx, "hmc_sample_to", out));
+  return hmc_sample_body(ctx, "hmc_sample_to", n_iter, burn_in, L, eps, seed, chain_offset, theta0, *out, accept_out, steps_out, seconds_out);
 }
 
 // ---- simplified manifold MALA (BLR_mMALA_Simp.m) -------------------------------------------------------------
@@ -1802,27 +1875,30 @@ static int mmala_sample_core(rmhmc_ctx* ctx, const Run& run, int64_t n_iter, int
   return RMHMC_OK;
 }
 
+static int mmala_sample_body(rmhmc_ctx* ctx, const char* who, int64_t n_iter, int64_t burn_in, double eps, uint64_t seed, int64_t chain_offset,
+                             const double* theta0, const rmhmc_out& out, int64_t* accept_out, double* seconds_out) {
+  if (burn_in < 0 || burn_in >= n_iter || !(eps > 0)) return fail(ctx, RMHMC_ERR_INVALID, std::string(who) + ": need 0 <= burn_in < n_iter, eps > 0");
+  RC(stats_limit(ctx, who, out, n_iter - burn_in));
+  ctx->chains_ready = false;
+  const Run run{RMHMC, 0, 0, eps, seed, chain_offset, nullptr};
+  return sample_to(ctx, n_iter - burn_in, out, [&](double* d_samples) -> int {
+    RC(mmala_sample_core(ctx, run, n_iter, burn_in, theta0, d_samples, seconds_out));
+    return counter_out(ctx, out, accept_out, ctx->batch.ch.accepted);
+  });
+}
+
 int rmhmc_mmala_sample(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, double eps, uint64_t seed, int64_t chain_offset,
                        const double* theta0, double* samples_out, int64_t* accept_out, double* seconds_out) {
   NEED_DATA(ctx);
-  if (!samples_out || burn_in < 0 || burn_in >= n_iter || !(eps > 0))
-    return fail(ctx, RMHMC_ERR_INVALID, "mmala_sample: need samples_out, 0 <= burn_in < n_iter, eps > 0");
-  ctx->chains_ready = false;
-  const Run run{RMHMC, 0, 0, eps, seed, chain_offset, nullptr};
-  const long long S = n_iter - burn_in;
-  double* d_samples = nullptr;
-  HIPCK(hipMalloc((void**)&d_samples, sizeof(double) * (size_t)ctx->n * S * ctx->D));
-  int rc = [&]() -> int {
-    RC(mmala_sample_core(ctx, run, n_iter, burn_in, theta0, d_samples, seconds_out));
-    HIPCK(hipMemcpyAsync(samples_out, d_samples, sizeof(double) * (size_t)ctx->n * S * ctx->D, hipMemcpyDeviceToHost, ctx->stream));
-    if (accept_out) {
-      static_assert(sizeof(long long) == sizeof(int64_t), "int64");
-      RC(download(ctx, (long long*)accept_out, ctx->batch.ch.accepted, ctx->n));
-    }
-    return sync(ctx);
-  }();
-  (void)hipFree(d_samples);
-  return rc;
+  if (!samples_out) return fail(ctx, RMHMC_ERR_INVALID, "mmala_sample: need samples_out");
+  return mmala_sample_body(ctx, "mmala_sample", n_iter, burn_in, eps, seed, chain_offset, theta0, {RMHMC_OUT_HOST, samples_out}, accept_out,
+                           seconds_out);
+}
+int rmhmc_mmala_sample_to(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, double eps, uint64_t seed, int64_t chain_offset,
+                          const double* theta0, const rmhmc_out* out, int64_t* accept_out, double* seconds_out) {
+  NEED_DATA(ctx);
+  RC(out_check(ctx, "mmala_sample_to", out));
+  return mmala_sample_body(ctx, "mmala_sample_to", n_iter, burn_in, eps, seed, chain_offset, theta0, *out, accept_out, seconds_out);
 }
 
 int rmhmc_chains_init(rmhmc_ctx* ctx, const double* theta0, uint64_t seed, int64_t chain_offset, int32_t L, double eps, int32_t K) {
@@ -1994,6 +2070,24 @@ int amh_run(rmhmc_ctx* ctx, AmhParams p, const double* theta0, double* seconds_o
 
 bool amh_iters_ok(int64_t n_iter, int64_t burn_in) { return burn_in >= 0 && burn_in < n_iter && n_iter <= (int64_t)0xffffffffLL; }
 
+int amh_sample_body(rmhmc_ctx* ctx, const char* who, int64_t n_iter, int64_t burn_in, uint64_t seed, int64_t chain_offset, const double* theta0,
+                    const rmhmc_out& out, int64_t* accepted_out, double* sd_out, double* seconds_out) {
+  if (!amh_iters_ok(n_iter, burn_in) || chain_offset < 0)
+    return fail(ctx, RMHMC_ERR_INVALID, std::string(who) + ": need 0 <= burn_in < n_iter < 2^32, chain_offset >= 0");
+  RC(stats_limit(ctx, who, out, n_iter - burn_in));
+  ctx->chains_ready = false;
+  return sample_to(ctx, n_iter - burn_in, out, [&](double* d_samples) -> int {
+    AmhParams p{};
+    p.samples = d_samples; p.seed = seed; p.chain_offset = chain_offset; p.n_iter = n_iter; p.burn_in = burn_in;
+    RC(amh_run(ctx, p, theta0, seconds_out));
+    RC(counter_out(ctx, out, accepted_out, ctx->batch.ch.accepted));
+    if (sd_out)  // [n][DP] -> [n][D]
+      HIPCK(hipMemcpy2DAsync(sd_out, ctx->D * sizeof(double), ctx->batch.ch.PM, ctx->DP * sizeof(double), ctx->D * sizeof(double), ctx->n,
+                             out_kind(out), ctx->stream));
+    return RMHMC_OK;
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -2001,26 +2095,15 @@ extern "C" {
 int rmhmc_amh_sample(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, uint64_t seed, int64_t chain_offset, const double* theta0,
                      double* samples_out, int64_t* accepted_out, double* sd_out, double* seconds_out) {
   NEED_DATA(ctx);
-  if (!samples_out || !amh_iters_ok(n_iter, burn_in) || chain_offset < 0)
-    return fail(ctx, RMHMC_ERR_INVALID, "amh_sample: need samples_out, 0 <= burn_in < n_iter < 2^32, chain_offset >= 0");
-  ctx->chains_ready = false;
-  const size_t n = ctx->n, D = ctx->D, S = (size_t)(n_iter - burn_in);
-  double* d_samples = nullptr;
-  HIPCK(hipMalloc((void**)&d_samples, sizeof(double) * n * S * D));
-  int rc = [&]() -> int {
-    AmhParams p{};
-    p.samples = d_samples; p.seed = seed; p.chain_offset = chain_offset; p.n_iter = n_iter; p.burn_in = burn_in;
-    RC(amh_run(ctx, p, theta0, seconds_out));
-    HIPCK(hipMemcpyAsync(samples_out, d_samples, sizeof(double) * n * S * D, hipMemcpyDeviceToHost, ctx->stream));
-    std::vector<long long> a(n);
-    RC(download(ctx, a.data(), ctx->batch.ch.accepted, n));
-    if (sd_out) RC(download_vec(ctx, sd_out, ctx->batch.ch.PM));
-    RC(sync(ctx));
-    if (accepted_out) for (size_t c = 0; c < n; ++c) accepted_out[c] = a[c];
-    return RMHMC_OK;
-  }();
-  (void)hipFree(d_samples);
-  return rc;
+  if (!samples_out) return fail(ctx, RMHMC_ERR_INVALID, "amh_sample: need samples_out");
+  return amh_sample_body(ctx, "amh_sample", n_iter, burn_in, seed, chain_offset, theta0, {RMHMC_OUT_HOST, samples_out}, accepted_out, sd_out,
+                         seconds_out);
+}
+int rmhmc_amh_sample_to(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, uint64_t seed, int64_t chain_offset, const double* theta0,
+                        const rmhmc_out* out, int64_t* accepted_out, double* sd_out, double* seconds_out) {
+  NEED_DATA(ctx);
+  RC(out_check(ctx, "amh_sample_to", out));
+  return amh_sample_body(ctx, "amh_sample_to", n_iter, burn_in, seed, chain_offset, theta0, *out, accepted_out, sd_out, seconds_out);
 }
 
 int rmhmc_amh_replay(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, const double* z, const double* u, const double* theta0,
@@ -2135,6 +2218,27 @@ int iwls_run(rmhmc_ctx* ctx, IwlsParams p, long long n_iter, bool sampling, cons
   return RMHMC_OK;
 }
 
+int iwls_sample_body(rmhmc_ctx* ctx, const char* who, int64_t n_iter, int64_t burn_in, int32_t compat, uint64_t seed, int64_t chain_offset,
+                     const double* theta0, const rmhmc_out& out, int64_t* accepted_out, int64_t* saturated_out, double* seconds_out) {
+  if (!amh_iters_ok(n_iter, burn_in) || chain_offset < 0)
+    return fail(ctx, RMHMC_ERR_INVALID, std::string(who) + ": need 0 <= burn_in < n_iter < 2^32, chain_offset >= 0");
+  RC(stats_limit(ctx, who, out, n_iter - burn_in));
+  if (ctx->D > 64) return fail(ctx, RMHMC_ERR_UNSUPPORTED, kIwlsDMsg);
+  ctx->chains_ready = false;
+  const int64_t S = n_iter - burn_in;
+  IwlsState s;
+  const int rc = sample_to(ctx, S, out, [&](double* d_samples) -> int {
+    IwlsParams p{};
+    RC(iwls_alloc(ctx, s, p, compat));
+    p.seed = seed; p.chain_offset = chain_offset; p.burn_in = burn_in; p.S = S; p.samples = d_samples; p.T = n_iter;
+    RC(iwls_run(ctx, p, n_iter, true, theta0, seconds_out));
+    RC(counter_out(ctx, out, accepted_out, ctx->batch.ch.accepted));
+    return counter_out(ctx, out, saturated_out, s.nsat);
+  });
+  iwls_free(s);
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2142,33 +2246,16 @@ extern "C" {
 int rmhmc_iwls_sample(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t compat, uint64_t seed, int64_t chain_offset,
                       const double* theta0, double* samples_out, int64_t* accepted_out, int64_t* saturated_out, double* seconds_out) {
   NEED_DATA(ctx);
-  if (!samples_out || !amh_iters_ok(n_iter, burn_in) || chain_offset < 0)
-    return fail(ctx, RMHMC_ERR_INVALID, "iwls_sample: need samples_out, 0 <= burn_in < n_iter < 2^32, chain_offset >= 0");
-  if (ctx->D > 64) return fail(ctx, RMHMC_ERR_UNSUPPORTED, kIwlsDMsg);
-  ctx->chains_ready = false;
-  const size_t n = ctx->n, D = ctx->D, S = (size_t)(n_iter - burn_in);
-  double* d_samples = nullptr;
-  IwlsState s;
-  int rc = [&]() -> int {
-    HIPCK(hipMalloc((void**)&d_samples, sizeof(double) * n * S * D));
-    IwlsParams p{};
-    RC(iwls_alloc(ctx, s, p, compat));
-    p.seed = seed; p.chain_offset = chain_offset; p.burn_in = burn_in; p.S = (long long)S; p.samples = d_samples; p.T = n_iter;
-    RC(iwls_run(ctx, p, n_iter, true, theta0, seconds_out));
-    HIPCK(hipMemcpyAsync(samples_out, d_samples, sizeof(double) * n * S * D, hipMemcpyDeviceToHost, ctx->stream));
-    std::vector<long long> a(n), b(n);
-    RC(download(ctx, a.data(), ctx->batch.ch.accepted, n));
-    RC(download(ctx, b.data(), s.nsat, n));
-    RC(sync(ctx));
-    for (size_t c = 0; c < n; ++c) {
-      if (accepted_out) accepted_out[c] = a[c];
-      if (saturated_out) saturated_out[c] = b[c];
-    }
-    return RMHMC_OK;
-  }();
-  if (d_samples) (void)hipFree(d_samples);
-  iwls_free(s);
-  return rc;
+  if (!samples_out) return fail(ctx, RMHMC_ERR_INVALID, "iwls_sample: need samples_out");
+  return iwls_sample_body(ctx, "iwls_sample", n_iter, burn_in, compat, seed, chain_offset, theta0, {RMHMC_OUT_HOST, samples_out}, accepted_out,
+                          saturated_out, seconds_out);
+}
+int rmhmc_iwls_sample_to(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t compat, uint64_t seed, int64_t chain_offset,
+                         const double* theta0, const rmhmc_out* out, int64_t* accepted_out, int64_t* saturated_out, double* seconds_out) {
+  NEED_DATA(ctx);
+  RC(out_check(ctx, "iwls_sample_to", out));
+  return iwls_sample_body(ctx, "iwls_sample_to", n_iter, burn_in, compat, seed, chain_offset, theta0, *out, accepted_out, saturated_out,
+                          seconds_out);
 }
 
 int rmhmc_iwls_replay(rmhmc_ctx* ctx, int64_t n_iter, int32_t compat, const double* w_prop, const double* u, const double* theta0,
@@ -2289,6 +2376,33 @@ int gibbs_run(rmhmc_ctx* ctx, const GibbsParams& p, long long n_iter, bool sampl
   return rc;
 }
 
+// Z_host, lam_host: [n][N] in host memory whatever the descriptor says, or NULL - the final state that rmhmc_gibbs_sample returns and
+// rmhmc_gibbs_sample_to does not; copied while the state of the call is alive
+int gibbs_sample_body(rmhmc_ctx* ctx, const char* who, int64_t n_iter, int64_t burn_in, uint64_t seed, int64_t chain_offset, const rmhmc_out& out,
+                      int64_t* capped_out, int64_t* stopped_out, double* Z_host, double* lam_host, double* seconds_out) {
+  if (!amh_iters_ok(n_iter, burn_in) || chain_offset < 0 || chain_offset + ctx->n > (int64_t)1 << 32)
+    return fail(ctx, RMHMC_ERR_INVALID, std::string(who) + ": need 0 <= burn_in < n_iter < 2^32, 0 <= chain_offset, chain_offset + n <= 2^32");
+  RC(stats_limit(ctx, who, out, n_iter - burn_in));
+  if (ctx->D > 64) return fail(ctx, RMHMC_ERR_UNSUPPORTED, kGibbsDMsg);
+  ctx->chains_ready = false;
+  const int64_t S = n_iter - burn_in;
+  GibbsState s;
+  const int rc = sample_to(ctx, S, out, [&](double* d_samples) -> int {
+    HIPCK(hipMemsetAsync(d_samples, 0xff, sizeof(double) * (size_t)ctx->n * (size_t)S * ctx->D, ctx->stream));  // NaN: the rows a stopped chain never writes
+    GibbsParams p{};
+    RC(gibbs_alloc(ctx, s, p));
+    p.seed = seed; p.chain_offset = chain_offset; p.burn_in = burn_in; p.S = S; p.samples = d_samples; p.T = n_iter;
+    RC(gibbs_run(ctx, p, n_iter, true, seconds_out));
+    const size_t n = ctx->n, N = ctx->M, Mp = ctx->Mp;  // [n][Mp] -> [n][N]
+    if (Z_host) HIPCK(hipMemcpy2DAsync(Z_host, N * sizeof(double), s.Z, Mp * sizeof(double), N * sizeof(double), n, hipMemcpyDeviceToHost, ctx->stream));
+    if (lam_host) HIPCK(hipMemcpy2DAsync(lam_host, N * sizeof(double), s.lam, Mp * sizeof(double), N * sizeof(double), n, hipMemcpyDeviceToHost, ctx->stream));
+    RC(counter_out(ctx, out, capped_out, s.capped));
+    return counter_out(ctx, out, stopped_out, s.dead);
+  });
+  gibbs_free(s);
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2296,37 +2410,16 @@ extern "C" {
 int rmhmc_gibbs_sample(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, uint64_t seed, int64_t chain_offset, double* samples_out,
                        int64_t* capped_out, int64_t* stopped_out, double* Z_out, double* lam_out, double* seconds_out) {
   NEED_DATA(ctx);
-  if (!samples_out || !amh_iters_ok(n_iter, burn_in) || chain_offset < 0 || chain_offset + ctx->n > (int64_t)1 << 32)
-    return fail(ctx, RMHMC_ERR_INVALID, "gibbs_sample: need samples_out, 0 <= burn_in < n_iter < 2^32, 0 <= chain_offset, chain_offset + n <= 2^32");
-  if (ctx->D > 64) return fail(ctx, RMHMC_ERR_UNSUPPORTED, kGibbsDMsg);
-  HIPCK(hipSetDevice(ctx->device));
-  ctx->chains_ready = false;
-  const size_t n = ctx->n, D = ctx->D, S = (size_t)(n_iter - burn_in);
-  double* d_samples = nullptr;
-  GibbsState s;
-  int rc = [&]() -> int {
-    HIPCK(hipMalloc((void**)&d_samples, sizeof(double) * n * S * D));
-    HIPCK(hipMemsetAsync(d_samples, 0xff, sizeof(double) * n * S * D, ctx->stream));  // NaN: the rows a stopped chain never writes
-    GibbsParams p{};
-    RC(gibbs_alloc(ctx, s, p));
-    p.seed = seed; p.chain_offset = chain_offset; p.burn_in = burn_in; p.S = (long long)S; p.samples = d_samples; p.T = n_iter;
-    RC(gibbs_run(ctx, p, n_iter, true, seconds_out));
-    HIPCK(hipMemcpyAsync(samples_out, d_samples, sizeof(double) * n * S * D, hipMemcpyDeviceToHost, ctx->stream));
-    const size_t N = ctx->M, Mp = ctx->Mp;
-    if (Z_out) HIPCK(hipMemcpy2DAsync(Z_out, N * sizeof(double), s.Z, Mp * sizeof(double), N * sizeof(double), n, hipMemcpyDeviceToHost, ctx->stream));
-    if (lam_out) HIPCK(hipMemcpy2DAsync(lam_out, N * sizeof(double), s.lam, Mp * sizeof(double), N * sizeof(double), n, hipMemcpyDeviceToHost, ctx->stream));
-    std::vector<long long> cp(n), dd(n);
-    RC(download(ctx, cp.data(), s.capped, n)); RC(download(ctx, dd.data(), s.dead, n));
-    RC(sync(ctx));
-    for (size_t c = 0; c < n; ++c) {
-      if (capped_out) capped_out[c] = cp[c];
-      if (stopped_out) stopped_out[c] = dd[c];
-    }
-    return RMHMC_OK;
-  }();
-  if (d_samples) (void)hipFree(d_samples);
-  gibbs_free(s);
-  return rc;
+  if (!samples_out) return fail(ctx, RMHMC_ERR_INVALID, "gibbs_sample: need samples_out");
+  return gibbs_sample_body(ctx, "gibbs_sample", n_iter, burn_in, seed, chain_offset, {RMHMC_OUT_HOST, samples_out}, capped_out, stopped_out,
+                           Z_out, lam_out, seconds_out);
+}
+int rmhmc_gibbs_sample_to(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, uint64_t seed, int64_t chain_offset, const rmhmc_out* out,
+                          int64_t* capped_out, int64_t* stopped_out, double* seconds_out) {
+  NEED_DATA(ctx);
+  RC(out_check(ctx, "gibbs_sample_to", out));
+  return gibbs_sample_body(ctx, "gibbs_sample_to", n_iter, burn_in, seed, chain_offset, *out, capped_out, stopped_out, nullptr, nullptr,
+                           seconds_out);
 }
 
 int rmhmc_gibbs_replay(rmhmc_ctx* ctx, int64_t n_iter, const double* u_init, const double* u_sweep, const double* T, const double* ks_draws,
@@ -2385,202 +2478,6 @@ int rmhmc_gibbs_replay(rmhmc_ctx* ctx, int64_t n_iter, const double* u_init, con
   for (void* q : {(void*)d_ui, (void*)d_us, (void*)d_T, (void*)d_ks, (void*)d_off, (void*)d_beta, (void*)d_B, (void*)d_att}) if (q) (void)hipFree(q);
   gibbs_free(s);
   return rc;
-}
-
-}  // extern "C"
-
-// ---- output descriptor: every sampler to host or device memory, raw or reduced (include/rmhmc_out.h, output.hip.h) ------------------
-namespace {
-
-hipMemcpyKind out_kind(const rmhmc_out& out) { return out.where == RMHMC_OUT_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost; }
-bool out_stats(const rmhmc_out& out) { return out.mean || out.var || out.ess || out.run_mean || out.run_ess; }
-
-// the refusals of a descriptor, before any sampling work; S: samples per chain of the call
-int out_check(rmhmc_ctx* ctx, const rmhmc_out* out, int64_t S) {
-  if (!out) return fail(ctx, RMHMC_ERR_INVALID, "sample_to: NULL output descriptor");
-  if (out->where != RMHMC_OUT_HOST && out->where != RMHMC_OUT_DEVICE)
-    return fail(ctx, RMHMC_ERR_INVALID, "sample_to: where must be RMHMC_OUT_HOST or RMHMC_OUT_DEVICE");
-  if (!out->samples && !out_stats(*out)) return fail(ctx, RMHMC_ERR_INVALID, "sample_to: the output descriptor requests no output");
-  if (out_stats(*out) && (S < 2 || S > 20000))
-    return fail(ctx, RMHMC_ERR_UNSUPPORTED, "sample_to: statistics need 2 <= n_iter - burn_in <= 20000 (the ESS kernel holds one series in LDS)");
-  return RMHMC_OK;
-}
-
-// The write-out of a call: d_samples [n][S][D] in device memory -> whatever `out` requests, copied or reduced.  Returns with the
-// stream idle and its own buffers freed.  Its wall time (the sampler has synchronised: the stream holds the counter copies at most) is
-// kept for rmhmc_kernel_time "write_out".
-int write_out(rmhmc_ctx* ctx, const double* d_samples, size_t n, size_t S, size_t D, const rmhmc_out& out) {
-  const auto t0 = std::chrono::steady_clock::now();
-  const hipMemcpyKind kind = out_kind(out);
-  const size_t nd = n * D, sd = S * D;
-  double* d_st = nullptr;  // [3][n][D]: ess, mean, var
-  double* d_rm = nullptr;  // [S][D] run mean, then [D] its ess
-  const int rc = [&]() -> int {
-    if (out.samples && out.samples != d_samples) HIPCK(hipMemcpyAsync(out.samples, d_samples, sizeof(double) * n * sd, kind, ctx->stream));
-    if (out.mean || out.var || out.ess) {
-      HIPCK(hipMalloc((void**)&d_st, sizeof(double) * 3 * nd));
-      RC(launch_ess(ctx, d_samples, (long long)n, (long long)S, (int)D, d_st, d_st + nd, d_st + 2 * nd));
-      if (out.ess) HIPCK(hipMemcpyAsync(out.ess, d_st, sizeof(double) * nd, kind, ctx->stream));
-      if (out.mean) HIPCK(hipMemcpyAsync(out.mean, d_st + nd, sizeof(double) * nd, kind, ctx->stream));
-      if (out.var) HIPCK(hipMemcpyAsync(out.var, d_st + 2 * nd, sizeof(double) * nd, kind, ctx->stream));
-    }
-    if (out.run_mean || out.run_ess) {
-      HIPCK(hipMalloc((void**)&d_rm, sizeof(double) * (sd + D)));
-      hipLaunchKernelGGL(k_run_mean, dim3((unsigned)((sd + 255) / 256)), dim3(256), 0, ctx->stream, d_samples, n, sd, d_rm);
-      if (out.run_ess) RC(launch_ess(ctx, d_rm, 1, (long long)S, (int)D, d_rm + sd, nullptr, nullptr));
-      if (out.run_mean) HIPCK(hipMemcpyAsync(out.run_mean, d_rm, sizeof(double) * sd, kind, ctx->stream));
-      if (out.run_ess) HIPCK(hipMemcpyAsync(out.run_ess, d_rm + sd, sizeof(double) * D, kind, ctx->stream));
-    }
-    return sync(ctx);
-  }();
-  ctx->write_out_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  if (d_st) (void)hipFree(d_st);
-  if (d_rm) (void)hipFree(d_rm);
-  return rc;
-}
-
-// a per-chain counter to the memory space of the descriptor (dst may be NULL)
-template <typename T>
-int counter_out(rmhmc_ctx* ctx, const rmhmc_out& out, int64_t* dst, const T* src) {
-  static_assert(sizeof(T) == sizeof(int64_t), "int64");
-  if (dst) HIPCK(hipMemcpyAsync(dst, src, sizeof(int64_t) * ctx->n, out_kind(out), ctx->stream));
-  return RMHMC_OK;
-}
-
-// One *_sample_to call after its argument checks.  core(d_samples) runs the sampler into d_samples [n][S][D] and queues its counter
-// copies; the samples go straight into the caller's buffer where that is device memory, into a buffer of the call's otherwise.
-template <typename F>
-int sample_to(rmhmc_ctx* ctx, int64_t S, const rmhmc_out& out, F&& core) {
-  const size_t n = ctx->n, D = ctx->D;
-  const bool direct = out.where == RMHMC_OUT_DEVICE && out.samples;
-  double* d_samples = direct ? out.samples : nullptr;
-  if (!direct) HIPCK(hipMalloc((void**)&d_samples, sizeof(double) * n * (size_t)S * D));
-  const int rc = [&]() -> int {
-    RC(core(d_samples));
-    return write_out(ctx, d_samples, n, (size_t)S, D, out);
-  }();
-  if (!direct) (void)hipFree(d_samples);
-  return rc;
-}
-
-}  // namespace
-
-extern "C" {
-
-int rmhmc_sample_to(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L, double eps, int32_t K, uint64_t seed, int64_t chain_offset,
-                    const double* theta0, const rmhmc_out* out, int64_t* accept_out, int64_t* steps_out, double* seconds_out) {
-  NEED_DATA(ctx);
-  if (burn_in < 0 || burn_in >= n_iter || L < 1 || K < 1)
-    return fail(ctx, RMHMC_ERR_INVALID, "sample_to: need 0 <= burn_in < n_iter, L >= 1, K >= 1");
-  RC(out_check(ctx, out, n_iter - burn_in));
-  ctx->chains_ready = false;
-  const Run run{RMHMC, L, K, eps, seed, chain_offset, nullptr};
-  return sample_to(ctx, n_iter - burn_in, *out, [&](double* d_samples) -> int {
-    Counters counters{};
-    RC(sample_core(ctx, run, n_iter, burn_in, theta0, d_samples, seconds_out, &counters));
-    return sample_counters(ctx, counters, accept_out, steps_out, out_kind(*out));
-  });
-}
-
-int rmhmc_hmc_sample_to(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L, double eps, uint64_t seed, int64_t chain_offset,
-                        const double* theta0, const rmhmc_out* out, int64_t* accept_out, int64_t* steps_out, double* seconds_out) {
-  NEED_DATA(ctx);
-  if (burn_in < 0 || burn_in >= n_iter || L < 1) return fail(ctx, RMHMC_ERR_INVALID, "hmc_sample_to: need 0 <= burn_in < n_iter, L >= 1");
-  RC(out_check(ctx, out, n_iter - burn_in));
-  ctx->chains_ready = false;
-  const Run run{HMC, L, 0, eps, seed, chain_offset, nullptr};  // (no fixed-point iterations: no K)
-  return sample_to(ctx, n_iter - burn_in, *out, [&](double* d_samples) -> int {
-    RC(hmc_sample_core(ctx, run, n_iter, burn_in, theta0, d_samples, seconds_out));
-    // d_steps0 = steps_done - d_steps0: the post-burn-in steps, the subtraction rmhmc_hmc_sample does on the host
-    hipLaunchKernelGGL(k_sub_ll, dim3((unsigned)((ctx->n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_steps0, ctx->batch.ch.steps_done, (size_t)ctx->n);
-    RC(counter_out(ctx, *out, accept_out, ctx->batch.ch.accepted));
-    return counter_out(ctx, *out, steps_out, ctx->d_steps0);
-  });
-}
-
-int rmhmc_mmala_sample_to(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, double eps, uint64_t seed, int64_t chain_offset,
-                          const double* theta0, const rmhmc_out* out, int64_t* accept_out, double* seconds_out) {
-  NEED_DATA(ctx);
-  if (burn_in < 0 || burn_in >= n_iter || !(eps > 0)) return fail(ctx, RMHMC_ERR_INVALID, "mmala_sample_to: need 0 <= burn_in < n_iter, eps > 0");
-  RC(out_check(ctx, out, n_iter - burn_in));
-  ctx->chains_ready = false;
-  const Run run{RMHMC, 0, 0, eps, seed, chain_offset, nullptr};
-  return sample_to(ctx, n_iter - burn_in, *out, [&](double* d_samples) -> int {
-    RC(mmala_sample_core(ctx, run, n_iter, burn_in, theta0, d_samples, seconds_out));
-    return counter_out(ctx, *out, accept_out, ctx->batch.ch.accepted);
-  });
-}
-
-int rmhmc_amh_sample_to(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, uint64_t seed, int64_t chain_offset, const double* theta0,
-                        const rmhmc_out* out, int64_t* accepted_out, double* sd_out, double* seconds_out) {
-  NEED_DATA(ctx);
-  if (!amh_iters_ok(n_iter, burn_in) || chain_offset < 0)
-    return fail(ctx, RMHMC_ERR_INVALID, "amh_sample_to: need 0 <= burn_in < n_iter < 2^32, chain_offset >= 0");
-  RC(out_check(ctx, out, n_iter - burn_in));
-  ctx->chains_ready = false;
-  return sample_to(ctx, n_iter - burn_in, *out, [&](double* d_samples) -> int {
-    AmhParams p{};
-    p.samples = d_samples; p.seed = seed; p.chain_offset = chain_offset; p.n_iter = n_iter; p.burn_in = burn_in;
-    RC(amh_run(ctx, p, theta0, seconds_out));
-    RC(counter_out(ctx, *out, accepted_out, ctx->batch.ch.accepted));
-    if (sd_out)  // [n][DP] -> [n][D]
-      HIPCK(hipMemcpy2DAsync(sd_out, ctx->D * sizeof(double), ctx->batch.ch.PM, ctx->DP * sizeof(double), ctx->D * sizeof(double), ctx->n,
-                             out_kind(*out), ctx->stream));
-    return RMHMC_OK;
-  });
-}
-
-int rmhmc_iwls_sample_to(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t compat, uint64_t seed, int64_t chain_offset,
-                         const double* theta0, const rmhmc_out* out, int64_t* accepted_out, int64_t* saturated_out, double* seconds_out) {
-  NEED_DATA(ctx);
-  if (!amh_iters_ok(n_iter, burn_in) || chain_offset < 0)
-    return fail(ctx, RMHMC_ERR_INVALID, "iwls_sample_to: need 0 <= burn_in < n_iter < 2^32, chain_offset >= 0");
-  RC(out_check(ctx, out, n_iter - burn_in));
-  if (ctx->D > 64) return fail(ctx, RMHMC_ERR_UNSUPPORTED, kIwlsDMsg);
-  ctx->chains_ready = false;
-  const int64_t S = n_iter - burn_in;
-  IwlsState s;
-  const int rc = sample_to(ctx, S, *out, [&](double* d_samples) -> int {
-    IwlsParams p{};
-    RC(iwls_alloc(ctx, s, p, compat));
-    p.seed = seed; p.chain_offset = chain_offset; p.burn_in = burn_in; p.S = S; p.samples = d_samples; p.T = n_iter;
-    RC(iwls_run(ctx, p, n_iter, true, theta0, seconds_out));
-    RC(counter_out(ctx, *out, accepted_out, ctx->batch.ch.accepted));
-    return counter_out(ctx, *out, saturated_out, s.nsat);
-  });
-  iwls_free(s);
-  return rc;
-}
-
-int rmhmc_gibbs_sample_to(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, uint64_t seed, int64_t chain_offset, const rmhmc_out* out,
-                          int64_t* capped_out, int64_t* stopped_out, double* seconds_out) {
-  NEED_DATA(ctx);
-  if (!amh_iters_ok(n_iter, burn_in) || chain_offset < 0 || chain_offset + ctx->n > (int64_t)1 << 32)
-    return fail(ctx, RMHMC_ERR_INVALID, "gibbs_sample_to: need 0 <= burn_in < n_iter < 2^32, 0 <= chain_offset, chain_offset + n <= 2^32");
-  RC(out_check(ctx, out, n_iter - burn_in));
-  if (ctx->D > 64) return fail(ctx, RMHMC_ERR_UNSUPPORTED, kGibbsDMsg);
-  ctx->chains_ready = false;
-  const int64_t S = n_iter - burn_in;
-  GibbsState s;
-  const int rc = sample_to(ctx, S, *out, [&](double* d_samples) -> int {
-    HIPCK(hipMemsetAsync(d_samples, 0xff, sizeof(double) * (size_t)ctx->n * (size_t)S * ctx->D, ctx->stream));  // NaN: the rows a stopped chain never writes
-    GibbsParams p{};
-    RC(gibbs_alloc(ctx, s, p));
-    p.seed = seed; p.chain_offset = chain_offset; p.burn_in = burn_in; p.S = S; p.samples = d_samples; p.T = n_iter;
-    RC(gibbs_run(ctx, p, n_iter, true, seconds_out));
-    RC(counter_out(ctx, *out, capped_out, s.capped));
-    return counter_out(ctx, *out, stopped_out, s.dead);
-  });
-  gibbs_free(s);
-  return rc;
-}
-
-int rmhmc_ess_dev(rmhmc_ctx* ctx, const double* samples_dev, int64_t n, int64_t S, int32_t P, double* ess_dev, double* mean_dev, double* var_dev) {
-  if (!ctx || !samples_dev || (!ess_dev && !mean_dev && !var_dev) || n < 1 || P < 1 || n * (int64_t)P > 0x7fffffffLL)
-    return fail(ctx, RMHMC_ERR_INVALID, "ess_dev: bad argument");
-  HIPCK(hipSetDevice(ctx->device));
-  RC(launch_ess(ctx, samples_dev, n, S, P, ess_dev, mean_dev, var_dev));
-  return sync(ctx);
 }
 
 }  // extern "C"

@@ -3,8 +3,10 @@ device, or both, against the sampler's existing *_sample call (bit for bit), the
 tools.CalculateESS (the project's tolerances: mean / var rtol 1e-12, atol 1e-14; ESS rtol 1e-9).
 
 Shapes: 200 rows, D = 5, 5 chains, 60 iterations of which 23 burn-in: S = 37 is odd, the ESS kernel's half = 18, n is a multiple of
-nothing; IWLS again at D = 33 (three column blocks) and Gibbs at D = 17; one case with RMHMC_FLAG_ESS_WRAP.  Needs an MI355X: run
-with  pytest -m gpu."""
+nothing; IWLS again at D = 33 (three column blocks) and Gibbs at D = 17; one case with RMHMC_FLAG_ESS_WRAP.  The older entry points
+are the same bodies behind a descriptor of their own: what only they allow (rmhmc_sample_stats without a statistic), what they
+refuse themselves (no samples_out) and the statistics limit, refused before any sampling work, at n = 3 and n = 5.  Needs an
+MI355X: run with  pytest -m gpu."""
 import ctypes as C
 import os
 import sys
@@ -234,6 +236,63 @@ def test_refusals(hip, sampler):
         # samples alone have no such limit - and the refusals have left the context usable
         got = ctx.sample_to(sampler, N_ITER, BURN, samples=True, seed=SEED)
         assert np.array_equal(got["samples"], runs(hip, sampler)["existing"]["samples"])
+
+
+# ---- the older entry points: thin wrappers of the same bodies (each builds its own descriptor) ----
+_RMHMC_RUN = (6, 0.5, 4, SEED, 0, None)   # L, eps, K, seed, chain_offset, theta0
+_secs = lambda s: C.cast(C.byref(s), _capi._dp)  # noqa: E731
+
+
+def test_sample_stats_without_a_statistic(hip):
+    """mean_out, var_out and ess_out all NULL: a descriptor that asks for nothing, which only rmhmc_sample_stats may pass - the sampler
+    runs, the counters and the time come back.  Then with the statistics: the write-out of the older call is the timed write_out."""
+    n = 3
+    with _context(hip, 5, _capi.COMPAT, n=n) as ctx:
+        acc = np.full(n, -5, dtype=np.int64); steps = np.full(n, -5, dtype=np.int64); secs = C.c_double(-7.0)
+        rc = hip.lib.rmhmc_sample_stats(ctx._h, N_ITER, BURN, *_RMHMC_RUN, None, None, None, _capi._ptr(acc, _capi._lp),
+                                        _capi._ptr(steps, _capi._lp), _secs(secs))
+        assert rc == 0 and secs.value > 0
+        _, want_acc, want_steps, _ = ctx.sample(N_ITER, BURN, seed=SEED)
+        assert np.array_equal(acc, want_acc) and np.array_equal(steps, want_steps) and (steps > 0).all()
+        st = ctx.sample_stats(N_ITER, BURN, seed=SEED)
+        assert np.array_equal(st["accepted"], want_acc) and np.isfinite(st["ess"]).all()
+        assert ctx.kernel_time("write_out")[0] > 0
+
+
+@pytest.mark.parametrize("S_bad", [1, 20001])
+def test_sample_stats_limit_is_refused_before_sampling(hip, S_bad):
+    """n_iter - burn_in outside 2..20000: RMHMC_ERR_UNSUPPORTED from rmhmc_sample_stats and rmhmc_sample_stats_dev before any sampling
+    work - nothing written, the timer untouched, the context as a fresh one's."""
+    nd = (N_CH, 5)
+    with _context(hip, 5, _capi.COMPAT) as ctx:
+        host = [np.full(nd, -3.0) for _ in range(3)] + [np.full(N_CH, -5, dtype=np.int64) for _ in range(2)]
+        dev = [torch.full(nd, -3.0, dtype=torch.float64, device="cuda:0") for _ in range(3)] + \
+              [torch.full((N_CH,), -5, dtype=torch.int64, device="cuda:0") for _ in range(2)]
+        torch.cuda.synchronize()
+        secs = C.c_double(-7.0)
+        front = (ctx._h, S_bad + BURN, BURN) + _RMHMC_RUN
+        rc = hip.lib.rmhmc_sample_stats(*front, *[_capi._ptr(a) for a in host[:3]], *[_capi._ptr(a, _capi._lp) for a in host[3:]], _secs(secs))
+        assert rc == -4 and hip.lib.rmhmc_last_error(ctx._h).decode().startswith("sample_stats:")
+        rc = hip.lib.rmhmc_sample_stats_dev(*front, *[t.data_ptr() for t in dev], _secs(secs))
+        assert rc == -4 and hip.lib.rmhmc_last_error(ctx._h).decode().startswith("sample_stats_dev:")
+        rc = hip.lib.rmhmc_sample_stats(*front, None, None, None, None, None, _secs(secs))      # nothing requested: the same code
+        assert rc == -4
+        assert secs.value == -7.0
+        for a in host + [t.cpu().numpy() for t in dev]:
+            assert (a == (-3.0 if a.dtype == np.float64 else -5)).all()
+        for a, b in zip(_history_probe(ctx), fresh_probe(hip, 5, _capi.COMPAT)):
+            assert np.array_equal(a, b)
+
+
+@pytest.mark.parametrize("sampler", list(_capi.SAMPLERS_TO))
+def test_older_calls_need_samples_out(hip, sampler):
+    """samples_out NULL: RMHMC_ERR_INVALID, and the message names the entry point that was called"""
+    name = _capi.SAMPLERS_TO[sampler][0][:-len("_to")]
+    fn = getattr(hip.lib, name)
+    with _context(hip, 5, 0, n=3) as ctx:
+        rest = len(fn.argtypes) - 3 - len(_FRONT[sampler])            # samples_out, the counters, seconds_out
+        assert fn(ctx._h, N_ITER, BURN, *_FRONT[sampler], *([None] * rest)) == -1
+        assert hip.lib.rmhmc_last_error(ctx._h).decode().startswith(name[len("rmhmc_"):] + ":")
 
 
 @pytest.mark.parametrize("sampler", ["iwls", "gibbs"])
