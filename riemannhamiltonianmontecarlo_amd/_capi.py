@@ -173,6 +173,18 @@ DIAG_SIGNATURES = {
 DIAG_KEYS = ("rhat", "ess_pooled", "pairs", "chains_used")   # what diag_finish returns, [P] each
 DIAG_S_MIN, DIAG_S_MAX = 4, 20000
 
+# include/rmhmc_phmc.h: HMC with a fixed dense mass matrix shared by all chains and the Newton search for the posterior mode, HIP
+# library only as well.  Not a key of SAMPLERS_TO: the sampler needs its mass matrix first (Context.phmc_set_mass), so it has methods
+# of its own (Context.phmc_sample_to) instead of a place in the tables every sampler is run from.
+PHMC_SIGNATURES = {
+    "rmhmc_phmc_set_mass": (C.c_int, [C.c_void_p, _dp]),
+    "rmhmc_phmc_mode": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.c_double, _dp, _dp, _ip, _dp]),
+    "rmhmc_phmc_transition": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp, C.c_int32, C.c_double, _ip, _ip, _dp, _dp, _dp, _dp, _ip]),
+    "rmhmc_phmc_sample_to": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_uint64, C.c_int64, _dp, _op, _vp, _vp,
+                                       _dp]),
+}
+PHMC_COUNTERS = (("accepted", False), ("leapfrog_steps", False))
+
 
 def diag_lags(S, max_lag=None):
     """(H, T) of a diagnostics call on S samples per chain: H = S // 2 rows per half chain, T = max_lag + 1 lags; max_lag None or 0:
@@ -250,6 +262,12 @@ class RmhmcLib:
         self.has_diag = all(hasattr(self.lib, name) for name in DIAG_SIGNATURES)
         if self.has_diag:
             for name, (res, args) in DIAG_SIGNATURES.items():
+                fn = getattr(self.lib, name)
+                fn.restype = res
+                fn.argtypes = args
+        self.has_phmc = all(hasattr(self.lib, name) for name in PHMC_SIGNATURES)
+        if self.has_phmc:
+            for name, (res, args) in PHMC_SIGNATURES.items():
                 fn = getattr(self.lib, name)
                 fn.restype = res
                 fn.argtypes = args
@@ -495,6 +513,50 @@ class Context:
                                            C.cast(C.byref(secs), _dp)))
         return samples, acc, steps, secs.value
 
+    # ---- HMC with a fixed dense mass matrix shared by all chains (include/rmhmc_phmc.h) -----------
+    def _need_phmc(self):
+        if not self.rl.has_phmc:
+            raise RmhmcError(-4, "%s does not export the fixed-metric HMC sampler (include/rmhmc_phmc.h)" % self.rl.path)
+
+    def phmc_set_mass(self, mass=None):
+        """the context's mass matrix: (D, D) symmetric positive definite (the lower triangle is read), None: the identity"""
+        self._need_phmc()
+        m = None if mass is None else _f64(mass, (self.D, self.D))
+        self._ck(self.lib.rmhmc_phmc_set_mass(self._h, _ptr(m)))
+
+    def phmc_mode(self, w0=None, max_iter=50, tol=1e-10):
+        """posterior mode by damped Newton from w0 (None: zeros): dict(w [D], G [D][D] the metric at w, iters, step: max|s| of the
+        last Newton step, converged: step <= tol * max(1, max|w|))"""
+        self._need_phmc()
+        D = self.D
+        w0 = None if w0 is None else _f64(w0, (D,))
+        w = np.empty(D); G = np.empty((D, D))
+        iters = C.c_int32(0); step = C.c_double(0.0)
+        self._ck(self.lib.rmhmc_phmc_mode(self._h, _ptr(w0), int(max_iter), float(tol), _ptr(w), _ptr(G), C.cast(C.byref(iters), _ip),
+                                          C.cast(C.byref(step), _dp)))
+        return dict(w=w, G=G, iters=iters.value, step=step.value,
+                    converged=bool(step.value <= float(tol) * max(1.0, float(np.abs(w).max()))))
+
+    def phmc_transition(self, w, z, u_len, u_acc, L=6, eps=0.5):
+        self._need_phmc()
+        n, D = self.n, self.D
+        w = _f64(w, (n, D)).copy()
+        z = _f64(z, (n, D)); u_len = _f64(u_len, (n,)); u_acc = _f64(u_acc, (n,))
+        acc = np.zeros(n, dtype=np.int32); ns = np.zeros(n, dtype=np.int32); status = np.zeros(n, dtype=np.int32)
+        Hc = np.empty(n); Hp = np.empty(n); wp = np.empty((n, D)); pp = np.empty((n, D))
+        self._ck(self.lib.rmhmc_phmc_transition(self._h, _ptr(w), _ptr(z), _ptr(u_len), _ptr(u_acc), int(L), float(eps),
+                                                _ptr(acc, _ip), _ptr(ns, _ip), _ptr(Hc), _ptr(Hp), _ptr(wp), _ptr(pp), _ptr(status, _ip)))
+        return dict(w=w, accepted=acc, nsteps=ns, H_cur=Hc, H_prop=Hp, w_prop=wp, p_prop=pp, status=status)
+
+    def phmc_sample_to(self, n_iter, burn_in, L=6, eps=0.5, *, where="host", device=None, samples=False, stats=False, run_mean=False,
+                       seed=0, chain_offset=0, theta0=None):
+        """One run of the sampler with the context's mass matrix, written out as sample_to writes the others: the requested outputs,
+        the counters accepted and leapfrog_steps (same memory space) and seconds."""
+        self._need_phmc()
+        self._need_out()
+        return self._call_sample_to("rmhmc_phmc_sample_to", PHMC_COUNTERS, (int(L), float(eps)), n_iter, burn_in, where, device, samples,
+                                    stats, run_mean, seed, chain_offset, theta0)
+
     # ---- adaptive Metropolis (code/metropolis.py, include/rmhmc_amh.h) -----------
     def _need_amh(self):
         if not self.rl.has_amh:
@@ -627,6 +689,23 @@ class Context:
         extra = sorted(k for k, v in given.items() if v is not None and k not in SAMPLER_ARGS[sampler])
         if extra:
             raise ValueError("sampler %r has no run argument %s" % (sampler, ", ".join(extra)))
+        if sampler == "rmhmc":
+            front = (int(6 if L is None else L), float(0.5 if eps is None else eps), int(4 if K is None else K))
+        elif sampler == "hmc":
+            front = (int(100 if L is None else L), float(0.14 if eps is None else eps))
+        elif sampler == "mmala":
+            front = (float(1.0 if eps is None else eps),)
+        elif sampler == "iwls":
+            front = (1 if compat or compat is None else 0,)
+        else:
+            front = ()
+        return self._call_sample_to(name, counters, front, n_iter, burn_in, where, device, samples, stats, run_mean, seed, chain_offset,
+                                    theta0, has_theta0=sampler != "gibbs")
+
+    def _call_sample_to(self, name, counters, front, n_iter, burn_in, where, device, samples, stats, run_mean, seed, chain_offset, theta0,
+                        has_theta0=True):
+        """the descriptor, the buffers and the call of one <sampler>_sample_to entry point: `front` its run arguments between burn_in
+        and seed, `counters` as in SAMPLERS_TO"""
         n, D = self.n, self.D
         n_iter, burn_in = int(n_iter), int(burn_in)
         S = n_iter - burn_in
@@ -661,17 +740,7 @@ class Context:
             res[key], ptr = buf((n, D) if vec else (n,), np.float64 if vec else np.int64)
             cptr.append(ptr)
         th = None if theta0 is None else _f64(np.broadcast_to(theta0, (n, D)))
-        tail = (int(seed), int(chain_offset)) + (() if sampler == "gibbs" else (_ptr(th),))
-        if sampler == "rmhmc":
-            front = (int(6 if L is None else L), float(0.5 if eps is None else eps), int(4 if K is None else K))
-        elif sampler == "hmc":
-            front = (int(100 if L is None else L), float(0.14 if eps is None else eps))
-        elif sampler == "mmala":
-            front = (float(1.0 if eps is None else eps),)
-        elif sampler == "iwls":
-            front = (1 if compat or compat is None else 0,)
-        else:
-            front = ()
+        tail = (int(seed), int(chain_offset)) + ((_ptr(th),) if has_theta0 else ())
         secs = C.c_double(0.0)
         if dev and device.type == "cuda":
             torch.cuda.current_stream(device).synchronize()   # nothing of torch's is pending on the buffers the library is handed

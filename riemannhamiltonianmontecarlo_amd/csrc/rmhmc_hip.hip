@@ -11,7 +11,9 @@
 #include "../../include/rmhmc_gibbs.h"
 #include "../../include/rmhmc_out.h"
 #include "../../include/rmhmc_diag.h"
+#include "../../include/rmhmc_phmc.h"
 #include "plan.h"
+#include "mass.h"
 #include "kernels.hip.h"
 #include "fused_small.hip.h"
 #include "large_d.hip.h"
@@ -22,6 +24,7 @@
 #include "gibbs.hip.h"
 #include "output.hip.h"
 #include "diag.hip.h"
+#include "phmc.hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -67,7 +70,7 @@ struct Group {
 // What one call asks of the stepping code.  The entry point builds it from its own arguments and hands it down by const&; nothing
 // below writes it, and the context keeps none of it (rmhmc_ctx::chains is the one exception).  A parameter the call's sampler
 // never reads is 0 (K of plain HMC, L of rmhmc_leapfrog, seed and chain_offset where the randomness is the caller's).
-enum Sampler { RMHMC, HMC };  // rmhmc.py / hmc.py: selects the global step
+enum Sampler { RMHMC, HMC, PHMC };  // rmhmc.py / hmc.py / HMC with the context's mass matrix (phmc.hip.h): selects the global step
 struct Run {
   Sampler sampler;
   int L, K;
@@ -118,6 +121,9 @@ struct rmhmc_ctx : Plan {
   double* d_zscale = nullptr;
   I8Pairs pairs{};
   double i8_bound = 0.0;       // certificate of the last set_data (metric_i8.hip.h: "Error bound"), 0 when the path is not requested
+  // fixed-metric HMC (phmc.hip.h): the images of rmhmc_phmc_set_mass, [DP][DP] each, allocated by its first call
+  double *d_massL = nullptr, *d_massInv = nullptr;
+  bool have_mass = false;
   // unit-API staging (device)
   double *d_z = nullptr, *d_ulen = nullptr, *d_gdir = nullptr, *d_uacc = nullptr;
   int *d_nsteps = nullptr, *d_dir = nullptr, *d_done = nullptr;
@@ -741,9 +747,35 @@ void launch_hmc_global_step(rmhmc_ctx* ctx, const Run& run, Group& g, const Iter
   SMALL(ctx, g, "small", k_hmc_end, ctx->D, ctx->DP, g.ch, ip);
 }
 
+// HMC with the context's mass matrix (phmc.hip.h): head / gradient pass / tail, the generic launches on every context
+#define PHMC_SWITCH(ctx, ...)                                     \
+  switch ((ctx)->DP / 16) {                                       \
+    case 1: { constexpr int NDB_ = 1; __VA_ARGS__; } break;       \
+    case 2: { constexpr int NDB_ = 2; __VA_ARGS__; } break;       \
+    case 3: { constexpr int NDB_ = 3; __VA_ARGS__; } break;       \
+    case 4: { constexpr int NDB_ = 4; __VA_ARGS__; } break;       \
+    case 8: { constexpr int NDB_ = 8; __VA_ARGS__; } break;       \
+    case 12: { constexpr int NDB_ = 12; __VA_ARGS__; } break;     \
+    default: { constexpr int NDB_ = 16; __VA_ARGS__; } break;     \
+  }
+void launch_phmc_global_step(rmhmc_ctx* ctx, const Run& run, Group& g, const IterBase& b) {
+  const double eps = run.eps;
+  const IterParams ip = iter_params(ctx, run, b);
+  const PhmcMass pm{ctx->d_massL, ctx->d_massInv};
+  const dim3 grid((unsigned)((g.n + 15) / 16)), block(256);
+  launch(ctx, "phmc", [&](hipStream_t st) {
+    PHMC_SWITCH(ctx, hipLaunchKernelGGL((k_phmc_head<NDB_>), grid, block, phmc_lds_bytes<NDB_>(), st, ctx->D, g.ch, ip, pm, eps));
+  });
+  launch_rowpass<RP_G>(ctx, g, g.ch.trj.w, nullptr);
+  launch(ctx, "phmc", [&](hipStream_t st) {
+    PHMC_SWITCH(ctx, hipLaunchKernelGGL((k_phmc_tail<NDB_>), grid, block, phmc_lds_bytes<NDB_>(), st, ctx->dd, g.ch, ip, pm, eps, ctx->nsplit));
+  });
+}
+
 // One global step of the batch g: transition start, one leapfrog step and transition end of every chain
 void launch_global_step(rmhmc_ctx* ctx, const Run& run, Group& g, const IterBase& b) {
   if (run.sampler == HMC) { launch_hmc_global_step(ctx, run, g, b); return; }
+  if (run.sampler == PHMC) { launch_phmc_global_step(ctx, run, g, b); return; }
   if (ctx->medium) {  // ... in ONE launch
     const int guards = (ctx->flags & RMHMC_FLAG_GUARDS) ? 1 : 0;
     const IterParams ip = iter_params(ctx, run, b);
@@ -1820,6 +1852,181 @@ int rmhmc_hmc_sample_to(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t
   NEED_DATA(ctx);
   RC(out_check(ctx, "hmc_sample_to", out));
   return hmc_sample_body(ctx, "hmc_sample_to", n_iter, burn_in, L, eps, seed, chain_offset, theta0, *out, accept_out, steps_out, seconds_out);
+}
+
+// ---- HMC with a fixed dense mass matrix shared by all chains (include/rmhmc_phmc.h, phmc.hip.h, mass.h) ----------------
+int rmhmc_phmc_set_mass(rmhmc_ctx* ctx, const double* mass) {
+  if (!ctx) return fail(nullptr, RMHMC_ERR_INVALID, "null context");
+  HIPCK(hipSetDevice(ctx->device));
+  std::vector<double> Lm, Mi;
+  const char* why = "";
+  if (mass_images(mass, ctx->D, ctx->DP, Lm, Mi, &why) != RMHMC_OK) return fail(ctx, RMHMC_ERR_INVALID, std::string("phmc_set_mass: ") + why);
+  const size_t nn = (size_t)ctx->DP * ctx->DP;
+  if (!ctx->d_massInv) {  // first use: the LDS limit of this shape's kernels (more than 64 KB for DP > 128), and the images
+    // (what the instantiation needs, the same for every context that uses it - not MAX_LDS: the kernels have static LDS besides)
+    int rc = RMHMC_OK;
+    PHMC_SWITCH(ctx, rc = raise_lds(ctx, k_phmc_head<NDB_>, (int)phmc_lds_bytes<NDB_>());
+                if (rc == RMHMC_OK) rc = raise_lds(ctx, k_phmc_tail<NDB_>, (int)phmc_lds_bytes<NDB_>()));
+    RC(rc);
+    if (!ctx->d_massL) RC(dalloc(ctx, &ctx->d_massL, nn));
+    RC(dalloc(ctx, &ctx->d_massInv, nn));
+  }
+  RC(upload(ctx, ctx->d_massL, Lm.data(), nn));
+  RC(upload(ctx, ctx->d_massInv, Mi.data(), nn));
+  RC(sync(ctx));  // (the staging vectors go out of scope)
+  ctx->have_mass = true;
+  return RMHMC_OK;
+}
+
+// gradient and log joint at theta0 committed as the current point of every chain, by the generic launches whatever the context
+static int phmc_init_chains(rmhmc_ctx* ctx, const double* theta0_host /* [n][D] or NULL: zeros */) {
+  std::vector<double> th;
+  if (!theta0_host) { th.assign((size_t)ctx->n * ctx->D, 0.0); theta0_host = th.data(); }
+  Group& g = ctx->batch;
+  RC(upload_vec(ctx, g.ch.trj.w, theta0_host));
+  fill_int(ctx, g.ch.phase, 1, ctx->n);
+  launch_rowpass<RP_G>(ctx, g, g.ch.trj.w, nullptr);
+  SMALL(ctx, g, "small", k_hmc_init, ctx->dd, g.ch, ctx->nsplit);
+  return reset_chains(ctx);
+}
+
+int rmhmc_phmc_mode(rmhmc_ctx* ctx, const double* w0, int32_t max_iter, double tol, double* w_out, double* G_out, int32_t* iters_out,
+                    double* step_out) {
+  NEED_DATA(ctx);
+  if (!w_out || max_iter < 0 || !(tol >= 0.0)) return fail(ctx, RMHMC_ERR_INVALID, "phmc_mode: need w_out, max_iter >= 0, tol >= 0");
+  ctx->chains_ready = false;
+  Group& g = ctx->batch;
+  const size_t n = ctx->n, D = ctx->D, DP = ctx->DP;
+  if (ctx->big && !ctx->d_Gcopy) RC(dalloc(ctx, &ctx->d_Gcopy, n * DP * DP));
+  std::vector<double> w(D, 0.0), s(D), W(n * D), ljl(n), G(G_out ? D * D : 0);
+  if (w0) w.assign(w0, w0 + D);
+  // The batch evaluates one point per chain: the Newton system at w on every chain (chain 0 is read), then the log joint of w and of
+  // the candidates w + s / 2^k, k = 0..20, as many at a time as there are chains.
+  constexpr int NPTS = 22;
+  auto point = [&](int idx, size_t d) { return idx == 0 ? w[d] : w[d] + std::ldexp(s[d], -(idx - 1)); };
+  int32_t it = 0;
+  double step = 0.0;
+  for (;; ++it) {
+    for (size_t c = 0; c < n; ++c) std::copy(w.begin(), w.end(), W.begin() + c * D);
+    RC(upload_vec(ctx, g.ch.trj.w, W.data()));
+    HIPCK(hipMemsetAsync(g.ch.p, 0, sizeof(double) * n * DP, ctx->stream));
+    fill_int(ctx, g.ch.phase, 1, n);
+    fill_int(ctx, g.ch.status, 0, n);
+    eval_point_phases(ctx, g, nullptr, 1, ctx->big);                               // G, its factor, G^-1, gradient, log joint
+    SMALL(ctx, g, "small", k_ginv_matvec, ctx->D, ctx->DP, g.ch, g.ch.trj.grad);  // s = G^-1 grad -> uq
+    RC(download(ctx, s.data(), g.ch.uq, D));
+    if (G_out)
+      HIPCK(hipMemcpy2DAsync(G.data(), D * 8, ctx->big ? ctx->d_Gcopy : g.ch.Gq, DP * 8, D * 8, D, hipMemcpyDeviceToHost, ctx->stream));
+    RC(sync(ctx));
+    double wmax = 0.0;
+    step = 0.0;
+    for (size_t d = 0; d < D; ++d) { step = std::fmax(step, std::fabs(s[d])); wmax = std::fmax(wmax, std::fabs(w[d])); if (s[d] != s[d]) step = s[d]; }
+    if (!std::isfinite(step) || step <= tol * std::fmax(1.0, wmax) || it >= max_iter) break;
+    bool taken = false;
+    double base = 0.0;
+    for (int first = 0; first < NPTS && !taken; first += (int)n) {
+      for (size_t c = 0; c < n; ++c)
+        for (size_t d = 0; d < D; ++d) W[c * D + d] = point(std::min(first + (int)c, NPTS - 1), d);
+      RC(upload_vec(ctx, g.ch.trj.w, W.data()));
+      fill_int(ctx, g.ch.phase, 1, n);
+      launch_rowpass<RP_G>(ctx, g, g.ch.trj.w, nullptr);
+      SMALL(ctx, g, "small", k_hmc_init, ctx->dd, g.ch, ctx->nsplit);
+      RC(download(ctx, ljl.data(), g.ch.trj.ljl, n));
+      RC(sync(ctx));
+      for (int c = 0; c < (int)n && first + c < NPTS && !taken; ++c) {
+        const int idx = first + c;
+        if (idx == 0) { base = ljl[0]; continue; }
+        if (std::isfinite(ljl[c]) && ljl[c] >= base) {
+          for (size_t d = 0; d < D; ++d) w[d] = W[(size_t)c * D + d];
+          taken = true;
+        }
+      }
+    }
+    if (!taken) break;
+  }
+  std::copy(w.begin(), w.end(), w_out);
+  if (G_out) {
+    std::copy(G.begin(), G.end(), G_out);
+    if (ctx->i8)  // the int8 assembly writes the lower triangle only
+      for (size_t a = 0; a < D; ++a)
+        for (size_t b = a + 1; b < D; ++b) G_out[a * D + b] = G_out[b * D + a];
+  }
+  if (iters_out) *iters_out = it;
+  if (step_out) *step_out = step;
+  return RMHMC_OK;
+}
+
+int rmhmc_phmc_transition(rmhmc_ctx* ctx, double* w, const double* z, const double* u_len, const double* u_acc, int32_t L, double eps,
+                          int32_t* accepted_out, int32_t* nsteps_out, double* H_cur_out, double* H_prop_out, double* w_prop_out,
+                          double* p_prop_out, int32_t* status_out) {
+  NEED_DATA(ctx);
+  if (!w || !z || !u_len || !u_acc || L < 1) return fail(ctx, RMHMC_ERR_INVALID, "phmc_transition: null pointer or L < 1");
+  if (!ctx->have_mass) return fail(ctx, RMHMC_ERR_INVALID, "phmc_transition: rmhmc_phmc_set_mass has not been called");
+  ctx->chains_ready = false;
+  const Run run{PHMC, L, 0, eps, 0, 0, nullptr};  // (the randomness is the caller's: no seed)
+  RC(phmc_init_chains(ctx, w));
+  RC(upload(ctx, ctx->d_z, z, (size_t)ctx->n * ctx->D));
+  RC(upload(ctx, ctx->d_ulen, u_len, ctx->n));
+  RC(upload(ctx, ctx->d_uacc, u_acc, ctx->n));
+  const IterBase ib{1, 0, 0, nullptr, true, false};
+  for (int s = 0; s < L; ++s) launch_phmc_global_step(ctx, run, ctx->batch, ib);
+  std::vector<long long> acc(ctx->n);
+  RC(download_vec(ctx, w, ctx->batch.ch.cur.w));
+  RC(download(ctx, acc.data(), ctx->batch.ch.accepted, ctx->n));
+  if (nsteps_out) RC(download(ctx, nsteps_out, ctx->batch.ch.nsteps_last, ctx->n));
+  if (H_cur_out) RC(download(ctx, H_cur_out, ctx->batch.ch.Hcur, ctx->n));
+  if (H_prop_out) RC(download(ctx, H_prop_out, ctx->batch.ch.Hprop, ctx->n));
+  if (w_prop_out) RC(download_vec(ctx, w_prop_out, ctx->batch.ch.trj.w));
+  if (p_prop_out) RC(download_vec(ctx, p_prop_out, ctx->batch.ch.p));
+  if (status_out) RC(download(ctx, status_out, ctx->batch.ch.status, ctx->n));
+  RC(sync(ctx));
+  if (accepted_out) for (int64_t c = 0; c < ctx->n; ++c) accepted_out[c] = (int32_t)acc[c];
+  return RMHMC_OK;
+}
+
+// Runs the sampler; the saved states go to the device buffer d_samples ([n][S][D]).  As hmc_sample_core it leaves the accepted
+// proposals in batch.ch.accepted and the post-burn-in leapfrog steps in d_steps0; there are no progress reports inside TimeTaken.
+static int phmc_sample_core(rmhmc_ctx* ctx, const Run& run, int64_t n_iter, int64_t burn_in, const double* theta0, double* d_samples, double* seconds_out) {
+  const long long S = n_iter - burn_in;
+  long long progress_next = ctx->progress_first;
+  RC(phmc_init_chains(ctx, theta0));
+  const IterBase ipA{burn_in + 1, burn_in, S, d_samples, false, true};
+  RC(run_phase(ctx, run, ipA, 0, &progress_next, false, true));
+  HIPCK(hipMemcpyAsync(ctx->d_steps0, ctx->batch.ch.steps_done, sizeof(long long) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
+  HIPCK(hipMemsetAsync(ctx->d_done, 0, sizeof(int), ctx->stream));
+  RC(sync(ctx));
+  if (ctx->progress_fn) RC(report_progress(ctx, RMHMC_EV_BURNIN_DONE, burn_in + 1));
+  const auto t0 = std::chrono::steady_clock::now();
+  if (n_iter > burn_in + 1) {
+    const IterBase ipB{n_iter, burn_in, S, d_samples, false, true};
+    RC(run_phase(ctx, run, ipB, burn_in + 1, nullptr));
+  }
+  RC(sync(ctx));
+  if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  hipLaunchKernelGGL(k_sub_ll, dim3((unsigned)((ctx->n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_steps0, ctx->batch.ch.steps_done, (size_t)ctx->n);
+  return RMHMC_OK;
+}
+
+static int phmc_sample_body(rmhmc_ctx* ctx, const char* who, int64_t n_iter, int64_t burn_in, int32_t L, double eps, uint64_t seed,
+                            int64_t chain_offset, const double* theta0, const rmhmc_out& out, int64_t* accept_out, int64_t* steps_out,
+                            double* seconds_out) {
+  if (burn_in < 0 || burn_in >= n_iter || L < 1) return fail(ctx, RMHMC_ERR_INVALID, std::string(who) + ": need 0 <= burn_in < n_iter, L >= 1");
+  if (!ctx->have_mass) return fail(ctx, RMHMC_ERR_INVALID, std::string(who) + ": rmhmc_phmc_set_mass has not been called");
+  RC(stats_limit(ctx, who, out, n_iter - burn_in));
+  ctx->chains_ready = false;
+  const Run run{PHMC, L, 0, eps, seed, chain_offset, nullptr};  // (no fixed-point iterations: no K)
+  return sample_to(ctx, n_iter - burn_in, out, [&](double* d_samples) -> int {
+    RC(phmc_sample_core(ctx, run, n_iter, burn_in, theta0, d_samples, seconds_out));
+    RC(counter_out(ctx, out, accept_out, ctx->batch.ch.accepted));
+    return counter_out(ctx, out, steps_out, ctx->d_steps0);
+  });
+}
+
+int rmhmc_phmc_sample_to(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L, double eps, uint64_t seed, int64_t chain_offset,
+                         const double* theta0, const rmhmc_out* out, int64_t* accept_out, int64_t* steps_out, double* seconds_out) {
+  NEED_DATA(ctx);
+  RC(out_check(ctx, "phmc_sample_to", out));
+  return phmc_sample_body(ctx, "phmc_sample_to", n_iter, burn_in, L, eps, seed, chain_offset, theta0, *out, accept_out, steps_out, seconds_out);
 }
 
 // ---- simplified manifold MALA (BLR_mMALA_Simp.m) -------------------------------------------------------------
