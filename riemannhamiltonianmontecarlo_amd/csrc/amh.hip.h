@@ -30,6 +30,7 @@
 // Injected mode (AmhParams::z_in != nullptr) reads z and u from tapes [n][n_iter][D] instead and records, per proposal, the decision
 // (bit 0) and whether u was read (bit 1), w and CurrentLJL after every iteration.
 #pragma once
+#include "kernels.hip.h"
 #include "plan.h"  // AMH_MAX_ONCHIP_ROWS
 
 #define AMH_VALU_PER_ROW 60   // ESTIMATE (not counted from the ISA) of the fp64 VALU instructions per data row and proposal: ocml exp ~24,
@@ -148,9 +149,7 @@ __global__ __launch_bounds__(NT) void k_amh(DevData dd, AmhParams p) {
         double U0, U1, V0, V1;
         rng_block(p.seed, gid, (uint32_t)it, AMH_BLOCK_Z + (uint32_t)(j >> 1), U0, U1);
         rng_block(p.seed, gid, (uint32_t)it, AMH_BLOCK_U + (uint32_t)(j >> 1), V0, V1);
-        double sn, cs;
-        sincos(RM_PI2 * U1, &sn, &cs);
-        z = sqrt(-2.0 * log(U0)) * ((j & 1) ? sn : cs);
+        z = normal_of_pair(U0, U1, j & 1);
         u = (j & 1) ? V1 : V0;
       }
       del_s[j] = z * sdv[k];

@@ -419,14 +419,9 @@ __global__ __launch_bounds__(64 * FS_WAVES) void k_fused_small(DevData dd, Chain
         const unsigned long long gid = (unsigned long long)(ip.chain_offset + c);
         double U0, U1;
         rng_block(ip.seed, gid, (uint32_t)iter, (uint32_t)(lane >> 1), U0, U1);
-        const double R = sqrt(-2.0 * log(U0));
-        double sn, cs;
-        sincos(RM_PI2 * U1, &sn, &cs);
-        zl = (lane < D) ? ((lane & 1) ? R * sn : R * cs) : 0.0;
-        double Ua;
-        rng_block(ip.seed, gid, (uint32_t)iter, 0x40000000u, u_len, Ua);
-        rng_block(ip.seed, gid, (uint32_t)iter, 0x40000001u, U0, U1);
-        g_dir = sqrt(-2.0 * log(U0)) * cos(RM_PI2 * U1);
+        zl = (lane < D) ? normal_of_pair(U0, U1, lane & 1) : 0.0;
+        u_len = rng_u_len(ip.seed, gid, (uint32_t)iter);
+        g_dir = rng_g_dir(ip.seed, gid, (uint32_t)iter);
       }
       double z[FS_D];
 #pragma unroll
@@ -535,14 +530,7 @@ __global__ __launch_bounds__(64 * FS_WAVES) void k_fused_small(DevData dd, Chain
       fs_symv(trj.Gi, p, y);
       Hprop = -trj.ljl + trj.hld + 0.5 * fs_dot(p, y);
       const double ratio = -Hprop + Hcur;
-      double u_acc;
-      if (ip.z_in) {
-        u_acc = ip.uacc_in[c];
-      } else {
-        double U0;
-        rng_block(ip.seed, (unsigned long long)(ip.chain_offset + c), (uint32_t)iter, 0x40000000u, U0, u_acc);
-      }
-      const bool accept = (ratio > 0.0) || (ratio > log(u_acc));
+      const bool accept = mh_accept(ratio, draw_u_acc(ip, c, c, iter));
       if (accept) { fs_point_to_lds(curL, lane, trj); accepted += 1; }
       if (ip.samples && iter >= ip.burn_in && iter - ip.burn_in < ip.S && lane == 0) {
 #pragma unroll

@@ -1,5 +1,5 @@
-// gibbs.hip.h — the reference's auxiliary-variable Gibbs sampler (Holmes and Held; code/gibbs_sampler.py:14-139) on gfx950, included by
-// rmhmc_hip.hip after kernels.hip.h.  D <= 64, fp64 throughout (the int8 metric flags of the context do not apply: the row weights
+// gibbs.hip.h — the reference's auxiliary-variable Gibbs sampler (Holmes and Held; code/gibbs_sampler.py:14-139) on gfx950, on the
+// helpers of kernels.hip.h.  D <= 64, fp64 throughout (the int8 metric flags of the context do not apply: the row weights
 // 1/lam are not the p(1-p) the slicing was certified for, so the weighted Gram matrix always goes through k_assemble on the fp64 matrix
 // cores, one row range per chain whatever the batch, so that a chain's sums do not depend on the batch it runs in).
 //
@@ -38,6 +38,7 @@
 //   block 0x63000000 + 2a, iteration i, row j   Box-Muller (cos) -> the normal of attempt a; block + 1: U0, U1 -> its two uniforms
 // Nothing depends on how a run is cut into launches.  The replay entry point reads all of these from tapes instead.
 #pragma once
+#include "kernels.hip.h"
 
 #define GIBBS_MAX_ATTEMPTS 64
 #define GIBBS_MAX_TERMS 64       // pairs of series terms
@@ -333,11 +334,9 @@ __global__ __launch_bounds__(64) void k_gibbs_beta(int D, int DP, GibbsParams p)
     if (p.T_in) {
       Tn = p.T_in[((size_t)c * p.T + p.it) * D + lane];
     } else {
-      double U0, U1, sn, cs;
+      double U0, U1;
       gibbs_rng(p, c, 0u, (uint32_t)p.it, 0x62000000u + (uint32_t)(lane >> 1), U0, U1);
-      const double R = sqrt(-2.0 * log(U0));
-      sincos(RM_PI2 * U1, &sn, &cs);
-      Tn = (lane & 1) ? R * sn : R * cs;
+      Tn = normal_of_pair(U0, U1, lane & 1);
     }
   }
   const double* __restrict__ Lt = p.Lt + (size_t)c * DP * DP;
@@ -385,7 +384,7 @@ __global__ __launch_bounds__(GIBBS_MIX_ROWS) void k_gibbs_mix(DevData dd, GibbsP
     } else {
       double U0, U1;
       gibbs_rng(p, c, (uint32_t)row, (uint32_t)p.it, 0x63000000u + 2u * (uint32_t)att, U0, U1);
-      Y = sqrt(-2.0 * log(U0)) * cos(RM_PI2 * U1);
+      Y = normal_first(U0, U1);
       gibbs_rng(p, c, (uint32_t)row, (uint32_t)p.it, 0x63000001u + 2u * (uint32_t)att, Ua, Ub);
     }
     Y = Y * Y;

@@ -1,5 +1,5 @@
-// iwls.hip.h — the reference's IWLS Metropolis-Hastings sampler (code/iwls.py:13-89) on gfx950, included by rmhmc_hip.hip after
-// kernels.hip.h.  D <= 64: one wavefront per chain, lane = dimension.
+// iwls.hip.h — the reference's IWLS Metropolis-Hastings sampler (code/iwls.py:13-89) on gfx950, on the helpers of kernels.hip.h.
+// D <= 64: one wavefront per chain, lane = dimension.
 //
 // Per chain, with the point record of kernels.hip.h (Rec: w, grad = X'(t - p) - w/alpha, L L' = G = X'WX + I/alpha, Ginv, ljl, hld):
 //   mean          m(w) = w + Ginv grad                      (the reference's cov X'W z, iwls.py:33-35,59-61, without 1/W)
@@ -12,9 +12,10 @@
 //
 // One iteration is: k_iwls_begin, the point evaluation at w' (eval_point_phases mode 1: row pass, assembly on the fp64 or int8 matrix
 // cores, factor / inverse), compat only k_iwls_ljit on trj.Ginv and k_iwls_sat, then k_iwls_end.
-// Random streams (kernels.hip.h header): proposal normals from draw_normals (blocks d/2, Box-Muller), acceptance uniform U1 of block
-// 0x40000000; counter iteration = i, key (seed, chain_offset + c).  The replay entry point reads w' and u from tapes instead.
+// Random streams (kernels.hip.h header): proposal normals from draw_normals (blocks d/2, Box-Muller), acceptance uniform from rng_u_acc
+// (RM_BLOCK_LEN_ACC); counter iteration = i, key (seed, chain_offset + c).  The replay entry point reads w' and u from tapes instead.
 #pragma once
+#include "kernels.hip.h"
 
 struct IwlsParams {
   unsigned long long seed;
@@ -34,35 +35,16 @@ struct IwlsParams {
   double* mcur;            // [n][DP] m(cur.w) of this iteration
 };
 
-// m_lane = w_lane + sum_j Ginv[j][lane] g_j (Ginv symmetric; gs: the gradient in LDS).  Sixteen rows in flight; the same sums in the
-// same order for cur (k_iwls_begin) and trj (k_iwls_end), so the mean of an accepted proposal is the one the next iteration recomputes.
+// m_lane = w_lane + sum_j Ginv[j][lane] g_j (Ginv symmetric; gs: the gradient in LDS).  The same sums in the same order for cur
+// (k_iwls_begin) and trj (k_iwls_end), so the mean of an accepted proposal is the one the next iteration recomputes.
 __device__ __forceinline__ double iwls_mean(const double* __restrict__ Gi, const double* gs, double w, int D, int DP, int lane) {
-  const bool in = lane < D;
-  double y = 0.0;
-  for (int j0 = 0; j0 < D; j0 += 16) {
-    double g[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) g[q] = (in && j0 + q < D) ? Gi[(size_t)(j0 + q) * DP + lane] : 0.0;
-#pragma unroll
-    for (int q = 0; q < 16; ++q)
-      if (in && j0 + q < D) y = fma(g[q], gs[j0 + q], y);
-  }
-  return w + y;
+  return w + symv64(Gi, D, DP, lane, [&](int j) { return gs[j]; });
 }
 
-// |L' d|^2 for d in LDS (L lower): y_lane = sum_{i >= lane} L[i][lane] d_i
+// |L' d|^2 for d in LDS (L lower)
 __device__ __forceinline__ double iwls_quad(const double* __restrict__ L, const double* ds, int D, int DP, int lane) {
-  const bool in = lane < D;
-  double y = 0.0;
-  for (int i0 = 0; i0 < D; i0 += 16) {
-    double l[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) l[q] = (in && i0 + q < D && i0 + q >= lane) ? L[(size_t)(i0 + q) * DP + lane] : 0.0;
-#pragma unroll
-    for (int q = 0; q < 16; ++q)
-      if (in && i0 + q < D && i0 + q >= lane) y = fma(l[q], ds[i0 + q], y);
-  }
-  return wave_sum(in ? y * y : 0.0);
+  const double y = ltv64(L, D, DP, lane, [&](int i) { return ds[i]; });
+  return wave_sum(lane < D ? y * y : 0.0);
 }
 
 // proposal, and LJL(w) + log q(w' | w) of the current state into Hcur
@@ -179,8 +161,7 @@ __global__ __launch_bounds__(64) void k_iwls_end(int D, int DP, Chains ch, IwlsP
     if (p.w_prop) {
       u = p.u_in[(size_t)c * p.T + p.it];
     } else {
-      double U0;
-      rng_block(p.seed, (unsigned long long)(p.chain_offset + c), (uint32_t)p.it, 0x40000000u, U0, u);
+      u = rng_u_acc(p.seed, (unsigned long long)(p.chain_offset + c), (uint32_t)p.it);
     }
     accept = ratio > log(u);
   }

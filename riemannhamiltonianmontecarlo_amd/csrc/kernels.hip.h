@@ -92,12 +92,14 @@ __device__ __forceinline__ double col4_sum(double x) {
 // ---------------------------------------------------------------------------------------------
 // Philox4x32-10 counter RNG — same stream specification as oracle/rmhmc_oracle.c:
 // key = seed, counter = (chain lo, chain hi, iteration, block); blocks 0..ceil(D/2)-1 -> momentum
-// normals (Box-Muller), block 0x40000000 -> (u_len, u_acc), block 0x40000001 -> g_dir.
+// normals (Box-Muller), block 0x40000000 = RM_BLOCK_LEN_ACC -> (u_len, u_acc), block 0x40000001 = RM_BLOCK_GDIR -> g_dir.
 // Adaptive Metropolis (amh.hip.h; no oracle counterpart): blocks 0x50000000 + d/2 -> proposal normals z_d (Box-Muller, cos for even
 // d, sin for odd), blocks 0x50001000 + d/2 -> acceptance uniforms u_d (U0 for even d, U1 for odd); iteration = IterationNum.
 // IWLS Metropolis-Hastings (iwls.hip.h; no oracle counterpart) reuses the streams above: proposal normals z from draw_normals (blocks
 // d/2, Box-Muller), acceptance uniform U1 of block 0x40000000; iteration = i, key (seed, chain_offset + c).
 // ---------------------------------------------------------------------------------------------
+#define RM_BLOCK_LEN_ACC 0x40000000u
+#define RM_BLOCK_GDIR 0x40000001u
 __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
 #pragma unroll
   for (int r = 0; r < 10; r++) {
@@ -116,6 +118,30 @@ __device__ __forceinline__ void rng_block(uint64_t seed, uint64_t chain, uint32_
   philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
   U0 = u53(c[0], c[1]);
   U1 = u53(c[2], c[3]);
+}
+// Box-Muller: normal number `odd` (0: the cosine one, 1: the sine one) of the pair (U0, U1), and the first alone (its cosine on its own:
+// one function, not sincos).  sincos before the radius: the other order costs k_amh a wave per SIMD (profiles/chain_helpers_ab.txt).
+__device__ __forceinline__ double normal_of_pair(double U0, double U1, bool odd) {
+  double sn, cs;
+  sincos(RM_PI2 * U1, &sn, &cs);
+  return sqrt(-2.0 * log(U0)) * (odd ? sn : cs);
+}
+__device__ __forceinline__ double normal_first(double U0, double U1) { return sqrt(-2.0 * log(U0)) * cos(RM_PI2 * U1); }
+// the draws of transition `iter` of chain `chain` that are not momentum normals
+__device__ __forceinline__ double rng_u_len(uint64_t seed, uint64_t chain, uint32_t iter) {
+  double u_len, u_acc;
+  rng_block(seed, chain, iter, RM_BLOCK_LEN_ACC, u_len, u_acc);
+  return u_len;
+}
+__device__ __forceinline__ double rng_u_acc(uint64_t seed, uint64_t chain, uint32_t iter) {
+  double u_len, u_acc;
+  rng_block(seed, chain, iter, RM_BLOCK_LEN_ACC, u_len, u_acc);
+  return u_acc;
+}
+__device__ __forceinline__ double rng_g_dir(uint64_t seed, uint64_t chain, uint32_t iter) {
+  double U0, U1;
+  rng_block(seed, chain, iter, RM_BLOCK_GDIR, U0, U1);
+  return normal_first(U0, U1);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1429,6 +1455,103 @@ __device__ __forceinline__ void load_mat_lds(double* A, const double* __restrict
   __builtin_amdgcn_wave_barrier();
 }
 
+// ---------------------------------------------------------------------------------------------
+// Building blocks of the one-wavefront-per-chain kernels.  Each exists ONCE per schedule, so that the sums two kernels must agree on
+// bit for bit (stepping paths, fused and unfused launches, a resumed and an uninterrupted chain) are the same loop.  A new per-chain
+// kernel calls these.  `s` is a callable: s(j) = element j of the vector (LDS, rdlane of a register, or computed on the fly).
+// ---------------------------------------------------------------------------------------------
+// y_lane = sum_j Gi[j][lane] s(j) for a symmetric Gi (row j read coalesced), D <= 64, lane = dimension, sixteen rows in flight
+template <class S>
+__device__ __forceinline__ double symv64(const double* __restrict__ Gi, int D, int DP, int lane, S s) {
+  const bool in = lane < D;
+  double y = 0.0;
+  for (int j0 = 0; j0 < D; j0 += 16) {
+    double g[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) g[q] = (in && j0 + q < D) ? Gi[(size_t)(j0 + q) * DP + lane] : 0.0;
+#pragma unroll
+    for (int q = 0; q < 16; ++q)
+      if (in && j0 + q < D) y = fma(g[q], s(j0 + q), y);
+  }
+  return y;
+}
+// The same product with the loads ahead of the sums: the caller requests the first sixteen rows (symv64_first) before its other loads,
+// every block of the loop the next sixteen.  Every chain's wavefront is resident at once in these launches, so a launch lasts as long
+// as ONE wavefront's chain of round trips.
+__device__ __forceinline__ void symv64_first(const double* __restrict__ Gi, int D, int DP, int lane, double (&g)[16]) {
+#pragma unroll
+  for (int q = 0; q < 16; ++q) g[q] = (lane < D && q < D) ? Gi[q * DP + lane] : 0.0;
+}
+template <class S>
+__device__ __forceinline__ double symv64_ahead(const double* __restrict__ Gi, int D, int DP, int lane, double (&g)[16], S s) {
+  const bool in = lane < D;
+  double y = 0.0;
+  for (int j0 = 0; j0 < D; j0 += 16) {
+    double gn[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) gn[q] = (in && j0 + 16 + q < D) ? Gi[(j0 + 16 + q) * DP + lane] : 0.0;
+#pragma unroll
+    for (int q = 0; q < 16; ++q)
+      if (in && j0 + q < D) y = fma(g[q], s(j0 + q), y);
+#pragma unroll
+    for (int q = 0; q < 16; ++q) g[q] = gn[q];
+  }
+  return y;
+}
+// y_lane = sum_{i >= lane} L[i][lane] s(i) = (L' s)_lane for a lower factor L, D <= 64, sixteen rows in flight
+template <class S>
+__device__ __forceinline__ double ltv64(const double* __restrict__ L, int D, int DP, int lane, S s) {
+  const bool in = lane < D;
+  double y = 0.0;
+  for (int i0 = 0; i0 < D; i0 += 16) {
+    double l[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) l[q] = (in && i0 + q < D && i0 + q >= lane) ? L[(size_t)(i0 + q) * DP + lane] : 0.0;
+#pragma unroll
+    for (int q = 0; q < 16; ++q)
+      if (in && i0 + q < D && i0 + q >= lane) y = fma(l[q], s(i0 + q), y);
+  }
+  return y;
+}
+// sum over the row-split planes part[(s n + c) DP + d], s < nsplit: one load, one add at a time ...
+__device__ __forceinline__ double plane_sum(const double* __restrict__ part, int nsplit, int n, int c, int DP, int d) {
+  double q = 0.0;
+  for (int s = 0; s < nsplit; ++s) q += part[((size_t)s * n + c) * DP + d];
+  return q;
+}
+// ... and with sixteen loads in flight (the same sum in the same order)
+__device__ __forceinline__ double plane_sum16(const double* __restrict__ part, int nsplit, int n, int c, int DP, int d) {
+  double q = 0.0;
+  for (int s0 = 0; s0 < nsplit; s0 += 16) {
+    double t[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) t[k] = (s0 + k < nsplit) ? part[((size_t)(s0 + k) * n + c) * DP + d] : 0.0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      if (s0 + k < nsplit) q += t[k];
+  }
+  return q;
+}
+// momentum update p + h (grad - tr/2 + q/2), h = tau eps / 2   (rmhmc.py:108,163)
+__device__ __forceinline__ double mom_step(double p, double h, double grad, double tr, double q) { return p + h * (grad - 0.5 * tr + 0.5 * q); }
+// register-resident data rows of a 256-thread workgroup (one chain per workgroup): thread t keeps rows n = t, t + 256, ... (RR of them;
+// Mp <= 256 RR) of X (row stride DPc) and of the targets for the whole launch; rows past Mp are zero
+template <int RR, int DPc>
+__device__ __forceinline__ void load_rows_regs(const double* __restrict__ Xr, const double* __restrict__ tv, int Mp, int t, double (&xk)[RR][DPc],
+                                               double (&tk)[RR]) {
+#pragma unroll
+  for (int r = 0; r < RR; ++r) {
+    const int n = t + 256 * r;
+    const bool in = n < Mp;
+    tk[r] = in ? tv[n] : 0.0;
+#pragma unroll
+    for (int d = 0; d < DPc; d += 2) {
+      const double2 q = in ? *(const double2*)(Xr + (size_t)n * DPc + d) : make_double2(0.0, 0.0);
+      xk[r][d] = q.x; xk[r][d + 1] = q.y;
+    }
+  }
+}
+
 // position fixed point, first iterate (rmhmc.py:113-122 with FixedIter = 0): G(Pw^0) = G(w) is the
 // factor already stored in the trajectory record, so u = u0 and Pw^1 = w + tau*eps*u0.
 // upd_nsplit > 0: the last momentum fixed-point update p = p + tau eps/2 (grad - tr/2 + q/2) (rmhmc.py:108,110; k_mom_update with final = 1)
@@ -1442,37 +1565,18 @@ __global__ __launch_bounds__(64) void k_pos_first(int D, int DP, Chains ch, doub
   if (ch.phase[c] != 1) return;
   const double* __restrict__ Gi = ch.trj.Ginv + (size_t)c * DP * DP;
   const bool in = lane < D;
-  double g[16];  // sixteen matrix rows in flight, the first sixteen requested before the partial sums (as k_mom_update_matvec)
-#pragma unroll
-  for (int q = 0; q < 16; ++q) g[q] = (in && q < D) ? Gi[q * DP + lane] : 0.0;  // symmetric: row j read coalesced
+  double g[16];  // the first sixteen matrix rows, requested before the partial sums (as k_mom_update_matvec)
+  symv64_first(Gi, D, DP, lane, g);
   double pb = in ? ch.p[(size_t)c * DP + lane] : 0.0;
   if (upd_nsplit > 0 && in) {
     const size_t o = (size_t)c * DP + lane;
-    double q = 0.0;
-    for (int s0 = 0; s0 < upd_nsplit; s0 += 16) {
-      double t[16];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) t[k] = (s0 + k < upd_nsplit) ? ch.qpart[((size_t)(s0 + k) * ch.n + c) * DP + lane] : 0.0;
-#pragma unroll
-      for (int k = 0; k < 16; ++k)
-        if (s0 + k < upd_nsplit) q += t[k];
-    }
-    pb = pb + (ch.tau[c] * eps * 0.5) * (ch.trj.grad[o] - 0.5 * ch.trj.tr[o] + 0.5 * q);
+    const double q = plane_sum16(ch.qpart, upd_nsplit, ch.n, c, DP, lane);
+    pb = mom_step(pb, ch.tau[c] * eps * 0.5, ch.trj.grad[o], ch.trj.tr[o], q);
     ch.p[o] = pb;
   }
-  double u0 = 0.0;
   A[lane] = pb;
   __builtin_amdgcn_wave_barrier();
-  for (int j0 = 0; j0 < D; j0 += 16) {
-    double gn[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) gn[q] = (in && j0 + 16 + q < D) ? Gi[(j0 + 16 + q) * DP + lane] : 0.0;
-#pragma unroll
-    for (int q = 0; q < 16; ++q)
-      if (in && j0 + q < D) u0 = fma(g[q], A[j0 + q], u0);
-#pragma unroll
-    for (int q = 0; q < 16; ++q) g[q] = gn[q];
-  }
+  const double u0 = symv64_ahead(Gi, D, DP, lane, g, [&](int j) { return A[j]; });
   if (lane < D) {
     ch.u0[(size_t)c * DP + lane] = u0;
     ch.wq[(size_t)c * DP + lane] = ch.trj.w[(size_t)c * DP + lane] + ch.tau[c] * eps * u0;
@@ -1510,6 +1614,20 @@ __global__ __launch_bounds__(64) void k_factor_solve(int D, int DP, Chains ch, d
 // (d = lane, lane+64, ...), so they serve D <= 64 and the large-D path (D <= 256) alike.
 #define RM_DMAX 256
 #define RM_DCH 4   // RM_DMAX / 64 dimension chunks per lane
+// symv64's product strided over up to RM_DMAX dimensions: y[k] = sum_j Gi[j][lane + 64 k] s(j), one row at a time
+template <class S>
+__device__ __forceinline__ void symv_strided(const double* __restrict__ Gi, int D, int DP, int lane, S s, double (&y)[RM_DCH]) {
+#pragma unroll
+  for (int k = 0; k < RM_DCH; ++k) y[k] = 0.0;
+  for (int j = 0; j < D; ++j) {
+    const double sj = s(j);
+#pragma unroll
+    for (int k = 0; k < RM_DCH; ++k) {
+      const int d = lane + 64 * k;
+      if (d < D) y[k] = fma(Gi[(size_t)j * DP + d], sj, y[k]);  // symmetric: row j read coalesced
+    }
+  }
+}
 
 // accept the position iterate as the new w and apply the position guard (rmhmc.py:123-130)
 __global__ __launch_bounds__(64) void k_pos_final(int D, int DP, Chains ch, int guards) {
@@ -1673,11 +1791,7 @@ __global__ __launch_bounds__(64) void k_factor_full(DevData dd, Chains ch, int n
   for (int b = lane; b < nsplit; b += 64) part += ch.ljl_part[(size_t)c * nsplit + b];
   const double wl = (lane < D) ? ch.trj.w[(size_t)c * DP + lane] : 0.0;
   // gradient = X'(t - s) - w/alpha (rmhmc.py:100,140): sum of the row-split partials of k_rowpass<RP_F>
-  if (lane < D) {
-    double g = 0.0;
-    for (int sp = 0; sp < nsplit; ++sp) g += ch.gpart[((size_t)sp * ch.n + c) * DP + lane];
-    ch.trj.grad[(size_t)c * DP + lane] = g - wl * dd.inv_alpha;
-  }
+  if (lane < D) ch.trj.grad[(size_t)c * DP + lane] = plane_sum(ch.gpart, nsplit, ch.n, c, DP, lane) - wl * dd.inv_alpha;
   part += (lane < D) ? (dd.log_prior_const - wl * wl * 0.5 * dd.inv_alpha) : 0.0;
   const double ljl = wave_sum(part);
   if (lane == 0) {
@@ -1692,30 +1806,15 @@ __global__ __launch_bounds__(64) void k_ginv_matvec(int D, int DP, Chains ch, co
   const int c = blockIdx.x, lane = threadIdx.x;
   if (ch.phase[c] != 1) return;
   const double* __restrict__ Gi = ch.trj.Ginv + (size_t)c * DP * DP;
-  if (D <= 64) {  // lane = dimension, sixteen rows in flight (as k_mom_update_matvec); the same sums in the same order as the loop below
+  if (D <= 64) {  // lane = dimension; the same sums in the same order as the strided product below
     const bool in = lane < D;
     const double sv = in ? src[(size_t)c * DP + lane] : 0.0;
-    double u0 = 0.0;
-    for (int j0 = 0; j0 < D; j0 += 16) {
-      double g[16];
-#pragma unroll
-      for (int q = 0; q < 16; ++q) g[q] = (in && j0 + q < D) ? Gi[(j0 + q) * DP + lane] : 0.0;
-#pragma unroll
-      for (int q = 0; q < 16; ++q)
-        if (in && j0 + q < D) u0 = fma(g[q], rdlane(sv, j0 + q), u0);
-    }
+    const double u0 = symv64(Gi, D, DP, lane, [&](int j) { return rdlane(sv, j); });
     if (in) ch.uq[(size_t)c * DP + lane] = u0;
     return;
   }
-  double u[RM_DCH] = {0.0, 0.0, 0.0, 0.0};
-  for (int j = 0; j < D; ++j) {
-    const double sj = src[(size_t)c * DP + j];
-#pragma unroll
-    for (int k = 0; k < RM_DCH; ++k) {
-      const int d = lane + 64 * k;
-      if (d < D) u[k] = fma(Gi[j * DP + d], sj, u[k]);  // symmetric: row j read coalesced
-    }
-  }
+  double u[RM_DCH];
+  symv_strided(Gi, D, DP, lane, [&](int j) { return src[(size_t)c * DP + j]; }, u);
 #pragma unroll
   for (int k = 0; k < RM_DCH; ++k)
     if (lane + 64 * k < D) ch.uq[(size_t)c * DP + lane + 64 * k] = u[k];
@@ -1728,9 +1827,7 @@ __global__ __launch_bounds__(64) void k_mom_update(int D, int DP, Chains ch, dou
   const double h = ch.tau[c] * eps * 0.5;
   for (int d = lane; d < D; d += 64) {
     const size_t o = (size_t)c * DP + d;
-    double q = 0.0;
-    for (int s = 0; s < nsplit; ++s) q += ch.qpart[((size_t)s * ch.n + c) * DP + d];
-    const double pm = ch.p[o] + h * (ch.trj.grad[o] - 0.5 * ch.trj.tr[o] + 0.5 * q);
+    const double pm = mom_step(ch.p[o], h, ch.trj.grad[o], ch.trj.tr[o], plane_sum(ch.qpart, nsplit, ch.n, c, DP, d));
     if (final) ch.p[o] = pm;
     else ch.PM[o] = pm;
   }
@@ -1743,36 +1840,15 @@ __global__ __launch_bounds__(64) void k_mom_update_matvec(int D, int DP, Chains 
   const size_t o = (size_t)c * DP + lane;
   const double* __restrict__ Gi = ch.trj.Ginv + (size_t)c * DP * DP;
   const bool in = lane < D;
-  // sixteen matrix rows in flight at a time, the first sixteen requested before the partial sums are (every chain's wavefront is resident at
-  // once here, so the launch lasts as long as ONE wavefront's chain of round trips: it was one per row and one per partial)
-  double g[16];
-#pragma unroll
-  for (int q = 0; q < 16; ++q) g[q] = (in && q < D) ? Gi[q * DP + lane] : 0.0;  // symmetric: row j read coalesced
+  double g[16];  // the first sixteen matrix rows, requested before the partial sums are (it was one round trip per row and one per partial)
+  symv64_first(Gi, D, DP, lane, g);
   double pm = 0.0;
   if (in) {
-    double q = 0.0;
-    for (int s0 = 0; s0 < nsplit; s0 += 16) {
-      double t[16];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) t[k] = (s0 + k < nsplit) ? ch.qpart[((size_t)(s0 + k) * ch.n + c) * DP + lane] : 0.0;
-#pragma unroll
-      for (int k = 0; k < 16; ++k)
-        if (s0 + k < nsplit) q += t[k];
-    }
-    pm = ch.p[o] + (ch.tau[c] * eps * 0.5) * (ch.trj.grad[o] - 0.5 * ch.trj.tr[o] + 0.5 * q);
+    const double q = plane_sum16(ch.qpart, nsplit, ch.n, c, DP, lane);
+    pm = mom_step(ch.p[o], ch.tau[c] * eps * 0.5, ch.trj.grad[o], ch.trj.tr[o], q);
     ch.PM[o] = pm;
   }
-  double u = 0.0;
-  for (int j0 = 0; j0 < D; j0 += 16) {
-    double gn[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) gn[q] = (in && j0 + 16 + q < D) ? Gi[(j0 + 16 + q) * DP + lane] : 0.0;
-#pragma unroll
-    for (int q = 0; q < 16; ++q)
-      if (j0 + q < D) u = fma(g[q], rdlane(pm, j0 + q), u);
-#pragma unroll
-    for (int q = 0; q < 16; ++q) g[q] = gn[q];
-  }
+  const double u = symv64_ahead(Gi, D, DP, lane, g, [&](int j) { return rdlane(pm, j); });
   if (in) ch.uq[o] = u;
 }
 
@@ -1785,15 +1861,10 @@ __global__ __launch_bounds__(64) void k_mom_final(int D, int DP, Chains ch, doub
   int nonfinite = 0;
   for (int d = lane; d < D; d += 64) {
     const size_t o = (size_t)c * DP + d;
-    if (trpart) {
-      double s = 0.0;
-      for (int sp = 0; sp < nsplit; ++sp) s += trpart[((size_t)sp * ch.n + c) * DP + d];
-      ch.trj.tr[o] = s;
-    }
-    double q = 0.0;
-    for (int s = 0; s < nsplit; ++s) q += ch.qpart[((size_t)s * ch.n + c) * DP + d];
+    if (trpart) ch.trj.tr[o] = plane_sum(trpart, nsplit, ch.n, c, DP, d);
+    const double q = plane_sum(ch.qpart, nsplit, ch.n, c, DP, d);
     ch.last[o] = q;
-    const double pn = advance ? ch.p[o] + h * (ch.trj.grad[o] - 0.5 * ch.trj.tr[o] + 0.5 * q) : ch.p[o];
+    const double pn = advance ? mom_step(ch.p[o], h, ch.trj.grad[o], ch.trj.tr[o], q) : ch.p[o];
     if (advance) ch.p[o] = pn;
     nonfinite |= !(isfinite(pn) && isfinite(ch.trj.w[o]));
   }
@@ -1875,27 +1946,11 @@ __device__ __forceinline__ double half_quadform(const double* __restrict__ Gi, i
   if (D <= 64) {
     // lane = dimension; sixteen rows in flight at a time (the loop below is one load - one wait per row: in k_iter_begin / k_iter_end, where only
     // the chains at a transition boundary work, 64 serial round trips were most of the kernels' 110 / 88 us).  Same sums in the same order.
-    const bool in = lane < D;
-    double y = 0.0;
-    for (int j0 = 0; j0 < D; j0 += 16) {
-      double g[16];
-#pragma unroll
-      for (int q = 0; q < 16; ++q) g[q] = (in && j0 + q < D) ? Gi[(size_t)(j0 + q) * DP + lane] : 0.0;
-#pragma unroll
-      for (int q = 0; q < 16; ++q)
-        if (in && j0 + q < D) y = fma(g[q], ps[j0 + q], y);
-    }
-    return 0.5 * wave_sum(in ? fma(y, ps[lane], 0.0) : 0.0);
+    const double y = symv64(Gi, D, DP, lane, [&](int j) { return ps[j]; });
+    return 0.5 * wave_sum(lane < D ? fma(y, ps[lane], 0.0) : 0.0);
   }
-  double y[RM_DCH] = {0.0, 0.0, 0.0, 0.0};
-  for (int j = 0; j < D; ++j) {
-    const double pj = ps[j];
-#pragma unroll
-    for (int k = 0; k < RM_DCH; ++k) {
-      const int d = lane + 64 * k;
-      if (d < D) y[k] = fma(Gi[j * DP + d], pj, y[k]);
-    }
-  }
+  double y[RM_DCH];
+  symv_strided(Gi, D, DP, lane, [&](int j) { return ps[j]; }, y);
   double s = 0.0;
 #pragma unroll
   for (int k = 0; k < RM_DCH; ++k)
@@ -1912,13 +1967,35 @@ __device__ __forceinline__ void draw_normals(const IterParams& ip, int c, long l
     } else {
       double U0, U1;
       rng_block(ip.seed, (unsigned long long)(ip.chain_offset + id), (uint32_t)it, (uint32_t)(d >> 1), U0, U1);
-      const double R = sqrt(-2.0 * log(U0));
-      double sn, cs;
-      sincos(RM_PI2 * U1, &sn, &cs);
-      zs[d] = (d & 1) ? R * sn : R * cs;
+      zs[d] = normal_of_pair(U0, U1, d & 1);
     }
   }
   __builtin_amdgcn_wave_barrier();  // callers are one wavefront (a 64-thread block, or wave 0 of k_step_medium): LDS is in order per wave
+}
+// trajectory-length and acceptance uniforms of transition `it` of the chain at position c, chain id in the caller's order (or the
+// caller-supplied draws)
+__device__ __forceinline__ double draw_u_len(const IterParams& ip, int c, long long id, long long it) {
+  return ip.z_in ? ip.ulen_in[c] : rng_u_len(ip.seed, (unsigned long long)(ip.chain_offset + id), (uint32_t)it);
+}
+__device__ __forceinline__ double draw_u_acc(const IterParams& ip, int c, long long id, long long it) {
+  return ip.z_in ? ip.uacc_in[c] : rng_u_acc(ip.seed, (unsigned long long)(ip.chain_offset + id), (uint32_t)it);
+}
+// accept test of a transition (rmhmc.py:181, hmc.py:77)
+__device__ __forceinline__ bool mh_accept(double ratio, double u_acc) { return (ratio > 0.0) || (ratio > log(u_acc)); }
+// End of a transition once the decision is taken and an accepted record copied (a lane reads back only what it wrote itself, or the
+// caller has put a barrier in between): the row of `samples`, Hprop, the counters, phase 0.  id: as draw_u_len.
+__device__ __forceinline__ void close_transition(int D, int DP, const Chains& ch, const IterParams& ip, int c, long long id, int lane, long long it,
+                                                 double hprop, bool accept) {
+  if (ip.samples && it >= ip.burn_in && it - ip.burn_in < ip.S)
+    for (int d = lane; d < D; d += 64)
+      ip.samples[((size_t)id * ip.S + (size_t)(it - ip.burn_in)) * D + d] = ch.cur.w[(size_t)c * DP + d];
+  if (lane == 0) {
+    ch.Hprop[c] = hprop;
+    if (accept) ch.accepted[c] += 1;
+    ch.iter[c] = it + 1;
+    ch.phase[c] = 0;
+    if (it + 1 == ip.iter_limit && ip.done_count) atomicAdd(ip.done_count, 1);
+  }
 }
 
 // start of a transition for chain c, executed by ONE wavefront (zs, ps: LDS scratch of D doubles each)
@@ -1933,40 +2010,27 @@ __device__ __forceinline__ void iter_begin_dev(int D, int DP, const Chains& ch, 
   const long long oc = ip.orig ? ip.orig[c] : c;
   // draws: z ~ randn(1,D), u_len ~ rand(), g_dir ~ randn()   (rmhmc.py:80,89,90)
   draw_normals(ip, c, it, D, lane, zs, oc);
-  double u_len, g_dir;
-  if (ip.z_in) {
-    u_len = ip.ulen_in[c];
-    g_dir = ip.gdir_in[c];
-  } else {
-    const unsigned long long gid = (unsigned long long)(ip.chain_offset + oc);
-    double U0, U1, Ua;
-    rng_block(ip.seed, gid, (uint32_t)it, 0x40000000u, u_len, Ua);
-    rng_block(ip.seed, gid, (uint32_t)it, 0x40000001u, U0, U1);
-    g_dir = sqrt(-2.0 * log(U0)) * cos(RM_PI2 * U1);
-  }
+  const double u_len = draw_u_len(ip, c, oc, it);
+  const double g_dir = ip.z_in ? ip.gdir_in[c] : rng_g_dir(ip.seed, (unsigned long long)(ip.chain_offset + oc), (uint32_t)it);
   // momentum p = L' z (reference, rmhmc.py:60,80) or L z (corrected)
   const double* __restrict__ Lc = ch.cur.L + (size_t)c * DP * DP;
   double p[RM_DCH] = {0.0, 0.0, 0.0, 0.0};
   if (D <= 64) {  // lane = dimension, sixteen loads in flight (as half_quadform); the same sums in the same order as the loops below
     const int d = lane;
-    double acc = 0.0;
-    for (int j0 = 0; j0 < D; j0 += 16) {
-      double l[16];
-      if (ip.flags & 1u) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) l[q] = (j0 + q < D && d <= j0 + q) ? Lc[(size_t)(j0 + q) * DP + d] : 0.0;   // L' z: column d of row j0 + q
-#pragma unroll
-        for (int q = 0; q < 16; ++q)
-          if (j0 + q < D && d <= j0 + q) acc = fma(l[q], zs[j0 + q], acc);
-      } else {
+    if (ip.flags & 1u) {
+      p[0] = ltv64(Lc, D, DP, lane, [&](int i) { return zs[i]; });  // L' z: column d of every row
+    } else {
+      double acc = 0.0;
+      for (int j0 = 0; j0 < D; j0 += 16) {
+        double l[16];
 #pragma unroll
         for (int q = 0; q < 16; ++q) l[q] = (d < D && j0 + q <= d) ? Lc[(size_t)d * DP + j0 + q] : 0.0;            // L z: the lane's own row
 #pragma unroll
         for (int q = 0; q < 16; ++q)
           if (d < D && j0 + q <= d) acc = fma(l[q], zs[j0 + q], acc);
       }
+      p[0] = acc;
     }
-    p[0] = acc;
   } else if (ip.flags & 1u) {
     for (int i = 0; i < D; ++i) {
       const double zi = zs[i];
@@ -2037,30 +2101,14 @@ __device__ __forceinline__ void iter_end_dev(int D, int DP, const Chains& ch, co
   const double quad = half_quadform(ch.trj.Ginv + (size_t)c * DP * DP, D, DP, lane, ps);
   const double Hp = -ch.trj.ljl[c] + ch.trj.hld[c] + quad;  // rmhmc.py:171-172
   const double ratio = -Hp + ch.Hcur[c];                     // rmhmc.py:179
-  double u_acc;
-  if (ip.z_in) {
-    u_acc = ip.uacc_in[c];
-  } else {
-    double U0;
-    rng_block(ip.seed, (unsigned long long)(ip.chain_offset + oc), (uint32_t)it, 0x40000000u, U0, u_acc);
-  }
-  const bool accept = (ratio > 0.0) || (ratio > log(u_acc));  // rmhmc.py:181
+  const bool accept = mh_accept(ratio, draw_u_acc(ip, c, oc, it));  // rmhmc.py:181
   if (accept) copy_rec(ch.cur, ch.trj, c, D, DP, lane, ip.lower_L != 0);
   __builtin_amdgcn_wave_barrier();  // (a lane reads back only what it wrote itself)
-  if (ip.samples && it >= ip.burn_in && it - ip.burn_in < ip.S)
-    for (int d = lane; d < D; d += 64)
-      ip.samples[((size_t)oc * ip.S + (size_t)(it - ip.burn_in)) * D + d] = ch.cur.w[(size_t)c * DP + d];
-  if (lane == 0) {
-    ch.Hprop[c] = Hp;
-    if (accept) ch.accepted[c] += 1;
-    else if (ch.cstale) {
-      ch.cstale[c] = 1;
-      if (ch.stale_list) ch.stale_list[atomicAdd(ch.stale_count, 1)] = c;
-    }
-    ch.iter[c] = it + 1;
-    ch.phase[c] = 0;
-    if (it + 1 == ip.iter_limit && ip.done_count) atomicAdd(ip.done_count, 1);
+  if (!accept && ch.cstale && lane == 0) {
+    ch.cstale[c] = 1;
+    if (ch.stale_list) ch.stale_list[atomicAdd(ch.stale_count, 1)] = c;
   }
+  close_transition(D, DP, ch, ip, c, oc, lane, it, Hp, accept);
 }
 
 __global__ __launch_bounds__(64) void k_iter_end(int D, int DP, Chains ch, IterParams ip) {
@@ -2083,9 +2131,7 @@ __device__ __forceinline__ void hmc_finish_eval(const DevData& dd, const Chains&
   double part = 0.0;
   for (int d = lane; d < D; d += 64) {
     const double wl = ch.trj.w[(size_t)c * DP + d];
-    double g = 0.0;
-    for (int sp = 0; sp < nsplit; ++sp) g += ch.gpart[((size_t)sp * ch.n + c) * DP + d];
-    ch.trj.grad[(size_t)c * DP + d] = g - wl * dd.inv_alpha;
+    ch.trj.grad[(size_t)c * DP + d] = plane_sum(ch.gpart, nsplit, ch.n, c, DP, d) - wl * dd.inv_alpha;
     part += dd.log_prior_const - wl * wl * 0.5 * dd.inv_alpha;
   }
   for (int b = lane; b < nsplit; b += 64) part += ch.ljl_part[(size_t)c * nsplit + b];
@@ -2106,6 +2152,29 @@ __global__ __launch_bounds__(64) void k_hmc_init(DevData dd, Chains ch, int nspl
   __syncthreads();
   hmc_copy(ch.cur, ch.trj, c, dd.D, dd.DP, lane);
 }
+// Start of transition `it` of chain c (hmc.py:41-48,72), executed by ONE wavefront: cur -> trj, z ~ N(0, I) into zs (D doubles in LDS),
+// the trajectory length, H_cur = -LJL + z'z / 2 (the kinetic energy of p = Lm z under Mass = Lm Lm', whatever Lm), counters and phase.
+// Returns the number of leapfrog steps.
+__device__ __forceinline__ int hmc_begin_dev(int D, int DP, const Chains& ch, const IterParams& ip, int c, int lane, long long it, double* zs) {
+  hmc_copy(ch.trj, ch.cur, c, D, DP, lane);
+  draw_normals(ip, c, it, D, lane, zs);
+  const double u_len = draw_u_len(ip, c, c, it);
+  double kin = 0.0;
+  for (int d = lane; d < D; d += 64) {
+    const double z = zs[d];
+    kin = fma(z, z, kin);
+  }
+  kin = 0.5 * wave_sum(kin);
+  const int ns = (int)ceil(u_len * (double)ip.L);  // hmc.py:48
+  if (lane == 0) {
+    ch.steps_left[c] = ns;
+    ch.nsteps_last[c] = ns;
+    ch.Hcur[c] = -ch.cur.ljl[c] + kin;  // hmc.py:72
+    ch.status[c] = 0;
+    ch.phase[c] = (ns > 0) ? 1 : 2;
+  }
+  return ns;
+}
 // start a transition (hmc.py:41-48,72)
 __global__ __launch_bounds__(64) void k_hmc_begin(int D, int DP, Chains ch, IterParams ip) {
   __shared__ double zs[RM_DMAX];
@@ -2113,30 +2182,8 @@ __global__ __launch_bounds__(64) void k_hmc_begin(int D, int DP, Chains ch, Iter
   if (ch.phase[c] != 0) return;
   const long long it = ch.iter[c];
   if (it >= ip.iter_limit) return;
-  hmc_copy(ch.trj, ch.cur, c, D, DP, lane);
-  draw_normals(ip, c, it, D, lane, zs);
-  double u_len;
-  if (ip.z_in) {
-    u_len = ip.ulen_in[c];
-  } else {
-    double Ua;
-    rng_block(ip.seed, (unsigned long long)(ip.chain_offset + c), (uint32_t)it, 0x40000000u, u_len, Ua);
-  }
-  double kin = 0.0;
-  for (int d = lane; d < D; d += 64) {
-    const double z = zs[d];
-    kin = fma(z, z, kin);
-    ch.p[(size_t)c * DP + d] = z;  // Mass = I: p = z (hmc.py:41)
-  }
-  kin = 0.5 * wave_sum(kin);
-  if (lane == 0) {
-    const int ns = (int)ceil(u_len * (double)ip.L);  // hmc.py:48
-    ch.steps_left[c] = ns;
-    ch.nsteps_last[c] = ns;
-    ch.Hcur[c] = -ch.cur.ljl[c] + kin;  // hmc.py:72
-    ch.status[c] = 0;
-    ch.phase[c] = (ns > 0) ? 1 : 2;
-  }
+  hmc_begin_dev(D, DP, ch, ip, c, lane, it, zs);
+  for (int d = lane; d < D; d += 64) ch.p[(size_t)c * DP + d] = zs[d];  // Mass = I: p = z (hmc.py:41)
 }
 // first momentum half step and the position step (hmc.py:52-58); a NaN momentum ends the trajectory (:56-57)
 __global__ __launch_bounds__(64) void k_hmc_pre(int D, int DP, Chains ch, double eps) {
@@ -2174,26 +2221,10 @@ __global__ __launch_bounds__(64) void k_hmc_end(int D, int DP, Chains ch, IterPa
   for (int d = lane; d < D; d += 64) { const double pl = ch.p[(size_t)c * DP + d]; kin = fma(pl, pl, kin); }
   const double Hp = -ch.trj.ljl[c] + 0.5 * wave_sum(kin);  // hmc.py:69
   const double ratio = -Hp + ch.Hcur[c];
-  double u_acc;
-  if (ip.z_in) {
-    u_acc = ip.uacc_in[c];
-  } else {
-    double U0;
-    rng_block(ip.seed, (unsigned long long)(ip.chain_offset + c), (uint32_t)it, 0x40000000u, U0, u_acc);
-  }
-  const bool accept = (ratio > 0.0) || (ratio > log(u_acc));  // hmc.py:77
+  const bool accept = mh_accept(ratio, draw_u_acc(ip, c, c, it));  // hmc.py:77
   if (accept) hmc_copy(ch.cur, ch.trj, c, D, DP, lane);
   __syncthreads();
-  if (ip.samples && it >= ip.burn_in && it - ip.burn_in < ip.S)
-    for (int d = lane; d < D; d += 64)
-      ip.samples[((size_t)c * ip.S + (size_t)(it - ip.burn_in)) * D + d] = ch.cur.w[(size_t)c * DP + d];
-  if (lane == 0) {
-    ch.Hprop[c] = Hp;
-    if (accept) ch.accepted[c] += 1;
-    ch.iter[c] = it + 1;
-    ch.phase[c] = 0;
-    if (it + 1 == ip.iter_limit && ip.done_count) atomicAdd(ip.done_count, 1);
-  }
+  close_transition(D, DP, ch, ip, c, c, lane, it, Hp, accept);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2276,15 +2307,8 @@ __global__ __launch_bounds__(64) void k_mmala_begin(int D, int DP, Chains ch, It
   }
   zz = wave_sum(zz);
   __syncthreads();
-  double u[RM_DCH] = {0.0, 0.0, 0.0, 0.0};
-  for (int j = 0; j < D; ++j) {
-    const double tj = ts[j];
-#pragma unroll
-    for (int k = 0; k < RM_DCH; ++k) {
-      const int d = lane + 64 * k;
-      if (d < D) u[k] = fma(Gi[(size_t)j * DP + d], tj, u[k]);
-    }
-  }
+  double u[RM_DCH];
+  symv_strided(Gi, D, DP, lane, [&](int j) { return ts[j]; }, u);
 #pragma unroll
   for (int k = 0; k < RM_DCH; ++k) {
     const int d = lane + 64 * k;
@@ -2305,15 +2329,8 @@ __global__ __launch_bounds__(64) void k_mmala_end(int D, int DP, Chains ch, Iter
   const double* __restrict__ Lp = ch.trj.L + (size_t)c * DP * DP;
   const double* __restrict__ Gi = ch.trj.Ginv + (size_t)c * DP * DP;
   // d = w' + eps/2 G'^-1 grad' - w
-  double u[RM_DCH] = {0.0, 0.0, 0.0, 0.0};
-  for (int j = 0; j < D; ++j) {
-    const double gj = ch.trj.grad[(size_t)c * DP + j] - (full ? ch.trj.tr[(size_t)c * DP + j] : 0.0);
-#pragma unroll
-    for (int k = 0; k < RM_DCH; ++k) {
-      const int d = lane + 64 * k;
-      if (d < D) u[k] = fma(Gi[(size_t)j * DP + d], gj, u[k]);
-    }
-  }
+  double u[RM_DCH];
+  symv_strided(Gi, D, DP, lane, [&](int j) { return ch.trj.grad[(size_t)c * DP + j] - (full ? ch.trj.tr[(size_t)c * DP + j] : 0.0); }, u);
 #pragma unroll
   for (int k = 0; k < RM_DCH; ++k) {
     const int d = lane + 64 * k;
@@ -2330,26 +2347,11 @@ __global__ __launch_bounds__(64) void k_mmala_end(int D, int DP, Chains ch, Iter
   yy = wave_sum(yy);
   const double q_rev = ch.trj.hld[c] - yy / (2.0 * eps);
   const double ratio = ch.trj.ljl[c] + q_rev - ch.Hcur[c];  // :251
-  double u_acc;
-  if (ip.z_in) {
-    u_acc = ip.uacc_in[c];
-  } else {
-    double U0;
-    rng_block(ip.seed, (unsigned long long)(ip.chain_offset + c), (uint32_t)it, 0x40000000u, U0, u_acc);
-  }
-  const bool accept = (ratio > 0.0) || (ratio > log(u_acc));
+  const bool accept = mh_accept(ratio, draw_u_acc(ip, c, c, it));
   __syncthreads();
   if (accept) copy_rec(ch.cur, ch.trj, c, D, DP, lane);
   __syncthreads();
-  if (ip.samples && it >= ip.burn_in && it - ip.burn_in < ip.S)
-    for (int d = lane; d < D; d += 64)
-      ip.samples[((size_t)c * ip.S + (size_t)(it - ip.burn_in)) * D + d] = ch.cur.w[(size_t)c * DP + d];
-  if (lane == 0) {
-    ch.Hprop[c] = ratio;
-    if (accept) ch.accepted[c] += 1;
-    ch.iter[c] = it + 1;
-    ch.phase[c] = 0;
-  }
+  close_transition(D, DP, ch, ip, c, c, lane, it, ratio, accept);  // (Hprop carries the ratio; the launches of this sampler count no finished chains)
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2434,11 +2436,7 @@ __global__ void k_traj_steps(unsigned long long seed, long long chain_offset, in
   size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (c >= n) return;
   long long t = 0;
-  for (long long it = it0; it < it1; ++it) {
-    double u_len, ua;
-    rng_block(seed, (unsigned long long)(chain_offset + (long long)c), (uint32_t)it, 0x40000000u, u_len, ua);
-    t += (long long)ceil(u_len * (double)L);
-  }
+  for (long long it = it0; it < it1; ++it) t += (long long)ceil(rng_u_len(seed, (unsigned long long)(chain_offset + (long long)c), (uint32_t)it) * (double)L);
   T[c] = t;
 }
 // dst[orig[i]] = src[i]

@@ -252,11 +252,7 @@ __global__ __launch_bounds__(256) void k_trace_big(DevData dd, int n_chains, int
 __global__ __launch_bounds__(64) void k_reduce_tr(int D, int DP, Chains ch, const double* __restrict__ trpart, int nsplit) {
   const int c = blockIdx.x, lane = threadIdx.x;
   if (ch.phase[c] != 1) return;
-  for (int d = lane; d < D; d += 64) {
-    double s = 0.0;
-    for (int sp = 0; sp < nsplit; ++sp) s += trpart[((size_t)sp * ch.n + c) * DP + d];
-    ch.trj.tr[(size_t)c * DP + d] = s;
-  }
+  for (int d = lane; d < D; d += 64) ch.trj.tr[(size_t)c * DP + d] = plane_sum(trpart, nsplit, ch.n, c, DP, d);
 }
 
 // gradient and log joint from the row-split partials of k_rowpass_big<RP_F> (what k_factor_full does for D <= 64)

@@ -70,19 +70,7 @@ __global__ __launch_bounds__(256) void k_step_medium(DevData dd, Chains ch, doub
   // row passes.  MODE 0: v (and c) at `wp`; 1: v, c, gradient partials and log joint at `wp`; 2: q_d = sum c_n (x_n.u)^2 x_nd;
   // 3: tr_d = sum c_n (x_n' G^-1 x_n) x_nd.  Result vector in tmp[], scalar returned.
   double xk[RR][DPc], tk[RR];
-  if (RPT > 0) {
-#pragma unroll
-    for (int r = 0; r < RR; ++r) {
-      const int n = t + 256 * r;
-      const bool in = n < Mp;
-      tk[r] = in ? dd.t[n] : 0.0;
-#pragma unroll
-      for (int d = 0; d < DPc; d += 2) {
-        const double2 q = in ? *(const double2*)(dd.Xr + (size_t)n * DPc + d) : make_double2(0.0, 0.0);
-        xk[r][d] = q.x; xk[r][d + 1] = q.y;
-      }
-    }
-  }
+  if (RPT > 0) load_rows_regs(dd.Xr, dd.t, Mp, t, xk, tk);
   auto row_pass = [&](int mode, const double* wp, const double* up) -> double {
     double acc[DPc];
 #pragma unroll
@@ -373,19 +361,7 @@ __global__ __launch_bounds__(256) void k_hmc_traj(DevData dd, Chains ch, double 
   int status = 0, done = 0;
   double ljl = 0.0;
   double xk[RR][DPc], tk[RR];
-  if (RPT > 0) {
-#pragma unroll
-    for (int r = 0; r < RR; ++r) {
-      const int n = t + 256 * r;
-      const bool in = n < Mp;
-      tk[r] = in ? dd.t[n] : 0.0;
-#pragma unroll
-      for (int d = 0; d < DPc; d += 2) {
-        const double2 q = in ? *(const double2*)(dd.Xr + (size_t)n * DPc + d) : make_double2(0.0, 0.0);
-        xk[r][d] = q.x; xk[r][d + 1] = q.y;
-      }
-    }
-  }
+  if (RPT > 0) load_rows_regs(dd.Xr, dd.t, Mp, t, xk, tk);
   __syncthreads();
   for (int s = 0; s < steps; ++s) {
     if (!eval_only) {  // first half step and the position step (hmc.py:52-58)

@@ -106,29 +106,7 @@ __global__ __launch_bounds__(256) void k_phmc_head(int D, Chains ch, IterParams 
       if (ph == 1) {
         f = PHMC_STEP;
       } else if (ph == 0 && it < ip.iter_limit) {
-        hmc_copy(ch.trj, ch.cur, c, D, DP, lane);
-        draw_normals(ip, c, it, D, lane, v);
-        double u_len;
-        if (ip.z_in) {
-          u_len = ip.ulen_in[c];
-        } else {
-          double Ua;
-          rng_block(ip.seed, (unsigned long long)(ip.chain_offset + c), (uint32_t)it, 0x40000000u, u_len, Ua);
-        }
-        double kin = 0.0;
-        for (int d = lane; d < D; d += 64) {
-          const double z = v[d];
-          kin = fma(z, z, kin);
-        }
-        kin = 0.5 * wave_sum(kin);  // p' Mass^-1 p / 2 = z'z / 2
-        const int ns = (int)ceil(u_len * (double)ip.L);  // hmc.py:48
-        if (lane == 0) {
-          ch.steps_left[c] = ns;
-          ch.nsteps_last[c] = ns;
-          ch.Hcur[c] = -ch.cur.ljl[c] + kin;  // hmc.py:72
-          ch.status[c] = 0;
-          ch.phase[c] = (ns > 0) ? 1 : 2;
-        }
+        const int ns = hmc_begin_dev(D, DP, ch, ip, c, lane, it, v);  // (p' Mass^-1 p / 2 = z'z / 2)
         f = PHMC_BEGUN | (ns > 0 ? PHMC_STEP : 0);
       }
     }
@@ -233,28 +211,12 @@ __global__ __launch_bounds__(256) void k_phmc_tail(DevData dd, Chains ch, IterPa
     const double Hc = ch.Hcur[c];
     const double Hp = -ch.trj.ljl[c] + 0.5 * wave_sum(kin);  // hmc.py:69
     const double ratio = -Hp + Hc;
-    double u_acc;
-    if (ip.z_in) {
-      u_acc = ip.uacc_in[c];
-    } else {
-      double U0;
-      rng_block(ip.seed, (unsigned long long)(ip.chain_offset + c), (uint32_t)it, 0x40000000u, U0, u_acc);
-    }
     // a chain FAILS (include/rmhmc.h) on a NaN momentum or a Hamiltonian that is not finite at either end: rejected, state untouched
     const bool failed = (ch.status[c] & 2) || !isfinite(Hc) || !isfinite(Hp);
-    const bool accept = !failed && ((ratio > 0.0) || (ratio > log(u_acc)));  // hmc.py:77
+    const bool accept = !failed && mh_accept(ratio, draw_u_acc(ip, c, c, it));  // hmc.py:77
     if (accept) hmc_copy(ch.cur, ch.trj, c, D, DP, lane);
     __builtin_amdgcn_wave_barrier();  // (a lane reads back only what it wrote itself)
-    if (ip.samples && it >= ip.burn_in && it - ip.burn_in < ip.S)
-      for (int d = lane; d < D; d += 64)
-        ip.samples[((size_t)c * ip.S + (size_t)(it - ip.burn_in)) * D + d] = ch.cur.w[(size_t)c * DP + d];
-    if (lane == 0) {
-      ch.Hprop[c] = Hp;
-      if (accept) ch.accepted[c] += 1;
-      if (failed) ch.status[c] |= 2;
-      ch.iter[c] = it + 1;
-      ch.phase[c] = 0;
-      if (it + 1 == ip.iter_limit && ip.done_count) atomicAdd(ip.done_count, 1);
-    }
+    if (failed && lane == 0) ch.status[c] |= 2;
+    close_transition(D, DP, ch, ip, c, c, lane, it, Hp, accept);
   }
 }

@@ -1760,14 +1760,15 @@ int rmhmc_ess_dev(rmhmc_ctx* ctx, const double* samples_dev, int64_t n, int64_t 
 }
 
 // ---- plain HMC (code/hmc.py) -------------------------------------------------------------------------
-// evaluate gradient and log joint at theta0 and commit them as the current point of every chain (no run parameters, as init_chains)
-static int hmc_init_chains(rmhmc_ctx* ctx, const double* theta0_host /* [n][D] or NULL: zeros, hmc.py:27 */) {
+// evaluate gradient and log joint at theta0 and commit them as the current point of every chain (no run parameters, as init_chains);
+// allow_traj = false: by the generic launches whatever the context (fixed-metric HMC never uses the one-launch trajectory kernel)
+static int hmc_init_chains(rmhmc_ctx* ctx, const double* theta0_host /* [n][D] or NULL: zeros, hmc.py:27 */, bool allow_traj) {
   std::vector<double> th;
   if (!theta0_host) { th.assign((size_t)ctx->n * ctx->D, 0.0); theta0_host = th.data(); }
   RC(upload_vec(ctx, ctx->batch.ch.trj.w, theta0_host));
   fill_int(ctx, ctx->batch.ch.phase, 1, ctx->n);
   Group& g = ctx->batch;
-  if (ctx->hmc_traj) {
+  if (allow_traj && ctx->hmc_traj) {
     launch_hmc_traj(ctx, g, nullptr);
   } else {
     launch_rowpass<RP_G>(ctx, g, g.ch.trj.w, nullptr);
@@ -1776,19 +1777,18 @@ static int hmc_init_chains(rmhmc_ctx* ctx, const double* theta0_host /* [n][D] o
   return reset_chains(ctx);
 }
 
-int rmhmc_hmc_transition(rmhmc_ctx* ctx, double* w, const double* z, const double* u_len, const double* u_acc, int32_t L, double eps,
-                         int32_t* accepted_out, int32_t* nsteps_out, double* H_cur_out, double* H_prop_out, double* w_prop_out,
-                         double* p_prop_out) {
-  NEED_DATA(ctx);
-  if (!w || !z || !u_len || !u_acc || L < 1) return fail(ctx, RMHMC_ERR_INVALID, "hmc_transition: null pointer or L < 1");
+// one transition with the caller's randomness, plain (HMC) or with the context's mass matrix (PHMC)
+static int hmc_transition_body(rmhmc_ctx* ctx, Sampler sampler, double* w, const double* z, const double* u_len, const double* u_acc, int32_t L,
+                               double eps, int32_t* accepted_out, int32_t* nsteps_out, double* H_cur_out, double* H_prop_out,
+                               double* w_prop_out, double* p_prop_out, int32_t* status_out) {
   ctx->chains_ready = false;
-  const Run run{HMC, L, 0, eps, 0, 0, nullptr};  // (no fixed-point iterations: no K; the randomness is the caller's: no seed)
-  RC(hmc_init_chains(ctx, w));
+  const Run run{sampler, L, 0, eps, 0, 0, nullptr};  // (no fixed-point iterations: no K; the randomness is the caller's: no seed)
+  RC(hmc_init_chains(ctx, w, sampler == HMC));
   RC(upload(ctx, ctx->d_z, z, (size_t)ctx->n * ctx->D));
   RC(upload(ctx, ctx->d_ulen, u_len, ctx->n));
   RC(upload(ctx, ctx->d_uacc, u_acc, ctx->n));
   const IterBase ib{1, 0, 0, nullptr, true, false};
-  for (int s = 0; s < L; ++s) launch_hmc_global_step(ctx, run, ctx->batch, ib);
+  for (int s = 0; s < L; ++s) launch_global_step(ctx, run, ctx->batch, ib);
   std::vector<long long> acc(ctx->n);
   RC(download_vec(ctx, w, ctx->batch.ch.cur.w));
   RC(download(ctx, acc.data(), ctx->batch.ch.accepted, ctx->n));
@@ -1797,17 +1797,26 @@ int rmhmc_hmc_transition(rmhmc_ctx* ctx, double* w, const double* z, const doubl
   if (H_prop_out) RC(download(ctx, H_prop_out, ctx->batch.ch.Hprop, ctx->n));
   if (w_prop_out) RC(download_vec(ctx, w_prop_out, ctx->batch.ch.trj.w));
   if (p_prop_out) RC(download_vec(ctx, p_prop_out, ctx->batch.ch.p));
+  if (status_out) RC(download(ctx, status_out, ctx->batch.ch.status, ctx->n));
   RC(sync(ctx));
   if (accepted_out) for (int64_t c = 0; c < ctx->n; ++c) accepted_out[c] = (int32_t)acc[c];
   return RMHMC_OK;
 }
 
-// Runs the plain HMC sampler; the saved states go to the device buffer d_samples ([n][S][D]).  It leaves the accepted proposals in
-// batch.ch.accepted and, as sample_core, the post-burn-in leapfrog steps in d_steps0.
+int rmhmc_hmc_transition(rmhmc_ctx* ctx, double* w, const double* z, const double* u_len, const double* u_acc, int32_t L, double eps,
+                         int32_t* accepted_out, int32_t* nsteps_out, double* H_cur_out, double* H_prop_out, double* w_prop_out,
+                         double* p_prop_out) {
+  NEED_DATA(ctx);
+  if (!w || !z || !u_len || !u_acc || L < 1) return fail(ctx, RMHMC_ERR_INVALID, "hmc_transition: null pointer or L < 1");
+  return hmc_transition_body(ctx, HMC, w, z, u_len, u_acc, L, eps, accepted_out, nsteps_out, H_cur_out, H_prop_out, w_prop_out, p_prop_out, nullptr);
+}
+
+// Runs the HMC sampler run.sampler names (HMC or PHMC); the saved states go to the device buffer d_samples ([n][S][D]).  It leaves the
+// accepted proposals in batch.ch.accepted and, as sample_core, the post-burn-in leapfrog steps in d_steps0.
 static int hmc_sample_core(rmhmc_ctx* ctx, const Run& run, int64_t n_iter, int64_t burn_in, const double* theta0, double* d_samples, double* seconds_out) {
   const long long S = n_iter - burn_in;
   long long progress_next = ctx->progress_first;
-  RC(hmc_init_chains(ctx, theta0));
+  RC(hmc_init_chains(ctx, theta0, run.sampler == HMC));
   const IterBase ipA{burn_in + 1, burn_in, S, d_samples, false, true};
   RC(run_phase(ctx, run, ipA, 0, &progress_next, false, true));
   HIPCK(hipMemcpyAsync(ctx->d_steps0, ctx->batch.ch.steps_done, sizeof(long long) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
@@ -1876,18 +1885,6 @@ int rmhmc_phmc_set_mass(rmhmc_ctx* ctx, const double* mass) {
   RC(sync(ctx));  // (the staging vectors go out of scope)
   ctx->have_mass = true;
   return RMHMC_OK;
-}
-
-// gradient and log joint at theta0 committed as the current point of every chain, by the generic launches whatever the context
-static int phmc_init_chains(rmhmc_ctx* ctx, const double* theta0_host /* [n][D] or NULL: zeros */) {
-  std::vector<double> th;
-  if (!theta0_host) { th.assign((size_t)ctx->n * ctx->D, 0.0); theta0_host = th.data(); }
-  Group& g = ctx->batch;
-  RC(upload_vec(ctx, g.ch.trj.w, theta0_host));
-  fill_int(ctx, g.ch.phase, 1, ctx->n);
-  launch_rowpass<RP_G>(ctx, g, g.ch.trj.w, nullptr);
-  SMALL(ctx, g, "small", k_hmc_init, ctx->dd, g.ch, ctx->nsplit);
-  return reset_chains(ctx);
 }
 
 int rmhmc_phmc_mode(rmhmc_ctx* ctx, const double* w0, int32_t max_iter, double tol, double* w_out, double* G_out, int32_t* iters_out,
@@ -1962,49 +1959,7 @@ int rmhmc_phmc_transition(rmhmc_ctx* ctx, double* w, const double* z, const doub
   NEED_DATA(ctx);
   if (!w || !z || !u_len || !u_acc || L < 1) return fail(ctx, RMHMC_ERR_INVALID, "phmc_transition: null pointer or L < 1");
   if (!ctx->have_mass) return fail(ctx, RMHMC_ERR_INVALID, "phmc_transition: rmhmc_phmc_set_mass has not been called");
-  ctx->chains_ready = false;
-  const Run run{PHMC, L, 0, eps, 0, 0, nullptr};  // (the randomness is the caller's: no seed)
-  RC(phmc_init_chains(ctx, w));
-  RC(upload(ctx, ctx->d_z, z, (size_t)ctx->n * ctx->D));
-  RC(upload(ctx, ctx->d_ulen, u_len, ctx->n));
-  RC(upload(ctx, ctx->d_uacc, u_acc, ctx->n));
-  const IterBase ib{1, 0, 0, nullptr, true, false};
-  for (int s = 0; s < L; ++s) launch_phmc_global_step(ctx, run, ctx->batch, ib);
-  std::vector<long long> acc(ctx->n);
-  RC(download_vec(ctx, w, ctx->batch.ch.cur.w));
-  RC(download(ctx, acc.data(), ctx->batch.ch.accepted, ctx->n));
-  if (nsteps_out) RC(download(ctx, nsteps_out, ctx->batch.ch.nsteps_last, ctx->n));
-  if (H_cur_out) RC(download(ctx, H_cur_out, ctx->batch.ch.Hcur, ctx->n));
-  if (H_prop_out) RC(download(ctx, H_prop_out, ctx->batch.ch.Hprop, ctx->n));
-  if (w_prop_out) RC(download_vec(ctx, w_prop_out, ctx->batch.ch.trj.w));
-  if (p_prop_out) RC(download_vec(ctx, p_prop_out, ctx->batch.ch.p));
-  if (status_out) RC(download(ctx, status_out, ctx->batch.ch.status, ctx->n));
-  RC(sync(ctx));
-  if (accepted_out) for (int64_t c = 0; c < ctx->n; ++c) accepted_out[c] = (int32_t)acc[c];
-  return RMHMC_OK;
-}
-
-// Runs the sampler; the saved states go to the device buffer d_samples ([n][S][D]).  As hmc_sample_core it leaves the accepted
-// proposals in batch.ch.accepted and the post-burn-in leapfrog steps in d_steps0; there are no progress reports inside TimeTaken.
-static int phmc_sample_core(rmhmc_ctx* ctx, const Run& run, int64_t n_iter, int64_t burn_in, const double* theta0, double* d_samples, double* seconds_out) {
-  const long long S = n_iter - burn_in;
-  long long progress_next = ctx->progress_first;
-  RC(phmc_init_chains(ctx, theta0));
-  const IterBase ipA{burn_in + 1, burn_in, S, d_samples, false, true};
-  RC(run_phase(ctx, run, ipA, 0, &progress_next, false, true));
-  HIPCK(hipMemcpyAsync(ctx->d_steps0, ctx->batch.ch.steps_done, sizeof(long long) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
-  HIPCK(hipMemsetAsync(ctx->d_done, 0, sizeof(int), ctx->stream));
-  RC(sync(ctx));
-  if (ctx->progress_fn) RC(report_progress(ctx, RMHMC_EV_BURNIN_DONE, burn_in + 1));
-  const auto t0 = std::chrono::steady_clock::now();
-  if (n_iter > burn_in + 1) {
-    const IterBase ipB{n_iter, burn_in, S, d_samples, false, true};
-    RC(run_phase(ctx, run, ipB, burn_in + 1, nullptr));
-  }
-  RC(sync(ctx));
-  if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  hipLaunchKernelGGL(k_sub_ll, dim3((unsigned)((ctx->n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_steps0, ctx->batch.ch.steps_done, (size_t)ctx->n);
-  return RMHMC_OK;
+  return hmc_transition_body(ctx, PHMC, w, z, u_len, u_acc, L, eps, accepted_out, nsteps_out, H_cur_out, H_prop_out, w_prop_out, p_prop_out, status_out);
 }
 
 static int phmc_sample_body(rmhmc_ctx* ctx, const char* who, int64_t n_iter, int64_t burn_in, int32_t L, double eps, uint64_t seed,
@@ -2016,7 +1971,7 @@ static int phmc_sample_body(rmhmc_ctx* ctx, const char* who, int64_t n_iter, int
   ctx->chains_ready = false;
   const Run run{PHMC, L, 0, eps, seed, chain_offset, nullptr};  // (no fixed-point iterations: no K)
   return sample_to(ctx, n_iter - burn_in, out, [&](double* d_samples) -> int {
-    RC(phmc_sample_core(ctx, run, n_iter, burn_in, theta0, d_samples, seconds_out));
+    RC(hmc_sample_core(ctx, run, n_iter, burn_in, theta0, d_samples, seconds_out));
     RC(counter_out(ctx, out, accept_out, ctx->batch.ch.accepted));
     return counter_out(ctx, out, steps_out, ctx->d_steps0);
   });
