@@ -185,6 +185,37 @@ PHMC_SIGNATURES = {
 }
 PHMC_COUNTERS = (("accepted", False), ("leapfrog_steps", False))
 
+# include/rmhmc_adapt.h: the warm-up of the fixed-metric HMC sampler (pooled covariance on the device, regularised mass, dual
+# averaging of the step size), HIP library only as well
+ADAPT_SIGNATURES = {
+    "rmhmc_cov_partial_dev": (C.c_int, [C.c_void_p, _vp, C.c_int64, C.c_int64, C.c_int32, _vp]),
+    "rmhmc_cov_finish": (C.c_int, [_dpp, C.c_int32, C.c_int32, _dp, _dp, _dp, _lp]),
+    "rmhmc_adapt_mass": (C.c_int, [_dp, C.c_int64, C.c_int32, _dp]),
+    "rmhmc_adapt_init": (C.c_int, [_dp, C.c_double, C.c_double]),
+    "rmhmc_adapt_step": (C.c_int, [_dp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _dp, _dp]),
+    "rmhmc_phmc_warmup": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint64,
+                                    C.c_int64, C.c_int32, _lp, _ip, C.c_int64, _dp, _dp, _dp, _dp, _dp, _ip, _dp]),
+}
+COV_MAX_P = 256      # widest sample row of rmhmc_cov_partial_dev
+COV_ROWS = 256       # smallest row block of its kernels (csrc/adapt.h)
+
+
+def adapt_schedule(warmup, window=25):
+    """(win_len, win_kind) of a warm-up of `warmup` iterations in W = warmup // window windows of `window` iterations (what is left over
+    is not run): the first max(1, round(0.15 W)) and the last max(1, round(0.1 W)) windows adapt the step size alone (kind 0), those
+    between them the step size and the mass (kind 1); halves round up (integer arithmetic, as adapt_schedule of csrc/adapt.h).
+    ValueError for W < 3."""
+    warmup, window = int(warmup), int(window)
+    if window < 1:
+        raise ValueError("window must be >= 1")
+    W = warmup // window
+    if W < 3:
+        raise ValueError("a warm-up needs at least 3 windows: warmup >= 3 * window")
+    head = max(1, (15 * W + 50) // 100)
+    tail = max(1, (10 * W + 50) // 100)
+    kind = np.array([0 if (w < head or w >= W - tail) else 1 for w in range(W)], dtype=np.int32)
+    return np.full(W, window, dtype=np.int64), kind
+
 
 def diag_lags(S, max_lag=None):
     """(H, T) of a diagnostics call on S samples per chain: H = S // 2 rows per half chain, T = max_lag + 1 lags; max_lag None or 0:
@@ -268,6 +299,12 @@ class RmhmcLib:
         self.has_phmc = all(hasattr(self.lib, name) for name in PHMC_SIGNATURES)
         if self.has_phmc:
             for name, (res, args) in PHMC_SIGNATURES.items():
+                fn = getattr(self.lib, name)
+                fn.restype = res
+                fn.argtypes = args
+        self.has_adapt = all(hasattr(self.lib, name) for name in ADAPT_SIGNATURES)
+        if self.has_adapt:
+            for name, (res, args) in ADAPT_SIGNATURES.items():
                 fn = getattr(self.lib, name)
                 fn.restype = res
                 fn.argtypes = args
@@ -556,6 +593,61 @@ class Context:
         self._need_out()
         return self._call_sample_to("rmhmc_phmc_sample_to", PHMC_COUNTERS, (int(L), float(eps)), n_iter, burn_in, where, device, samples,
                                     stats, run_mean, seed, chain_offset, theta0)
+
+    # ---- warm-up of the fixed-metric HMC sampler (include/rmhmc_adapt.h) -----------
+    def _need_adapt(self):
+        if not self.rl.has_adapt:
+            raise RmhmcError(-4, "%s does not export the warm-up of the fixed-metric HMC sampler (include/rmhmc_adapt.h)" % self.rl.path)
+
+    def cov_partial(self, samples):
+        """The mergeable partial [(2 + P), P] (include/rmhmc_adapt.h) of a float64 torch tensor [n][S][P] already on the context's GPU,
+        reduced there.  torch's current stream is synchronised first, as in ess_dev."""
+        import torch
+        self._need_adapt()
+        if self.rl.on_gpu and not samples.is_cuda:
+            raise ValueError("cov_partial: a tensor on the context's GPU is required")
+        x = samples.contiguous()
+        if x.dtype != torch.float64 or x.dim() != 3:
+            raise ValueError("cov_partial: float64 tensor [n][S][P] required")
+        n, S, P = x.shape
+        part = torch.empty((2 + P, P), dtype=torch.float64, device=x.device)
+        if x.is_cuda:
+            torch.cuda.current_stream(x.device).synchronize()
+        self._ck(self.lib.rmhmc_cov_partial_dev(self._h, x.data_ptr(), n, S, P, part.data_ptr()))
+        return part
+
+    def pooled_cov(self, samples):
+        """pooled mean and covariance of the rows of samples [n][S][P] on the context's GPU (rows with a non-finite entry left out):
+        dict(mean [P], cov [P][P], rows_used: host; partial: the device tensor of cov_partial)"""
+        part = self.cov_partial(samples)
+        out = cov_finish([part], lib=self.rl)
+        return dict(mean=out["mean"], cov=out["cov"], rows_used=out["rows_used"], partial=part)
+
+    def phmc_warmup(self, win_len, win_kind, L=6, eps0=0.5, *, min_rows=None, delta=0.8, gamma=0.05, t0=10.0, kappa=0.75, seed=0,
+                    chain_offset=0, theta0=None):
+        """The windowed warm-up of phmc_sample_to (rmhmc_phmc_warmup) from the context's mass and eps0: window w runs win_len[w]
+        iterations and adapts the step size (win_kind[w] = 0) or the step size and then the mass (1; adapt_schedule builds the usual
+        schedule).  min_rows: pooled rows a mass update needs, default 10 D.  Returns dict(step_size, mass [D][D] or None when no
+        update happened, theta [n][D] the last positions, eps_trace, accept_trace, mass_updated [W], seconds).  The context is left
+        with the adapted mass."""
+        self._need_adapt()
+        n, D = self.n, self.D
+        wl = np.ascontiguousarray(win_len, dtype=np.int64).reshape(-1)
+        wk = np.ascontiguousarray(win_kind, dtype=np.int32).reshape(-1)
+        if wl.shape != wk.shape or wl.size < 1:
+            raise ValueError("phmc_warmup: win_len and win_kind of one length W >= 1 required")
+        W = wl.size
+        min_rows = 10 * D if min_rows is None else int(min_rows)
+        th = None if theta0 is None else _f64(np.broadcast_to(theta0, (n, D)))
+        eps = C.c_double(0.0); secs = C.c_double(0.0)
+        mass = np.empty((D, D)); theta = np.empty((n, D))
+        eps_trace = np.empty(W); acc_trace = np.empty(W); upd = np.zeros(W, dtype=np.int32)
+        self._ck(self.lib.rmhmc_phmc_warmup(self._h, _ptr(th), int(L), float(eps0), float(delta), float(gamma), float(t0), float(kappa),
+                                            int(seed) % 2 ** 64, int(chain_offset), W, _ptr(wl, _lp), _ptr(wk, _ip), min_rows,
+                                            C.cast(C.byref(eps), _dp), _ptr(mass), _ptr(theta), _ptr(eps_trace), _ptr(acc_trace),
+                                            _ptr(upd, _ip), C.cast(C.byref(secs), _dp)))
+        return dict(step_size=eps.value, mass=mass if (upd == 1).any() else None, theta=theta, eps_trace=eps_trace,
+                    accept_trace=acc_trace, mass_updated=upd, seconds=secs.value)
 
     # ---- adaptive Metropolis (code/metropolis.py, include/rmhmc_amh.h) -----------
     def _need_amh(self):
@@ -957,6 +1049,66 @@ def diag_info(st, diagnostics):
 def diag_identity(T, P):
     """the partial of no series at all (an empty shard): the identity of the merge"""
     return np.zeros((4 + int(T), int(P)))
+
+
+def _adapt_lib(lib):
+    lib = lib if lib is not None else load_hip_library()
+    if not lib.has_adapt:
+        raise RmhmcError(-4, "%s does not export the warm-up of the fixed-metric HMC sampler (include/rmhmc_adapt.h)" % lib.path)
+    return lib
+
+
+def cov_finish(partials, lib=None):
+    """rmhmc_cov_finish (include/rmhmc_adapt.h): the partials ([(2 + P), P] each: torch tensors on any device or NumPy arrays) merged in
+    the order given and finished on the host.  Returns dict(mean [P], cov [P][P] (NaN for fewer than 2 rows), rows_used, merged)."""
+    lib = _adapt_lib(lib)
+    parts = [_f64(p if isinstance(p, np.ndarray) else p.detach().cpu().numpy()) for p in partials]
+    if not parts or parts[0].ndim != 2 or parts[0].shape[0] != parts[0].shape[1] + 2 or any(p.shape != parts[0].shape for p in parts):
+        raise ValueError("cov_finish: partials of one shape [(2 + P), P] required")
+    P = parts[0].shape[1]
+    ptrs = (_dp * len(parts))(*[_ptr(p) for p in parts])
+    merged = np.empty((2 + P, P)); mean = np.empty(P); cov = np.empty((P, P)); used = C.c_int64(0)
+    rc = lib.lib.rmhmc_cov_finish(ptrs, len(parts), P, _ptr(merged), _ptr(mean), _ptr(cov), C.cast(C.byref(used), _lp))
+    if rc != 0:
+        raise RmhmcError(rc, lib.lib.rmhmc_last_error(None).decode())
+    return dict(mean=mean, cov=cov, rows_used=used.value, merged=merged)
+
+
+def adapt_mass(cov, rows_used, lib=None):
+    """rmhmc_adapt_mass: the inverse of the shrunk covariance m / (m + 5) cov + 1e-3 * 5 / (m + 5) I, or None where the library refuses
+    it (fewer than 2 rows, not finite, not positive definite): the caller keeps its mass"""
+    lib = _adapt_lib(lib)
+    cov = _f64(cov)
+    if cov.ndim != 2 or cov.shape[0] != cov.shape[1]:
+        raise ValueError("adapt_mass: a square covariance required")
+    mass = np.empty_like(cov)
+    rc = lib.lib.rmhmc_adapt_mass(_ptr(cov), int(rows_used), cov.shape[0], _ptr(mass))
+    return mass if rc == 0 else None
+
+
+def adapt_init(eps, factor=10.0, lib=None):
+    """rmhmc_adapt_init: the dual-averaging state (t, Hbar, log epsbar, mu = log(factor eps)) of a (re)start at step size eps; the
+    warm-up starts with factor 10 and restarts with factor 1 after a mass update"""
+    lib = _adapt_lib(lib)
+    state = np.empty(4)
+    rc = lib.lib.rmhmc_adapt_init(_ptr(state), float(eps), float(factor))
+    if rc != 0:
+        raise RmhmcError(rc, lib.lib.rmhmc_last_error(None).decode())
+    return state
+
+
+def adapt_step(state, accept, delta=0.8, gamma=0.05, t0=10.0, kappa=0.75, lib=None):
+    """rmhmc_adapt_step: one dual-averaging update of `state` (a float64 array of 4, updated in place) with the acceptance statistic
+    of a window.  Returns (eps_next, eps_bar)."""
+    lib = _adapt_lib(lib)
+    if not (isinstance(state, np.ndarray) and state.dtype == np.float64 and state.shape == (4,) and state.flags.c_contiguous):
+        raise ValueError("adapt_step: the state is a contiguous float64 array of 4")
+    e = C.c_double(0.0); eb = C.c_double(0.0)
+    rc = lib.lib.rmhmc_adapt_step(_ptr(state), float(accept), float(delta), float(gamma), float(t0), float(kappa),
+                                  C.cast(C.byref(e), _dp), C.cast(C.byref(eb), _dp))
+    if rc != 0:
+        raise RmhmcError(rc, lib.lib.rmhmc_last_error(None).decode())
+    return e.value, eb.value
 
 
 _hip = None

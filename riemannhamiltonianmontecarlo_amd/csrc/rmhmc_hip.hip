@@ -12,6 +12,7 @@
 #include "../../include/rmhmc_out.h"
 #include "../../include/rmhmc_diag.h"
 #include "../../include/rmhmc_phmc.h"
+#include "../../include/rmhmc_adapt.h"
 #include "plan.h"
 #include "mass.h"
 #include "kernels.hip.h"
@@ -25,6 +26,7 @@
 #include "output.hip.h"
 #include "diag.hip.h"
 #include "phmc.hip.h"
+#include "adapt.hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -2713,6 +2715,152 @@ int rmhmc_diag_finish(const double* const* partials, int32_t k, int64_t H, int64
   const int rc = diag_finish(partials, k, H, T, P, merged, rhat, ess, pairs, chains_used);
   return rc == RMHMC_OK ? rc : fail(nullptr, rc, rc == RMHMC_ERR_NOMEM ? "diag_finish: out of memory"
                                                                        : "diag_finish: need k >= 1, H >= 2, 2 <= T <= H, P >= 1 and no NULL partial");
+}
+
+}  // extern "C"
+
+// ---- warm-up of the fixed-metric HMC sampler: pooled covariance, regularised mass, dual averaging (include/rmhmc_adapt.h, adapt.h,
+// adapt.hip.h) ------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// samples [N][P] -> the partial [(2 + P)][P], all in device memory; queued on the stream, its scratch buffer returned for the caller to
+// free once the stream is idle
+int launch_cov(rmhmc_ctx* ctx, const double* d_x, size_t N, int P, double* d_partial, void** d_scratch) {
+  int64_t nb1, rpb1, nb2, rpb2;
+  cov_plan_sums((int64_t)N, &nb1, &rpb1);
+  cov_plan((int64_t)N, P, &nb2, &rpb2);
+  const size_t p = (size_t)P, nt = (p + 15) / 16;
+  const size_t doubles = (size_t)nb1 * 3 * p + 2 * p + (size_t)nb2 * p * p;
+  HIPCK(hipMalloc(d_scratch, sizeof(double) * doubles + N));
+  double* blk = (double*)*d_scratch;
+  double* ctr = blk + (size_t)nb1 * 3 * p;
+  double* scr = ctr + 2 * p;
+  unsigned char* valid = (unsigned char*)(scr + (size_t)nb2 * p * p);
+  launch(ctx, "cov", [&](hipStream_t st) {
+    hipLaunchKernelGGL(k_cov_sums, dim3((unsigned)nb1), dim3(256), 0, st, d_x, N, P, (size_t)rpb1, valid, blk);
+    hipLaunchKernelGGL(k_cov_mean, dim3(1), dim3(256), 0, st, blk, (size_t)nb1, P, d_partial, ctr);
+    hipLaunchKernelGGL(k_cov_xtx, dim3((unsigned)(nt * (nt + 1) / 2), (unsigned)nb2), dim3(64), 0, st, d_x, N, P, (size_t)rpb2, valid, ctr, scr);
+    hipLaunchKernelGGL(k_cov_reduce, dim3((unsigned)((p * p + 255) / 256)), dim3(256), 0, st, scr, (size_t)nb2, P, d_partial);
+  });
+  HIPCK(hipGetLastError());
+  return RMHMC_OK;
+}
+
+int cov_partial(rmhmc_ctx* ctx, const double* d_x, size_t N, int P, double* d_partial) {
+  void* d_scratch = nullptr;
+  const int rc = launch_cov(ctx, d_x, N, P, d_partial, &d_scratch);
+  const int rs = sync(ctx);
+  if (d_scratch) (void)hipFree(d_scratch);
+  return rc != RMHMC_OK ? rc : rs;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rmhmc_cov_partial_dev(rmhmc_ctx* ctx, const double* samples_dev, int64_t n, int64_t S, int32_t P, double* partial_dev) {
+  if (!ctx || !samples_dev || !partial_dev || n < 1 || S < 1 || P < 1 || n > INT64_MAX / S)
+    return fail(ctx, RMHMC_ERR_INVALID, "cov_partial_dev: need samples, a partial, n >= 1, S >= 1, P >= 1");
+  if (P > COV_MAX_P) return fail(ctx, RMHMC_ERR_UNSUPPORTED, "cov_partial_dev: P <= 256");
+  HIPCK(hipSetDevice(ctx->device));
+  return cov_partial(ctx, samples_dev, (size_t)n * (size_t)S, P, partial_dev);
+}
+
+int rmhmc_cov_finish(const double* const* partials, int32_t k, int32_t P, double* merged, double* mean, double* cov, int64_t* rows_used) {
+  const int rc = cov_finish(partials, k, P, merged, mean, cov, rows_used);
+  return rc == RMHMC_OK ? rc : fail(nullptr, rc, rc == RMHMC_ERR_NOMEM ? "cov_finish: out of memory" : "cov_finish: need k >= 1, P >= 1 and no NULL partial");
+}
+
+int rmhmc_adapt_mass(const double* cov, int64_t m, int32_t P, double* mass_out) {
+  const char* why = "";
+  const int rc = adapt_mass(cov, m, P, mass_out, &why);
+  return rc == RMHMC_OK ? rc : fail(nullptr, rc, why);
+}
+
+int rmhmc_adapt_init(double state[4], double eps, double factor) {
+  const int rc = adapt_init(state, eps, factor);
+  return rc == RMHMC_OK ? rc : fail(nullptr, rc, "adapt_init: need a state, a finite step size > 0 and a finite factor > 0");
+}
+
+int rmhmc_adapt_step(double state[4], double accept, double delta, double gamma, double t0, double kappa, double* eps_next, double* eps_bar) {
+  const int rc = adapt_step(state, accept, delta, gamma, t0, kappa, eps_next, eps_bar);
+  return rc == RMHMC_OK ? rc : fail(nullptr, rc, "adapt_step: need a state, a finite acceptance statistic and a step size that stays finite and > 0");
+}
+
+int rmhmc_phmc_warmup(rmhmc_ctx* ctx, const double* theta0, int32_t L, double eps0, double delta, double gamma, double t0, double kappa,
+                      uint64_t seed, int64_t chain_offset, int32_t W, const int64_t* win_len, const int32_t* win_kind, int64_t min_rows,
+                      double* eps_out, double* mass_out, double* theta_out, double* eps_trace, double* accept_trace, int32_t* mass_updated,
+                      double* seconds_out) {
+  NEED_DATA(ctx);
+  const auto t_start = std::chrono::steady_clock::now();
+  if (!win_len || !win_kind || W < 1 || L < 1 || min_rows < 1 || !std::isfinite(eps0) || !(eps0 > 0.0))
+    return fail(ctx, RMHMC_ERR_INVALID, "phmc_warmup: need a schedule of W >= 1 windows, L >= 1, min_rows >= 1 and a finite eps0 > 0");
+  int64_t Kmax = 0;
+  for (int32_t w = 0; w < W; ++w) {
+    if (win_len[w] < 1 || (win_kind[w] != 0 && win_kind[w] != 1))
+      return fail(ctx, RMHMC_ERR_INVALID, "phmc_warmup: every window needs a length >= 1 and a kind 0 or 1");
+    Kmax = std::max<int64_t>(Kmax, win_len[w]);
+  }
+  if (!ctx->have_mass) return fail(ctx, RMHMC_ERR_INVALID, "phmc_warmup: rmhmc_phmc_set_mass has not been called");
+  if (ctx->D > COV_MAX_P) return fail(ctx, RMHMC_ERR_UNSUPPORTED, "phmc_warmup: D <= 256");
+  const size_t n = ctx->n, D = ctx->D, plen = (2 + D) * D;
+  double state[4];
+  RC(adapt_init(state, eps0, ADAPT_FACTOR_START) == RMHMC_OK ? RMHMC_OK : fail(ctx, RMHMC_ERR_INVALID, "phmc_warmup: bad eps0"));
+  std::vector<double> theta, running(plen, 0.0), wpart(plen), merged(plen), cov(D * D), mass(D * D), mass_last(D * D, NAN);
+  std::vector<long long> acc(n);
+  if (theta0) theta.assign(theta0, theta0 + n * D);
+  double eps = eps0, eps_bar = eps0;
+  double *d_win = nullptr, *d_part = nullptr;  // the samples of one window [n][K][D]; its partial
+  HIPCK(hipMalloc((void**)&d_win, sizeof(double) * n * (size_t)Kmax * D));
+  const int rc = [&]() -> int {
+    HIPCK(hipMalloc((void**)&d_part, sizeof(double) * plen));
+    for (int32_t w = 0; w < W; ++w) {
+      const int64_t K = win_len[w];
+      ctx->chains_ready = false;
+      const Run run{PHMC, L, 0, eps, seed + 1 + (uint64_t)w, chain_offset, nullptr};
+      RC(hmc_sample_core(ctx, run, K, 0, theta.empty() ? nullptr : theta.data(), d_win, nullptr));
+      RC(download(ctx, acc.data(), ctx->batch.ch.accepted, n));
+      theta.resize(n * D);
+      HIPCK(hipMemcpy2DAsync(theta.data(), D * sizeof(double), d_win + (size_t)(K - 1) * D, (size_t)K * D * sizeof(double), D * sizeof(double), n,
+                             hipMemcpyDeviceToHost, ctx->stream));
+      RC(sync(ctx));
+      const double a = adapt_accept((const int64_t*)acc.data(), (int64_t)n, K);
+      if (eps_trace) eps_trace[w] = eps;
+      if (accept_trace) accept_trace[w] = a;
+      if (mass_updated) mass_updated[w] = 0;
+      double eps_next = eps;
+      if (adapt_step(state, a, delta, gamma, t0, kappa, &eps_next, &eps_bar) != RMHMC_OK)
+        return fail(ctx, RMHMC_ERR_INVALID, "phmc_warmup: the step size has left the finite positive numbers (dual averaging constants?)");
+      eps = eps_next;
+      if (win_kind[w] != 1) continue;
+      RC(cov_partial(ctx, d_win, n * (size_t)K, (int)D, d_part));
+      RC(download(ctx, wpart.data(), d_part, plen));
+      RC(sync(ctx));
+      const double* const two[2] = {running.data(), wpart.data()};
+      int64_t m = 0;
+      RC(cov_finish(two, 2, (int32_t)D, merged.data(), nullptr, cov.data(), &m));
+      running = merged;
+      if (m < min_rows) continue;
+      const char* why = "";
+      if (adapt_mass(cov.data(), m, (int32_t)D, mass.data(), &why) == RMHMC_OK && rmhmc_phmc_set_mass(ctx, mass.data()) == RMHMC_OK) {
+        mass_last = mass;
+        std::fill(running.begin(), running.end(), 0.0);
+        (void)adapt_init(state, eps, ADAPT_FACTOR_RESTART);
+        if (mass_updated) mass_updated[w] = 1;
+      } else {  // refused: the previous mass stays
+        if (mass_updated) mass_updated[w] = -1;
+      }
+    }
+    return RMHMC_OK;
+  }();
+  (void)hipFree(d_win);
+  if (d_part) (void)hipFree(d_part);
+  if (rc != RMHMC_OK) return rc;
+  if (eps_out) *eps_out = eps_bar;
+  if (mass_out) std::copy(mass_last.begin(), mass_last.end(), mass_out);
+  if (theta_out) std::copy(theta.begin(), theta.end(), theta_out);
+  if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+  return RMHMC_OK;
 }
 
 }  // extern "C"
