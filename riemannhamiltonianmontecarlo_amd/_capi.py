@@ -6,6 +6,7 @@ extension is missing or cannot run — there is no CPU fallback.  The test-suite
 binds the CPU oracle with the same class to diff results.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -199,6 +200,58 @@ ADAPT_SIGNATURES = {
 COV_MAX_P = 256      # widest sample row of rmhmc_cov_partial_dev
 COV_ROWS = 256       # smallest row block of its kernels (csrc/adapt.h)
 
+# include/rmhmc_ais.h: the log marginal likelihood by annealed importance sampling with tempered fixed-metric HMC, HIP library only as
+# well.  Like PHMC it has methods of its own (Context.tphmc_sample_to, Context.ais_run) and no place in the sampler tables.
+AIS_SIGNATURES = {
+    "rmhmc_tphmc_transition": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp, C.c_int32, C.c_double, _ip, _ip, _dp, _dp, _dp, _dp, _ip, C.c_double,
+                                         _dp, _dp]),
+    "rmhmc_tphmc_sample_to": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_uint64, C.c_int64, _dp, _op, _vp, _vp,
+                                        _dp, C.c_double, _dp, _dp]),
+    "rmhmc_ais_prior": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, _dp]),
+    "rmhmc_ais_partial_dev": (C.c_int, [C.c_void_p, _vp, C.c_int64, _vp]),
+    "rmhmc_ais_finish": (C.c_int, [_dpp, C.c_int32, _dp, _dp, _dp, _dp, _lp, _lp]),
+    "rmhmc_ais_run": (C.c_int, [C.c_void_p, _dp, C.c_double, C.c_int32, _dp, _lp, _ip, _dp, C.c_int32, C.c_double, C.c_uint64, C.c_int64,
+                                _dp, _dp, _dp, _dp, _dp]),
+}
+AIS_PRIOR_ITER = 0xFFFFFFFF   # iteration counter of the prior draws (RMHMC_AIS_PRIOR_ITER)
+AIS_KEYS = ("log_mean_w", "se", "weight_ess", "m", "n_nan")   # what ais_finish returns besides the merged partial
+
+
+def ais_schedule(n_temps, ladder="power4", mass_every=1, iters_per_temp=1):
+    """(beta [T], stage_len [T], stage_mass [T]) of an annealing run of T = n_temps stages (csrc/ais.h): ladder "power<q>" is
+    beta_k = ((k + 1) / T)^q, "log<b>" the log-spaced beta_k = b^(1 - (k + 1) / T) with 0 < b < 1 ("log" alone: b = 1e-6); the last
+    beta is exactly 1.  stage_mass: 1 every mass_every stages and in the first and the last; mass_every None: no stage installs a mass
+    (stage_mass is None).  ValueError for T < 1, an unknown ladder, mass_every < 1 or iters_per_temp < 1."""
+    T, K = int(n_temps), int(iters_per_temp)
+    if T != n_temps or T < 1:
+        raise ValueError("n_temps must be a number of stages >= 1")
+    if K != iters_per_temp or K < 1:
+        raise ValueError("iters_per_temp must be >= 1")
+    if not isinstance(ladder, str) or not (ladder.startswith("power") or ladder.startswith("log")):
+        raise ValueError('ladder must be "power<q>" or "log<beta_min>"')
+    frac = (np.arange(T, dtype=np.float64) + 1.0) / float(T)
+    try:
+        if ladder.startswith("power"):
+            q = float(ladder[5:])
+            if not (np.isfinite(q) and q > 0.0):
+                raise ValueError
+            beta = np.array([math.pow(f, q) for f in frac])
+        else:
+            b = float(ladder[3:]) if len(ladder) > 3 else 1e-6
+            if not 0.0 < b < 1.0:
+                raise ValueError
+            beta = np.array([math.exp(math.log(b) * (1.0 - f)) for f in frac])
+    except ValueError:
+        raise ValueError('ladder must be "power<q>" with q > 0 or "log<beta_min>" with 0 < beta_min < 1') from None
+    beta[-1] = 1.0
+    stage_mass = None
+    if mass_every is not None:
+        if int(mass_every) != mass_every or mass_every < 1:
+            raise ValueError("mass_every must be None or a number of stages >= 1")
+        k = np.arange(T)
+        stage_mass = ((k % int(mass_every) == 0) | (k == T - 1)).astype(np.int32)
+    return beta, np.full(T, K, dtype=np.int64), stage_mass
+
 
 def adapt_schedule(warmup, window=25):
     """(win_len, win_kind) of a warm-up of `warmup` iterations in W = warmup // window windows of `window` iterations (what is left over
@@ -305,6 +358,12 @@ class RmhmcLib:
         self.has_adapt = all(hasattr(self.lib, name) for name in ADAPT_SIGNATURES)
         if self.has_adapt:
             for name, (res, args) in ADAPT_SIGNATURES.items():
+                fn = getattr(self.lib, name)
+                fn.restype = res
+                fn.argtypes = args
+        self.has_ais = all(hasattr(self.lib, name) for name in AIS_SIGNATURES)
+        if self.has_ais:
+            for name, (res, args) in AIS_SIGNATURES.items():
                 fn = getattr(self.lib, name)
                 fn.restype = res
                 fn.argtypes = args
@@ -649,6 +708,82 @@ class Context:
         return dict(step_size=eps.value, mass=mass if (upd == 1).any() else None, theta=theta, eps_trace=eps_trace,
                     accept_trace=acc_trace, mass_updated=upd, seconds=secs.value)
 
+    # ---- annealed importance sampling with tempered fixed-metric HMC (include/rmhmc_ais.h) -----------
+    def _need_ais(self):
+        if not self.rl.has_ais:
+            raise RmhmcError(-4, "%s does not export annealed importance sampling (include/rmhmc_ais.h)" % self.rl.path)
+
+    def tphmc_transition(self, w, z, u_len, u_acc, L=6, eps=0.5, beta=1.0):
+        """phmc_transition on the target tempered by beta; the dict gains loglik0 (at the start) and loglik (at the returned w)"""
+        self._need_ais()
+        n, D = self.n, self.D
+        w = _f64(w, (n, D)).copy()
+        z = _f64(z, (n, D)); u_len = _f64(u_len, (n,)); u_acc = _f64(u_acc, (n,))
+        acc = np.zeros(n, dtype=np.int32); ns = np.zeros(n, dtype=np.int32); status = np.zeros(n, dtype=np.int32)
+        Hc = np.empty(n); Hp = np.empty(n); wp = np.empty((n, D)); pp = np.empty((n, D)); ll0 = np.empty(n); ll = np.empty(n)
+        self._ck(self.lib.rmhmc_tphmc_transition(self._h, _ptr(w), _ptr(z), _ptr(u_len), _ptr(u_acc), int(L), float(eps), _ptr(acc, _ip),
+                                                 _ptr(ns, _ip), _ptr(Hc), _ptr(Hp), _ptr(wp), _ptr(pp), _ptr(status, _ip), float(beta),
+                                                 _ptr(ll0), _ptr(ll)))
+        return dict(w=w, accepted=acc, nsteps=ns, H_cur=Hc, H_prop=Hp, w_prop=wp, p_prop=pp, status=status, loglik0=ll0, loglik=ll)
+
+    def tphmc_sample_to(self, n_iter, burn_in, L=6, eps=0.5, beta=1.0, *, where="host", device=None, samples=False, stats=False,
+                        run_mean=False, seed=0, chain_offset=0, theta0=None):
+        """phmc_sample_to on the target tempered by beta (the power posterior p(t|w)^beta p(w)); the result gains loglik0 [n] (the
+        log-likelihood at theta0) and loglik [n] (at the last state), host arrays whatever `where` says"""
+        self._need_ais()
+        self._need_out()
+        ll0 = np.empty(self.n); ll = np.empty(self.n)
+        res = self._call_sample_to("rmhmc_tphmc_sample_to", PHMC_COUNTERS, (int(L), float(eps)), n_iter, burn_in, where, device, samples,
+                                   stats, run_mean, seed, chain_offset, theta0, back=(float(beta), _ptr(ll0), _ptr(ll)))
+        res["loglik0"], res["loglik"] = ll0, ll
+        return res
+
+    def ais_prior(self, seed=0, chain_offset=0):
+        """exact draws from the prior N(0, alpha I), [n][D]: the start of an annealing run"""
+        self._need_ais()
+        th = np.empty((self.n, self.D))
+        self._ck(self.lib.rmhmc_ais_prior(self._h, int(seed) % 2 ** 64, int(chain_offset), _ptr(th)))
+        return th
+
+    def ais_partial(self, logw):
+        """The mergeable partial [5] = (m, n_nan, max, S1, S2) (include/rmhmc_ais.h) of a float64 torch tensor [n] of log weights already
+        on the context's GPU, reduced there.  torch's current stream is synchronised first, as in ess_dev."""
+        import torch
+        self._need_ais()
+        if self.rl.on_gpu and not logw.is_cuda:
+            raise ValueError("ais_partial: a tensor on the context's GPU is required")
+        x = logw.contiguous()
+        if x.dtype != torch.float64 or x.dim() != 1 or x.numel() < 1:
+            raise ValueError("ais_partial: float64 tensor [n], n >= 1, required")
+        part = torch.empty(5, dtype=torch.float64, device=x.device)
+        if x.is_cuda:
+            torch.cuda.current_stream(x.device).synchronize()
+        self._ck(self.lib.rmhmc_ais_partial_dev(self._h, x.data_ptr(), x.numel(), part.data_ptr()))
+        return part
+
+    def ais_run(self, beta, stage_len, stage_mass=None, H_lik=None, L=6, eps=0.5, *, beta0=0.0, seed=0, chain_offset=0, theta0=None):
+        """rmhmc_ais_run: stage k installs the mass beta[k] H_lik + I / alpha where stage_mass[k] is 1, runs stage_len[k] tempered
+        iterations at beta[k] from the last positions and adds (beta[k] - beta[k - 1]) loglik0 to logw; theta0 None: the chains start
+        from the prior (beta0 must be 0).  ais_schedule builds the usual (beta, stage_len, stage_mass).  Returns dict(logw [n], theta
+        [n][D] the last positions, accept_trace [T], partial [5], seconds, and the AIS_KEYS of ais_finish on the partial).  The context
+        is left with the last mass installed."""
+        self._need_ais()
+        n, D = self.n, self.D
+        b = _f64(beta).reshape(-1)
+        sl = np.ascontiguousarray(stage_len, dtype=np.int64).reshape(-1)
+        sm = None if stage_mass is None else np.ascontiguousarray(stage_mass, dtype=np.int32).reshape(-1)
+        if b.size < 1 or sl.shape != b.shape or (sm is not None and sm.shape != b.shape):
+            raise ValueError("ais_run: beta, stage_len and stage_mass of one length T >= 1 required")
+        H = None if H_lik is None else _f64(H_lik, (D, D))
+        th = None if theta0 is None else _f64(np.broadcast_to(theta0, (n, D)))
+        logw = np.empty(n); theta = np.empty((n, D)); trace = np.empty(b.size); part = np.empty(5); secs = C.c_double(0.0)
+        self._ck(self.lib.rmhmc_ais_run(self._h, _ptr(th), float(beta0), b.size, _ptr(b), _ptr(sl, _lp), _ptr(sm, _ip), _ptr(H), int(L),
+                                        float(eps), int(seed) % 2 ** 64, int(chain_offset), _ptr(logw), _ptr(theta), _ptr(trace),
+                                        _ptr(part), C.cast(C.byref(secs), _dp)))
+        out = dict(logw=logw, theta=theta, accept_trace=trace, partial=part, seconds=secs.value)
+        out.update(ais_finish([part], lib=self.rl))
+        return out
+
     # ---- adaptive Metropolis (code/metropolis.py, include/rmhmc_amh.h) -----------
     def _need_amh(self):
         if not self.rl.has_amh:
@@ -795,9 +930,9 @@ class Context:
                                     theta0, has_theta0=sampler != "gibbs")
 
     def _call_sample_to(self, name, counters, front, n_iter, burn_in, where, device, samples, stats, run_mean, seed, chain_offset, theta0,
-                        has_theta0=True):
+                        has_theta0=True, back=()):
         """the descriptor, the buffers and the call of one <sampler>_sample_to entry point: `front` its run arguments between burn_in
-        and seed, `counters` as in SAMPLERS_TO"""
+        and seed, `back` those after seconds_out, `counters` as in SAMPLERS_TO"""
         n, D = self.n, self.D
         n_iter, burn_in = int(n_iter), int(burn_in)
         S = n_iter - burn_in
@@ -836,7 +971,7 @@ class Context:
         secs = C.c_double(0.0)
         if dev and device.type == "cuda":
             torch.cuda.current_stream(device).synchronize()   # nothing of torch's is pending on the buffers the library is handed
-        self._ck(getattr(self.lib, name)(self._h, n_iter, burn_in, *front, *tail, C.byref(o), *cptr, C.cast(C.byref(secs), _dp)))
+        self._ck(getattr(self.lib, name)(self._h, n_iter, burn_in, *front, *tail, C.byref(o), *cptr, C.cast(C.byref(secs), _dp), *back))
         res["seconds"] = secs.value
         return res
 
@@ -1109,6 +1244,24 @@ def adapt_step(state, accept, delta=0.8, gamma=0.05, t0=10.0, kappa=0.75, lib=No
     if rc != 0:
         raise RmhmcError(rc, lib.lib.rmhmc_last_error(None).decode())
     return e.value, eb.value
+
+
+def ais_finish(partials, lib=None):
+    """rmhmc_ais_finish (include/rmhmc_ais.h): the weight partials ([5] each: torch tensors on any device or NumPy arrays) merged in the
+    order given and finished on the host.  Returns dict(log_mean_w, se (NaN for m < 2), weight_ess, m, n_nan, merged [5])."""
+    lib = lib if lib is not None else load_hip_library()
+    if not lib.has_ais:
+        raise RmhmcError(-4, "%s does not export annealed importance sampling (include/rmhmc_ais.h)" % lib.path)
+    parts = [_f64(p if isinstance(p, np.ndarray) else p.detach().cpu().numpy()) for p in partials]
+    if not parts or any(p.shape != (5,) for p in parts):
+        raise ValueError("ais_finish: partials of shape [5] required")
+    ptrs = (_dp * len(parts))(*[_ptr(p) for p in parts])
+    merged = np.empty(5); lm = C.c_double(0.0); se = C.c_double(0.0); ess = C.c_double(0.0); m = C.c_int64(0); nn = C.c_int64(0)
+    rc = lib.lib.rmhmc_ais_finish(ptrs, len(parts), _ptr(merged), C.cast(C.byref(lm), _dp), C.cast(C.byref(se), _dp),
+                                  C.cast(C.byref(ess), _dp), C.cast(C.byref(m), _lp), C.cast(C.byref(nn), _lp))
+    if rc != 0:
+        raise RmhmcError(rc, lib.lib.rmhmc_last_error(None).decode())
+    return dict(log_mean_w=lm.value, se=se.value, weight_ess=ess.value, m=m.value, n_nan=nn.value, merged=merged)
 
 
 _hip = None

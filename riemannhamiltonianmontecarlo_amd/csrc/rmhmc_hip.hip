@@ -13,6 +13,7 @@
 #include "../../include/rmhmc_diag.h"
 #include "../../include/rmhmc_phmc.h"
 #include "../../include/rmhmc_adapt.h"
+#include "../../include/rmhmc_ais.h"
 #include "plan.h"
 #include "mass.h"
 #include "kernels.hip.h"
@@ -27,6 +28,7 @@
 #include "diag.hip.h"
 #include "phmc.hip.h"
 #include "adapt.hip.h"
+#include "ais.hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -72,13 +74,15 @@ struct Group {
 // What one call asks of the stepping code.  The entry point builds it from its own arguments and hands it down by const&; nothing
 // below writes it, and the context keeps none of it (rmhmc_ctx::chains is the one exception).  A parameter the call's sampler
 // never reads is 0 (K of plain HMC, L of rmhmc_leapfrog, seed and chain_offset where the randomness is the caller's).
-enum Sampler { RMHMC, HMC, PHMC };  // rmhmc.py / hmc.py / HMC with the context's mass matrix (phmc.hip.h): selects the global step
+// rmhmc.py / hmc.py / HMC with the context's mass matrix (phmc.hip.h) / the same on the tempered target (ais.hip.h): selects the global step
+enum Sampler { RMHMC, HMC, PHMC, TPHMC };
 struct Run {
   Sampler sampler;
   int L, K;
   double eps;
   uint64_t seed; int64_t chain_offset;  // Philox key of chain c: (seed, chain_offset + c)
   const int* orig;  // work-sorted layout (sample_core): [n] position -> chain index in the caller's order, or nullptr: position = chain
+  double beta = 1.0;  // TPHMC only: the temperature (include/rmhmc_ais.h)
 };
 struct IterBase {  // ... and of the transition bookkeeping of the steps it issues
   long long limit, burn_in, S;
@@ -126,6 +130,9 @@ struct rmhmc_ctx : Plan {
   // fixed-metric HMC (phmc.hip.h): the images of rmhmc_phmc_set_mass, [DP][DP] each, allocated by its first call
   double *d_massL = nullptr, *d_massInv = nullptr;
   bool have_mass = false;
+  // tempered fixed-metric HMC and annealed importance sampling (ais.hip.h), [n] each, allocated by the first call that needs them:
+  // loglik of every chain's current point, that of the last initial evaluation, the log weights of rmhmc_ais_run
+  double *d_ais_ll = nullptr, *d_ais_ll0 = nullptr, *d_ais_logw = nullptr;
   // unit-API staging (device)
   double *d_z = nullptr, *d_ulen = nullptr, *d_gdir = nullptr, *d_uacc = nullptr;
   int *d_nsteps = nullptr, *d_dir = nullptr, *d_done = nullptr;
@@ -774,10 +781,27 @@ void launch_phmc_global_step(rmhmc_ctx* ctx, const Run& run, Group& g, const Ite
   });
 }
 
+// ... on the tempered target (ais.hip.h): the head and the gradient pass as they are, the tail under run.beta
+void launch_tphmc_global_step(rmhmc_ctx* ctx, const Run& run, Group& g, const IterBase& b) {
+  const double eps = run.eps, beta = run.beta;
+  const IterParams ip = iter_params(ctx, run, b);
+  const PhmcMass pm{ctx->d_massL, ctx->d_massInv};
+  const dim3 grid((unsigned)((g.n + 15) / 16)), block(256);
+  launch(ctx, "phmc", [&](hipStream_t st) {
+    PHMC_SWITCH(ctx, hipLaunchKernelGGL((k_phmc_head<NDB_>), grid, block, phmc_lds_bytes<NDB_>(), st, ctx->D, g.ch, ip, pm, eps));
+  });
+  launch_rowpass<RP_G>(ctx, g, g.ch.trj.w, nullptr);
+  launch(ctx, "ais", [&](hipStream_t st) {
+    PHMC_SWITCH(ctx, hipLaunchKernelGGL((k_tphmc_tail<NDB_>), grid, block, phmc_lds_bytes<NDB_>(), st, ctx->dd, g.ch, ip, pm, eps, ctx->nsplit, beta,
+                                        ctx->d_ais_ll));
+  });
+}
+
 // One global step of the batch g: transition start, one leapfrog step and transition end of every chain
 void launch_global_step(rmhmc_ctx* ctx, const Run& run, Group& g, const IterBase& b) {
   if (run.sampler == HMC) { launch_hmc_global_step(ctx, run, g, b); return; }
   if (run.sampler == PHMC) { launch_phmc_global_step(ctx, run, g, b); return; }
+  if (run.sampler == TPHMC) { launch_tphmc_global_step(ctx, run, g, b); return; }
   if (ctx->medium) {  // ... in ONE launch
     const int guards = (ctx->flags & RMHMC_FLAG_GUARDS) ? 1 : 0;
     const IterParams ip = iter_params(ctx, run, b);
@@ -1779,13 +1803,47 @@ static int hmc_init_chains(rmhmc_ctx* ctx, const double* theta0_host /* [n][D] o
   return reset_chains(ctx);
 }
 
-// one transition with the caller's randomness, plain (HMC) or with the context's mass matrix (PHMC)
+// the per-chain buffers of the tempered sampler and of annealed importance sampling, on first use
+static int ais_buffers(rmhmc_ctx* ctx) {
+  if (ctx->d_ais_logw) return RMHMC_OK;
+  if (!ctx->d_ais_ll) RC(dalloc(ctx, &ctx->d_ais_ll, ctx->n));
+  if (!ctx->d_ais_ll0) RC(dalloc(ctx, &ctx->d_ais_ll0, ctx->n));
+  return dalloc(ctx, &ctx->d_ais_logw, ctx->n);
+}
+// hmc_init_chains on the tempered target (include/rmhmc_ais.h), from the positions that are in trj.w already: the gradient pass and
+// k_tphmc_init, which leaves loglik in d_ais_ll and d_ais_ll0 and, with logw, adds dbeta loglik to it (a stage of rmhmc_ais_run)
+static int tphmc_init_dev(rmhmc_ctx* ctx, double beta, double* logw, double dbeta) {
+  Group& g = ctx->batch;
+  fill_int(ctx, g.ch.phase, 1, ctx->n);
+  launch_rowpass<RP_G>(ctx, g, g.ch.trj.w, nullptr);
+  launch(ctx, "ais", [&](hipStream_t st) {
+    hipLaunchKernelGGL(k_tphmc_init, dim3((unsigned)g.n), dim3(64), 0, st, ctx->dd, g.ch, ctx->nsplit, beta, ctx->d_ais_ll, ctx->d_ais_ll0, logw, dbeta);
+  });
+  return reset_chains(ctx);
+}
+static int tphmc_init_chains(rmhmc_ctx* ctx, const double* theta0_host /* [n][D] or NULL: zeros */, double beta) {
+  std::vector<double> th;
+  if (!theta0_host) { th.assign((size_t)ctx->n * ctx->D, 0.0); theta0_host = th.data(); }
+  RC(upload_vec(ctx, ctx->batch.ch.trj.w, theta0_host));
+  return tphmc_init_dev(ctx, beta, nullptr, 0.0);  // (synchronises: the staging vector goes out of scope)
+}
+
+// one transition with the caller's randomness, plain (HMC), with the context's mass matrix (PHMC), or that on the target tempered by beta
+// (TPHMC, which also returns loglik at the start and at the returned w)
 static int hmc_transition_body(rmhmc_ctx* ctx, Sampler sampler, double* w, const double* z, const double* u_len, const double* u_acc, int32_t L,
                                double eps, int32_t* accepted_out, int32_t* nsteps_out, double* H_cur_out, double* H_prop_out,
-                               double* w_prop_out, double* p_prop_out, int32_t* status_out) {
+                               double* w_prop_out, double* p_prop_out, int32_t* status_out, double beta = 1.0, double* loglik0_out = nullptr,
+                               double* loglik_out = nullptr) {
   ctx->chains_ready = false;
-  const Run run{sampler, L, 0, eps, 0, 0, nullptr};  // (no fixed-point iterations: no K; the randomness is the caller's: no seed)
-  RC(hmc_init_chains(ctx, w, sampler == HMC));
+  Run run{sampler, L, 0, eps, 0, 0, nullptr};  // (no fixed-point iterations: no K; the randomness is the caller's: no seed)
+  run.beta = beta;
+  if (sampler == TPHMC) {
+    RC(ais_buffers(ctx));
+    RC(tphmc_init_chains(ctx, w, beta));
+    if (loglik0_out) RC(download(ctx, loglik0_out, ctx->d_ais_ll0, ctx->n));
+  } else {
+    RC(hmc_init_chains(ctx, w, sampler == HMC));
+  }
   RC(upload(ctx, ctx->d_z, z, (size_t)ctx->n * ctx->D));
   RC(upload(ctx, ctx->d_ulen, u_len, ctx->n));
   RC(upload(ctx, ctx->d_uacc, u_acc, ctx->n));
@@ -1800,6 +1858,7 @@ static int hmc_transition_body(rmhmc_ctx* ctx, Sampler sampler, double* w, const
   if (w_prop_out) RC(download_vec(ctx, w_prop_out, ctx->batch.ch.trj.w));
   if (p_prop_out) RC(download_vec(ctx, p_prop_out, ctx->batch.ch.p));
   if (status_out) RC(download(ctx, status_out, ctx->batch.ch.status, ctx->n));
+  if (loglik_out && sampler == TPHMC) RC(download(ctx, loglik_out, ctx->d_ais_ll, ctx->n));
   RC(sync(ctx));
   if (accepted_out) for (int64_t c = 0; c < ctx->n; ++c) accepted_out[c] = (int32_t)acc[c];
   return RMHMC_OK;
@@ -1815,10 +1874,15 @@ int rmhmc_hmc_transition(rmhmc_ctx* ctx, double* w, const double* z, const doubl
 
 // Runs the HMC sampler run.sampler names (HMC or PHMC); the saved states go to the device buffer d_samples ([n][S][D]).  It leaves the
 // accepted proposals in batch.ch.accepted and, as sample_core, the post-burn-in leapfrog steps in d_steps0.
+static int hmc_sample_run(rmhmc_ctx* ctx, const Run& run, int64_t n_iter, int64_t burn_in, double* d_samples, double* seconds_out);
 static int hmc_sample_core(rmhmc_ctx* ctx, const Run& run, int64_t n_iter, int64_t burn_in, const double* theta0, double* d_samples, double* seconds_out) {
+  RC(hmc_init_chains(ctx, theta0, run.sampler == HMC));
+  return hmc_sample_run(ctx, run, n_iter, burn_in, d_samples, seconds_out);
+}
+// ... from chains that have their initial record (hmc_init_chains, or tphmc_init_chains for the tempered sampler)
+static int hmc_sample_run(rmhmc_ctx* ctx, const Run& run, int64_t n_iter, int64_t burn_in, double* d_samples, double* seconds_out) {
   const long long S = n_iter - burn_in;
   long long progress_next = ctx->progress_first;
-  RC(hmc_init_chains(ctx, theta0, run.sampler == HMC));
   const IterBase ipA{burn_in + 1, burn_in, S, d_samples, false, true};
   RC(run_phase(ctx, run, ipA, 0, &progress_next, false, true));
   HIPCK(hipMemcpyAsync(ctx->d_steps0, ctx->batch.ch.steps_done, sizeof(long long) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
@@ -1866,27 +1930,32 @@ int rmhmc_hmc_sample_to(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t
 }
 
 // ---- HMC with a fixed dense mass matrix shared by all chains (include/rmhmc_phmc.h, phmc.hip.h, mass.h) ----------------
-int rmhmc_phmc_set_mass(rmhmc_ctx* ctx, const double* mass) {
-  if (!ctx) return fail(nullptr, RMHMC_ERR_INVALID, "null context");
-  HIPCK(hipSetDevice(ctx->device));
-  std::vector<double> Lm, Mi;
-  const char* why = "";
-  if (mass_images(mass, ctx->D, ctx->DP, Lm, Mi, &why) != RMHMC_OK) return fail(ctx, RMHMC_ERR_INVALID, std::string("phmc_set_mass: ") + why);
+// the two images of a mass matrix (mass.h) into the context
+static int install_mass_images(rmhmc_ctx* ctx, const std::vector<double>& Lm, const std::vector<double>& Mi) {
   const size_t nn = (size_t)ctx->DP * ctx->DP;
   if (!ctx->d_massInv) {  // first use: the LDS limit of this shape's kernels (more than 64 KB for DP > 128), and the images
     // (what the instantiation needs, the same for every context that uses it - not MAX_LDS: the kernels have static LDS besides)
     int rc = RMHMC_OK;
     PHMC_SWITCH(ctx, rc = raise_lds(ctx, k_phmc_head<NDB_>, (int)phmc_lds_bytes<NDB_>());
-                if (rc == RMHMC_OK) rc = raise_lds(ctx, k_phmc_tail<NDB_>, (int)phmc_lds_bytes<NDB_>()));
+                if (rc == RMHMC_OK) rc = raise_lds(ctx, k_phmc_tail<NDB_>, (int)phmc_lds_bytes<NDB_>());
+                if (rc == RMHMC_OK) rc = raise_lds(ctx, k_tphmc_tail<NDB_>, (int)phmc_lds_bytes<NDB_>()));
     RC(rc);
     if (!ctx->d_massL) RC(dalloc(ctx, &ctx->d_massL, nn));
     RC(dalloc(ctx, &ctx->d_massInv, nn));
   }
   RC(upload(ctx, ctx->d_massL, Lm.data(), nn));
   RC(upload(ctx, ctx->d_massInv, Mi.data(), nn));
-  RC(sync(ctx));  // (the staging vectors go out of scope)
+  RC(sync(ctx));  // (the caller's staging vectors may go out of scope)
   ctx->have_mass = true;
   return RMHMC_OK;
+}
+int rmhmc_phmc_set_mass(rmhmc_ctx* ctx, const double* mass) {
+  if (!ctx) return fail(nullptr, RMHMC_ERR_INVALID, "null context");
+  HIPCK(hipSetDevice(ctx->device));
+  std::vector<double> Lm, Mi;
+  const char* why = "";
+  if (mass_images(mass, ctx->D, ctx->DP, Lm, Mi, &why) != RMHMC_OK) return fail(ctx, RMHMC_ERR_INVALID, std::string("phmc_set_mass: ") + why);
+  return install_mass_images(ctx, Lm, Mi);
 }
 
 int rmhmc_phmc_mode(rmhmc_ctx* ctx, const double* w0, int32_t max_iter, double tol, double* w_out, double* G_out, int32_t* iters_out,
@@ -2859,6 +2928,163 @@ int rmhmc_phmc_warmup(rmhmc_ctx* ctx, const double* theta0, int32_t L, double ep
   if (eps_out) *eps_out = eps_bar;
   if (mass_out) std::copy(mass_last.begin(), mass_last.end(), mass_out);
   if (theta_out) std::copy(theta.begin(), theta.end(), theta_out);
+  if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+  return RMHMC_OK;
+}
+
+}  // extern "C"
+
+// ---- annealed importance sampling with tempered fixed-metric HMC (include/rmhmc_ais.h, ais.h, ais.hip.h) ----------------------------------
+namespace {
+
+// logw [n] -> the partial [5], all in device memory; synchronises
+int ais_partial(rmhmc_ctx* ctx, const double* d_lw, size_t n, double* d_partial) {
+  int64_t nb, pb;
+  ais_plan((int64_t)n, &nb, &pb);
+  double* d_scr = nullptr;  // blk [nb][3], sums [nb][4]
+  HIPCK(hipMalloc((void**)&d_scr, sizeof(double) * 7 * (size_t)nb));
+  launch(ctx, "ais", [&](hipStream_t st) {
+    hipLaunchKernelGGL(k_ais_max, dim3((unsigned)nb), dim3(256), 0, st, d_lw, n, (size_t)pb, d_scr);
+    hipLaunchKernelGGL(k_ais_sums, dim3((unsigned)nb), dim3(256), 0, st, d_lw, n, (size_t)pb, (const double*)d_scr, (int)nb, d_scr + 3 * (size_t)nb);
+    hipLaunchKernelGGL(k_ais_fin, dim3(1), dim3(64), 0, st, (const double*)d_scr, (const double*)(d_scr + 3 * (size_t)nb), (int)nb, d_partial);
+  });
+  const hipError_t e = hipGetLastError();
+  const int rs = sync(ctx);
+  (void)hipFree(d_scr);
+  if (e != hipSuccess) return fail(ctx, RMHMC_ERR_RUNTIME, std::string(hipGetErrorString(e)) + " in ais_partial");
+  return rs;
+}
+
+// prior draws of key (seed, chain_offset + c) into out [n][ld] (device memory), queued on the stream
+void launch_ais_prior(rmhmc_ctx* ctx, uint64_t seed, int64_t chain_offset, double* out, int ld) {
+  launch(ctx, "ais", [&](hipStream_t st) {
+    hipLaunchKernelGGL(k_ais_prior, dim3((unsigned)ctx->n), dim3(64), 0, st, ctx->D, (unsigned long long)seed, (long long)chain_offset,
+                       std::sqrt(ctx->alpha), out, ld);
+  });
+}
+
+int tphmc_sample_body(rmhmc_ctx* ctx, const char* who, int64_t n_iter, int64_t burn_in, int32_t L, double eps, uint64_t seed, int64_t chain_offset,
+                      const double* theta0, const rmhmc_out& out, int64_t* accept_out, int64_t* steps_out, double* seconds_out, double beta,
+                      double* loglik0_out, double* loglik_out) {
+  if (burn_in < 0 || burn_in >= n_iter || L < 1) return fail(ctx, RMHMC_ERR_INVALID, std::string(who) + ": need 0 <= burn_in < n_iter, L >= 1");
+  if (!ais_beta_ok(beta)) return fail(ctx, RMHMC_ERR_INVALID, std::string(who) + ": beta must be finite and >= 0");
+  if (!ctx->have_mass) return fail(ctx, RMHMC_ERR_INVALID, std::string(who) + ": rmhmc_phmc_set_mass has not been called");
+  RC(stats_limit(ctx, who, out, n_iter - burn_in));
+  ctx->chains_ready = false;
+  RC(ais_buffers(ctx));
+  Run run{TPHMC, L, 0, eps, seed, chain_offset, nullptr};  // (no fixed-point iterations: no K)
+  run.beta = beta;
+  return sample_to(ctx, n_iter - burn_in, out, [&](double* d_samples) -> int {
+    RC(tphmc_init_chains(ctx, theta0, beta));
+    RC(hmc_sample_run(ctx, run, n_iter, burn_in, d_samples, seconds_out));
+    RC(counter_out(ctx, out, accept_out, ctx->batch.ch.accepted));
+    RC(counter_out(ctx, out, steps_out, ctx->d_steps0));
+    if (loglik0_out) RC(download(ctx, loglik0_out, ctx->d_ais_ll0, ctx->n));
+    if (loglik_out) RC(download(ctx, loglik_out, ctx->d_ais_ll, ctx->n));
+    return RMHMC_OK;
+  });
+}
+
+}  // namespace
+
+extern "C" {
+
+int rmhmc_tphmc_transition(rmhmc_ctx* ctx, double* w, const double* z, const double* u_len, const double* u_acc, int32_t L, double eps,
+                           int32_t* accepted_out, int32_t* nsteps_out, double* H_cur_out, double* H_prop_out, double* w_prop_out,
+                           double* p_prop_out, int32_t* status_out, double beta, double* loglik0_out, double* loglik_out) {
+  NEED_DATA(ctx);
+  if (!w || !z || !u_len || !u_acc || L < 1) return fail(ctx, RMHMC_ERR_INVALID, "tphmc_transition: null pointer or L < 1");
+  if (!ais_beta_ok(beta)) return fail(ctx, RMHMC_ERR_INVALID, "tphmc_transition: beta must be finite and >= 0");
+  if (!ctx->have_mass) return fail(ctx, RMHMC_ERR_INVALID, "tphmc_transition: rmhmc_phmc_set_mass has not been called");
+  return hmc_transition_body(ctx, TPHMC, w, z, u_len, u_acc, L, eps, accepted_out, nsteps_out, H_cur_out, H_prop_out, w_prop_out, p_prop_out, status_out,
+                             beta, loglik0_out, loglik_out);
+}
+
+int rmhmc_tphmc_sample_to(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L, double eps, uint64_t seed, int64_t chain_offset,
+                          const double* theta0, const rmhmc_out* out, int64_t* accept_out, int64_t* steps_out, double* seconds_out, double beta,
+                          double* loglik0_out, double* loglik_out) {
+  NEED_DATA(ctx);
+  RC(out_check(ctx, "tphmc_sample_to", out));
+  return tphmc_sample_body(ctx, "tphmc_sample_to", n_iter, burn_in, L, eps, seed, chain_offset, theta0, *out, accept_out, steps_out, seconds_out, beta,
+                           loglik0_out, loglik_out);
+}
+
+int rmhmc_ais_prior(rmhmc_ctx* ctx, uint64_t seed, int64_t chain_offset, double* theta_out) {
+  if (!ctx || !theta_out) return fail(ctx, RMHMC_ERR_INVALID, "ais_prior: need a context and theta_out");
+  HIPCK(hipSetDevice(ctx->device));
+  const size_t nd = (size_t)ctx->n * ctx->D;
+  double* d_th = nullptr;
+  HIPCK(hipMalloc((void**)&d_th, sizeof(double) * nd));
+  const int rc = [&]() -> int {
+    launch_ais_prior(ctx, seed, chain_offset, d_th, ctx->D);
+    HIPCK(hipGetLastError());
+    RC(download(ctx, theta_out, d_th, nd));
+    return sync(ctx);
+  }();
+  (void)hipFree(d_th);
+  return rc;
+}
+
+int rmhmc_ais_partial_dev(rmhmc_ctx* ctx, const double* logw_dev, int64_t n, double* partial_dev) {
+  if (!ctx || !logw_dev || !partial_dev || n < 1) return fail(ctx, RMHMC_ERR_INVALID, "ais_partial_dev: need logw, a partial and n >= 1");
+  HIPCK(hipSetDevice(ctx->device));
+  return ais_partial(ctx, logw_dev, (size_t)n, partial_dev);
+}
+
+int rmhmc_ais_finish(const double* const* partials, int32_t k, double* merged, double* log_mean_w, double* se, double* weight_ess, int64_t* m_out,
+                     int64_t* n_nan_out) {
+  const int rc = ais_finish(partials, k, merged, log_mean_w, se, weight_ess, m_out, n_nan_out);
+  return rc == RMHMC_OK ? rc : fail(nullptr, rc, "ais_finish: need k >= 1 and no NULL partial");
+}
+
+int rmhmc_ais_run(rmhmc_ctx* ctx, const double* theta0, double beta0, int32_t T, const double* beta, const int64_t* stage_len,
+                  const int32_t* stage_mass, const double* H_lik, int32_t L, double eps, uint64_t seed, int64_t chain_offset, double* logw_out,
+                  double* theta_out, double* accept_trace, double* partial_out, double* seconds_out) {
+  NEED_DATA(ctx);
+  const auto t_start = std::chrono::steady_clock::now();
+  if (const char* why = ais_check_run(theta0 != nullptr, beta0, T, beta, stage_len, stage_mass, H_lik != nullptr, L))
+    return fail(ctx, RMHMC_ERR_INVALID, std::string("ais_run: ") + why);
+  if (!ctx->have_mass) return fail(ctx, RMHMC_ERR_INVALID, "ais_run: rmhmc_phmc_set_mass has not been called");
+  ctx->chains_ready = false;
+  RC(ais_buffers(ctx));
+  const size_t n = ctx->n;
+  Group& g = ctx->batch;
+  HIPCK(hipMemsetAsync(ctx->d_ais_logw, 0, sizeof(double) * n, ctx->stream));
+  if (theta0) RC(upload_vec(ctx, g.ch.trj.w, theta0));
+  else launch_ais_prior(ctx, seed, chain_offset, g.ch.trj.w, ctx->DP);
+  std::vector<long long> acc(accept_trace ? n : 0);
+  std::vector<double> mass, Lm, Mi;
+  double prev = beta0;
+  for (int32_t k = 0; k < T; ++k) {
+    if (stage_mass && stage_mass[k]) {  // (a refusal - a beta H_lik + I / alpha that is not finite or not positive definite - keeps the previous mass)
+      const char* why = "";
+      if (ais_stage_mass_images(beta[k], H_lik, ctx->D, ctx->DP, ctx->dd.inv_alpha, mass, Lm, Mi, &why) == RMHMC_OK) RC(install_mass_images(ctx, Lm, Mi));
+    }
+    // the last positions of the previous stage are the current points of its chains
+    if (k > 0) HIPCK(hipMemcpyAsync(g.ch.trj.w, g.ch.cur.w, sizeof(double) * n * ctx->DP, hipMemcpyDeviceToDevice, ctx->stream));
+    RC(tphmc_init_dev(ctx, beta[k], ctx->d_ais_logw, beta[k] - prev));
+    Run run{TPHMC, L, 0, eps, seed + 1 + (uint64_t)k, chain_offset, nullptr};
+    run.beta = beta[k];
+    RC(hmc_sample_run(ctx, run, stage_len[k], 0, nullptr, nullptr));  // (no sample buffer: the positions stay in the records)
+    if (accept_trace) {
+      RC(download(ctx, acc.data(), g.ch.accepted, n));
+      RC(sync(ctx));
+      accept_trace[k] = adapt_accept((const int64_t*)acc.data(), (int64_t)n, stage_len[k]);
+    }
+    prev = beta[k];
+  }
+  if (logw_out) RC(download(ctx, logw_out, ctx->d_ais_logw, n));
+  if (theta_out) RC(download_vec(ctx, theta_out, g.ch.cur.w));
+  if (partial_out) {
+    double* d_part = nullptr;
+    HIPCK(hipMalloc((void**)&d_part, sizeof(double) * 5));
+    int rc = ais_partial(ctx, ctx->d_ais_logw, n, d_part);
+    if (rc == RMHMC_OK) rc = download(ctx, partial_out, d_part, (size_t)5);
+    if (rc == RMHMC_OK) rc = sync(ctx);
+    (void)hipFree(d_part);
+    RC(rc);
+  }
+  RC(sync(ctx));
   if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
   return RMHMC_OK;
 }
