@@ -12,6 +12,7 @@
  * A tempered transition is the transition of rmhmc_phmc.h with LJL_beta and grad_beta in place of LJL and grad: the same streams,
  * trajectory length, NaN rule, failure rule (RMHMC_ST_NONFINITE) and acceptance.  At beta = 0 a chain whose loglik is not finite has
  * LJL_0 = 0 * inf = NaN: it fails, as it does at every other beta.
+ * At a position with an entry that is not finite some row has t f = 0 * inf or f - log(1 + exp f) = inf - inf: loglik is NaN there.
  *
  * Two equalities anchor the tempered sampler to tested code:
  *   beta = 1           rmhmc_tphmc_transition and rmhmc_tphmc_sample_to equal rmhmc_phmc_transition and rmhmc_phmc_sample_to bit for bit

@@ -33,14 +33,16 @@
 
 #pragma clang fp contract(off)
 
-// LJL_beta, grad_beta of the row pass's partials into trj.grad / trj.ljl; returns loglik (every lane)
+// LJL_beta, grad_beta of the row pass's partials into trj.grad / trj.ljl; returns loglik (every lane), NaN where trj.w is not finite
 __device__ __forceinline__ double tphmc_finish_eval(const DevData& dd, const Chains& ch, int c, int lane, int nsplit, double beta) {
   const int D = dd.D, DP = dd.DP;
   double part = 0.0, lik = 0.0;
+  int w_bad = 0;
   for (int d = lane; d < D; d += 64) {
     const double wl = ch.trj.w[(size_t)c * DP + d];
     ch.trj.grad[(size_t)c * DP + d] = fma(-dd.inv_alpha, wl, beta * plane_sum(ch.gpart, nsplit, ch.n, c, DP, d));
     part = part + fma(dd.inv_alpha, (wl * wl) * -0.5, dd.log_prior_const);
+    w_bad |= !isfinite(wl);
   }
   for (int b = lane; b < nsplit; b += 64) {
     const double x = ch.ljl_part[(size_t)c * nsplit + b];
@@ -50,7 +52,10 @@ __device__ __forceinline__ double tphmc_finish_eval(const DevData& dd, const Cha
   const double ljl = wave_sum(part);
   const double ll = wave_sum(lik);
   if (lane == 0) ch.trj.ljl[c] = ljl;
-  return ll;
+  // a position that is not finite has f = +-inf or NaN on every row its column reaches, and t f - log(1 + exp f) is 0 x inf or inf - inf
+  // there: loglik is NaN (include/rmhmc_ais.h).  The row pass of D <= 64 reports an f above 709.78 as -inf whatever else the split holds
+  // (kernels.hip.h), which is the reference's value for a finite f and hid the NaN of an infinite one; large_d.hip.h keeps it.
+  return __ballot(w_bad) ? __builtin_nan("") : ll;
 }
 
 // initial evaluation at trj.w under beta: trj -> cur, ll[c] = loglik; ll0 | nullptr: a copy that the stepping does not overwrite;

@@ -4,7 +4,9 @@ pins to the CPU oracle.
 
 GPU-versus-restatement tolerances are those of plain HMC against its oracle (tests/test_gpu_parity.py): step counts and decisions
 equal, w_prop / p_prop / H_prop 1e-9, samples 1e-8.  No decision of the restatement may be within 1e-6 of a tie, so that rounding
-cannot flip one.  Measured on an MI355X: 3e-16 ... 1.4e-14 relative, the smallest tie margin 9e-3."""
+cannot flip one.  Measured on an MI355X: 3e-16 ... 1.4e-14 relative, the smallest tie margin 9e-3.
+Every chain slot of a workgroup, the tile edges of D, zero-step trajectories and the sampler against the chained restatement:
+tests/test_gpu_phmc_edges.py."""
 import os
 import sys
 
