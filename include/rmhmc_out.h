@@ -43,7 +43,9 @@ typedef struct {
  * population variance per chain and dimension; RMHMC_FLAG_ESS_WRAP of the context selects the FFT-length
  * convention).  run_mean[s][d] = (sum over c = 0..n-1, in that order, of samples[c][s][d]) / n; run_ess:
  * the same ESS kernel on run_mean as one series block of S x D.  NaN propagates: a Gibbs chain that
- * stopped has NaN rows, so its mean / var / ess and the rows of run_mean it touches are NaN.
+ * stopped has NaN rows, so its mean / var / ess and the rows of run_mean it touches are NaN.  The same
+ * holds for a series with an inf: mean, var and ess are all NaN (not the +-inf of the sum).  A constant
+ * series has its mean, var = 0 and ess = NaN.
  *
  * The counters ([n] int64 unless noted, each may be NULL) live in the memory space `where` names;
  * seconds_out is a host scalar. */

@@ -952,7 +952,7 @@ static void ess_series(const double *x, int64_t S, int64_t stride, double *ess, 
   double *xc = (double *)malloc(sizeof(double) * S);
   double c0 = 0;
   for (int64_t s = 0; s < S; s++) { xc[s] = x[s * stride] - m; c0 += xc[s] * xc[s]; }
-  if (mean_out) *mean_out = m;
+  if (mean_out) *mean_out = (c0 == c0) ? m : NAN; /* a series with a NaN or an inf: mean, variance and ESS are all NaN */
   if (var_out) *var_out = c0 / (double)S;
   double prev = INFINITY, sum = 0;
   const int64_t half = S / 2; /* floor((MaxLag+1)/2) with MaxLag = S-1 */

@@ -2358,7 +2358,8 @@ __global__ __launch_bounds__(64) void k_mmala_end(int D, int DP, Chains ch, Iter
 // ESS on the device (widening row 8f-2): tools.CalculateESS(Samples, S-1), tools.py:32-74, for one series per
 // wavefront.  samples[(c*S + s)*P + d]; the centred series lives in LDS; autocovariances are evaluated lag by lag
 // (two per Geyer pair, tools.py:46-50) until the running-minimum pair sum (:54-60) turns non-positive, which is
-// where the reference's "sum of the positive Gammas" (:62-67) ends.  Also returns mean and population variance.
+// where the reference's "sum of the positive Gammas" (:62-67) ends.  Also returns mean and population variance; all three
+// are NaN for a series that holds a NaN or an inf, and a constant series has its mean, variance 0 and no ESS (NaN).
 // nfft = 0: linear autocovariances (the MATLAB original, ac.m:78: a 2^(k+1)-point FFT never wraps).  nfft > 0
 // (RMHMC_FLAG_ESS_WRAP): the reference's Python translation takes an FFT of length nFFT = nextpow2(S)+1 (tools.py:16-23), whose
 // circular autocorrelation at lag l is the linear one at l PLUS the linear one at nFFT - l; reproduced term by term.
@@ -2404,7 +2405,7 @@ __global__ __launch_bounds__(64) void k_ess(const double* __restrict__ samples, 
   if (mono < 1.0) mono = 1.0;
   if (lane == 0) {
     if (ess_out) ess_out[idx] = (c0 > 0.0) ? (double)S / mono : NAN;
-    if (mean_out) mean_out[idx] = m;
+    if (mean_out) mean_out[idx] = (c0 == c0) ? m : NAN;  // a series with a NaN or an inf has no statistic: not the +-inf of its sum
     if (var_out) var_out[idx] = c0 / (double)S;
   }
 }

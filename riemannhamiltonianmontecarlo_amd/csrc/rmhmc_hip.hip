@@ -1553,8 +1553,13 @@ static int run_sorted_phase(rmhmc_ctx* ctx, const Run& run, const IterBase& ib, 
 namespace {
 
 // ESS / posterior summaries on the device (tools.py:32-74)
-int launch_ess(rmhmc_ctx* ctx, const double* d_samples, long long nblocks, long long S, int P, double* d_ess, double* d_mean, double* d_var) {
+// the series length the kernel holds: checked by rmhmc_ess and rmhmc_ess_dev before they size or touch anything by S, and by every launch
+int ess_range(rmhmc_ctx* ctx, long long S) {
   if (S < 2 || S > 20000) return fail(ctx, RMHMC_ERR_UNSUPPORTED, "ess: 2 <= S <= 20000 samples per chain (the centred series is held in LDS)");
+  return RMHMC_OK;
+}
+int launch_ess(rmhmc_ctx* ctx, const double* d_samples, long long nblocks, long long S, int P, double* d_ess, double* d_mean, double* d_var) {
+  RC(ess_range(ctx, S));
   HIPCK(hipFuncSetAttribute((const void*)k_ess, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS));  // per device: set where it is used
   long long nfft = 0;
   if (ctx->flags & RMHMC_FLAG_ESS_WRAP) { nfft = 1; while (nfft < S) nfft *= 2; nfft += 1; }  // tools.py:16-23
@@ -1762,6 +1767,7 @@ int rmhmc_sample_to(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, int32_t L, 
 // ---- ESS of given samples (tools.py:32-74; launch_ess above) -------------------------------------------
 int rmhmc_ess(rmhmc_ctx* ctx, const double* samples, int64_t n, int64_t S, int32_t P, double* ess_out) {
   if (!ctx || !samples || !ess_out || n < 1 || P < 1 || n * (int64_t)P > 0x7fffffffLL) return fail(ctx, RMHMC_ERR_INVALID, "ess: bad argument");
+  RC(ess_range(ctx, S));  // before the buffers below are sized by S
   HIPCK(hipSetDevice(ctx->device));
   double *d_s = nullptr, *d_e = nullptr;
   HIPCK(hipMalloc((void**)&d_s, sizeof(double) * (size_t)n * S * P));
@@ -1780,6 +1786,7 @@ int rmhmc_ess(rmhmc_ctx* ctx, const double* samples, int64_t n, int64_t S, int32
 int rmhmc_ess_dev(rmhmc_ctx* ctx, const double* samples_dev, int64_t n, int64_t S, int32_t P, double* ess_dev, double* mean_dev, double* var_dev) {
   if (!ctx || !samples_dev || (!ess_dev && !mean_dev && !var_dev) || n < 1 || P < 1 || n * (int64_t)P > 0x7fffffffLL)
     return fail(ctx, RMHMC_ERR_INVALID, "ess_dev: bad argument");
+  RC(ess_range(ctx, S));
   HIPCK(hipSetDevice(ctx->device));
   RC(launch_ess(ctx, samples_dev, n, S, P, ess_dev, mean_dev, var_dev));
   return sync(ctx);

@@ -3,7 +3,8 @@ device, or both, against the sampler's existing *_sample call (bit for bit), the
 tools.CalculateESS (the project's tolerances: mean / var rtol 1e-12, atol 1e-14; ESS rtol 1e-9).
 
 Shapes: 200 rows, D = 5, 5 chains, 60 iterations of which 23 burn-in: S = 37 is odd, the ESS kernel's half = 18, n is a multiple of
-nothing; IWLS again at D = 33 (three column blocks) and Gibbs at D = 17; one case with RMHMC_FLAG_ESS_WRAP.  The older entry points
+nothing; IWLS again at D = 33 (three column blocks) and Gibbs at D = 17; one case with RMHMC_FLAG_ESS_WRAP (at S = 37 no wrapped lag
+is reached before the sums stop, so it checks the flag's plumbing only: the wrap itself is tested in tests/test_gpu_ess_edges.py).  The older entry points
 are the same bodies behind a descriptor of their own: what only they allow (rmhmc_sample_stats without a statistic), what they
 refuse themselves (no samples_out) and the statistics limit, refused before any sampling work, at n = 3 and n = 5.  Needs an
 MI355X: run with  pytest -m gpu."""
@@ -39,7 +40,7 @@ CASES = {
     "gibbs": ("gibbs", 5, 0, 0),
     "iwls_d33": ("iwls", 33, 0, 20),
     "gibbs_d17": ("gibbs", 17, 0, 0),
-    "hmc_wrap": ("hmc", 5, _capi.FLAG_ESS_WRAP, 0),
+    "hmc_wrap": ("hmc", 5, _capi.FLAG_ESS_WRAP, 0),   # S = 37, nfft = 65: the first wrapped lag is 29, never reached (see the docstring)
 }
 MEAN_TOL = dict(rtol=1e-12, atol=1e-14)   # (tests/test_gpu_bench.py: the device mean against NumPy)
 ESS_RTOL = 1e-9                           # (the ESS kernel against tools.CalculateESS)

@@ -76,12 +76,15 @@ def test_python_fft_length_wraparound_is_reproduced(oracle):
         for name in ("ess_s4096", "ess_ar1", "ess_pima_chain"):
             gg = np.load(os.path.join(GOLDEN, name + ".npz"))
             assert np.allclose(ctx.ess(gg["samples"])[0], gg["ess"], rtol=1e-10), name
-    # a short series where the two FFT lengths visibly disagree: S = 9 -> nFFT = 17, lag l collects lag 17 - l
+    # short series where the two FFT lengths visibly disagree: S a power of two -> nFFT = S + 1, every lag l >= 2 collects lag S + 1 - l.
+    # (Not S = 9: nFFT = 17 there, and no lag l <= 8 has a partner 17 - l inside the series.)
     rs = np.random.RandomState(5)
-    y = np.cumsum(rs.randn(9, 3), axis=0)
-    with oracle.context(10, 2, 1, flags=_capi.FLAG_ESS_WRAP) as ctx:
-        wrapped = ctx.ess(y)[0]
-    with oracle.context(10, 2, 1, flags=0) as ctx:
-        linear = ctx.ess(y)[0]
-    assert np.allclose(wrapped, tools.CalculateESS(y, 8, nfft="python").ravel(), rtol=1e-10)
-    assert np.allclose(linear, tools.CalculateESS(y, 8, nfft="matlab").ravel(), rtol=1e-10)
+    for S in (8, 16):
+        y = np.cumsum(rs.randn(S, 3), axis=0)
+        with oracle.context(10, 2, 1, flags=_capi.FLAG_ESS_WRAP) as ctx:
+            wrapped = ctx.ess(y)[0]
+        with oracle.context(10, 2, 1, flags=0) as ctx:
+            linear = ctx.ess(y)[0]
+        assert np.allclose(wrapped, tools.CalculateESS(y, S - 1, nfft="python").ravel(), rtol=1e-10)
+        assert np.allclose(linear, tools.CalculateESS(y, S - 1, nfft="matlab").ravel(), rtol=1e-10)
+        assert (np.abs(wrapped / linear - 1) > 1e-3).any(), S
