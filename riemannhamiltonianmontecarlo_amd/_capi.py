@@ -216,6 +216,14 @@ AIS_SIGNATURES = {
 AIS_PRIOR_ITER = 0xFFFFFFFF   # iteration counter of the prior draws (RMHMC_AIS_PRIOR_ITER)
 AIS_KEYS = ("log_mean_w", "se", "weight_ess", "m", "n_nan")   # what ais_finish returns besides the merged partial
 
+# include/rmhmc_pred.h: posterior predictive probabilities of new rows from draws on the device, HIP library only as well
+PRED_SIGNATURES = {
+    "rmhmc_pred_partial_dev": (C.c_int, [C.c_void_p, _vp, C.c_int64, C.c_int64, C.c_int32, _dp, _dp, C.c_int64, _vp]),
+    "rmhmc_pred_finish": (C.c_int, [_dpp, C.c_int32, C.c_int64, _dp, _dp, _dp, _dp, _dp, _lp]),
+}
+PRED_KEYS = ("prob", "pvar", "lpd", "lpd_total", "draws_used")   # what pred_finish returns besides the merged partial
+PRED_MAX_D = 256     # widest draw of rmhmc_pred_partial_dev
+
 
 def ais_schedule(n_temps, ladder="power4", mass_every=1, iters_per_temp=1):
     """(beta [T], stage_len [T], stage_mass [T]) of an annealing run of T = n_temps stages (csrc/ais.h): ladder "power<q>" is
@@ -364,6 +372,12 @@ class RmhmcLib:
         self.has_ais = all(hasattr(self.lib, name) for name in AIS_SIGNATURES)
         if self.has_ais:
             for name, (res, args) in AIS_SIGNATURES.items():
+                fn = getattr(self.lib, name)
+                fn.restype = res
+                fn.argtypes = args
+        self.has_pred = all(hasattr(self.lib, name) for name in PRED_SIGNATURES)
+        if self.has_pred:
+            for name, (res, args) in PRED_SIGNATURES.items():
                 fn = getattr(self.lib, name)
                 fn.restype = res
                 fn.argtypes = args
@@ -783,6 +797,47 @@ class Context:
         out = dict(logw=logw, theta=theta, accept_trace=trace, partial=part, seconds=secs.value)
         out.update(ais_finish([part], lib=self.rl))
         return out
+
+    # ---- posterior predictive probabilities of new rows (include/rmhmc_pred.h) -----------
+    def _need_pred(self):
+        if not self.rl.has_pred:
+            raise RmhmcError(-4, "%s does not export the posterior predictive probabilities (include/rmhmc_pred.h)" % self.rl.path)
+
+    def predict_partial(self, samples, xnew, tnew=None):
+        """The mergeable partial [4, R] = (m, S1, S2, SQ) (include/rmhmc_pred.h) of the draws of a float64 torch tensor [n][S][D] already
+        on the context's GPU for the rows xnew [R][D] (host) and the held-out labels tnew [R] (host, 0 or 1) or None, reduced there.
+        torch's current stream is synchronised first, as in ess_dev."""
+        import torch
+        self._need_pred()
+        if self.rl.on_gpu and not samples.is_cuda:
+            raise ValueError("predict_partial: a tensor on the context's GPU is required")
+        w = samples.contiguous()
+        if w.dtype != torch.float64 or w.dim() != 3:
+            raise ValueError("predict_partial: float64 tensor [n][S][D] required")
+        n, S, D = w.shape
+        x = _f64(xnew)
+        if x.ndim != 2 or x.shape[1] != D:
+            raise ValueError("predict_partial: xnew must be (R, D) with the D of the samples")
+        R = x.shape[0]
+        t = None if tnew is None else _f64(tnew).reshape(-1)
+        if t is not None and t.shape[0] != R:
+            raise ValueError("predict_partial: tnew must have R entries")
+        part = torch.empty((4, R), dtype=torch.float64, device=w.device)
+        if w.is_cuda:
+            torch.cuda.current_stream(w.device).synchronize()
+        self._ck(self.lib.rmhmc_pred_partial_dev(self._h, w.data_ptr(), n, S, D, _ptr(x), _ptr(t), R, part.data_ptr()))
+        return part
+
+    def predict(self, samples, xnew, tnew=None):
+        """posterior predictive probabilities of the rows xnew [R][D] under the draws samples [n][S][D] on the context's GPU (draws with
+        a non-finite entry left out): dict(prob [R] = p(t* = 1 | x*, data), pvar [R] the variance of p over the draws, lpd [R] the log
+        pointwise predictive density of tnew (NaN without labels), lpd_total, draws_used: host; partial: the device tensor of
+        predict_partial)"""
+        part = self.predict_partial(samples, xnew, tnew)
+        out = pred_finish([part], lib=self.rl)
+        res = {k: out[k] for k in PRED_KEYS}
+        res["partial"] = part
+        return res
 
     # ---- adaptive Metropolis (code/metropolis.py, include/rmhmc_amh.h) -----------
     def _need_amh(self):
@@ -1262,6 +1317,30 @@ def ais_finish(partials, lib=None):
     if rc != 0:
         raise RmhmcError(rc, lib.lib.rmhmc_last_error(None).decode())
     return dict(log_mean_w=lm.value, se=se.value, weight_ess=ess.value, m=m.value, n_nan=nn.value, merged=merged)
+
+
+def pred_finish(partials, lib=None):
+    """rmhmc_pred_finish (include/rmhmc_pred.h): the partials ([4, R] each: torch tensors on any device or NumPy arrays) merged in the
+    order given and finished on the host.  Returns dict(prob, pvar, lpd [R], lpd_total, draws_used, merged [4, R])."""
+    lib = lib if lib is not None else load_hip_library()
+    if not lib.has_pred:
+        raise RmhmcError(-4, "%s does not export the posterior predictive probabilities (include/rmhmc_pred.h)" % lib.path)
+    parts = [_f64(p if isinstance(p, np.ndarray) else p.detach().cpu().numpy()) for p in partials]
+    if not parts or parts[0].ndim != 2 or parts[0].shape[0] != 4 or any(p.shape != parts[0].shape for p in parts):
+        raise ValueError("pred_finish: partials of one shape [4, R] required")
+    R = parts[0].shape[1]
+    ptrs = (_dp * len(parts))(*[_ptr(p) for p in parts])
+    merged = np.empty((4, R)); prob = np.empty(R); pvar = np.empty(R); lpd = np.empty(R); total = C.c_double(0.0); used = C.c_int64(0)
+    rc = lib.lib.rmhmc_pred_finish(ptrs, len(parts), R, _ptr(merged), _ptr(prob), _ptr(pvar), _ptr(lpd), C.cast(C.byref(total), _dp),
+                                   C.cast(C.byref(used), _lp))
+    if rc != 0:
+        raise RmhmcError(rc, lib.lib.rmhmc_last_error(None).decode())
+    return dict(prob=prob, pvar=pvar, lpd=lpd, lpd_total=total.value, draws_used=used.value, merged=merged)
+
+
+def pred_identity(R):
+    """the partial of no draws at all (an empty shard): the identity of the merge"""
+    return np.zeros((4, int(R)))
 
 
 _hip = None

@@ -14,6 +14,7 @@
 #include "../../include/rmhmc_phmc.h"
 #include "../../include/rmhmc_adapt.h"
 #include "../../include/rmhmc_ais.h"
+#include "../../include/rmhmc_pred.h"
 #include "plan.h"
 #include "mass.h"
 #include "kernels.hip.h"
@@ -29,6 +30,7 @@
 #include "phmc.hip.h"
 #include "adapt.hip.h"
 #include "ais.hip.h"
+#include "pred.hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -3094,6 +3096,66 @@ int rmhmc_ais_run(rmhmc_ctx* ctx, const double* theta0, double beta0, int32_t T,
   RC(sync(ctx));
   if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
   return RMHMC_OK;
+}
+
+}  // extern "C"
+
+// ---- posterior predictive probabilities of new rows (include/rmhmc_pred.h, pred.h, pred.hip.h) -----------------------------------------------
+namespace {
+
+// draws [N][D] (device), xnew [R][D] and tnew [R] | NULL (host, checked) -> the partial [4][R] (device); synchronises
+int pred_partial(rmhmc_ctx* ctx, const double* d_w, size_t N, int D, const double* xnew, const double* tnew, size_t R, double* d_partial) {
+  const pred_plan_t pl = pred_plan((int64_t)N, (int64_t)R, D);
+  void* d_scratch = nullptr;
+  HIPCK(hipMalloc(&d_scratch, (size_t)pl.scratch_bytes));
+  double* rec = (double*)d_scratch;
+  double* cnt = rec + pl.rec_doubles;
+  double* d_x = cnt + pl.cnt_doubles;
+  double* d_t = d_x + R * (size_t)D;
+  unsigned char* valid = (unsigned char*)(d_t + R);
+  const int rc = [&]() -> int {
+    RC(upload(ctx, d_x, xnew, R * (size_t)D));
+    if (tnew) RC(upload(ctx, d_t, tnew, R));
+    const dim3 grid((unsigned)pl.row_tiles, (unsigned)pl.nblocks);
+    const double* t_arg = tnew ? d_t : nullptr;
+    launch(ctx, "pred", [&](hipStream_t st) {
+      hipLaunchKernelGGL(k_pred_valid, dim3((unsigned)pl.vblocks), dim3(256), 0, st, d_w, N, D, (size_t)pl.draws_per_vblock, valid, cnt);
+      switch (pl.ksteps) {
+#define PRED_CASE(KS_) case KS_: hipLaunchKernelGGL(k_pred_main<KS_>, grid, dim3(64 * PRED_WAVES), 0, st, d_w, N, D, (size_t)pl.draws_per_block, valid, d_x, t_arg, R, rec); break
+        PRED_CASE(4); PRED_CASE(8); PRED_CASE(16); PRED_CASE(24); PRED_CASE(32); PRED_CASE(40); PRED_CASE(48); PRED_CASE(56);
+        default: static_assert(PRED_MAX_D == 256, "the cases above end at 64 steps"); PRED_CASE(64);
+#undef PRED_CASE
+      }
+      hipLaunchKernelGGL(k_pred_fin, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, rec, (size_t)pl.nblocks, cnt, (size_t)pl.vblocks, R,
+                         tnew ? 1 : 0, d_partial);
+    });
+    HIPCK(hipGetLastError());
+    return RMHMC_OK;
+  }();
+  const int rs = sync(ctx);
+  (void)hipFree(d_scratch);
+  return rc != RMHMC_OK ? rc : rs;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rmhmc_pred_partial_dev(rmhmc_ctx* ctx, const double* samples_dev, int64_t n, int64_t S, int32_t D, const double* xnew, const double* tnew,
+                           int64_t R, double* partial_dev) {
+  if (!ctx || !samples_dev || !xnew || !partial_dev || n < 1 || S < 1 || D < 1 || R < 1 || n > INT64_MAX / S || R > INT64_MAX / 4 / D ||
+      (R + PRED_ROW_TILE - 1) / PRED_ROW_TILE > 0x7fffffffLL)
+    return fail(ctx, RMHMC_ERR_INVALID, "pred_partial_dev: need samples, xnew, a partial, n >= 1, S >= 1, D >= 1, R >= 1");
+  if (D > PRED_MAX_D) return fail(ctx, RMHMC_ERR_UNSUPPORTED, "pred_partial_dev: D <= 256");
+  if (const char* why = pred_check_rows(xnew, tnew, R, D)) return fail(ctx, RMHMC_ERR_INVALID, std::string("pred_partial_dev: ") + why);
+  HIPCK(hipSetDevice(ctx->device));
+  return pred_partial(ctx, samples_dev, (size_t)n * (size_t)S, D, xnew, tnew, (size_t)R, partial_dev);
+}
+
+int rmhmc_pred_finish(const double* const* partials, int32_t k, int64_t R, double* merged, double* prob, double* pvar, double* lpd,
+                      double* lpd_total, int64_t* draws_used) {
+  const int rc = pred_finish(partials, k, R, merged, prob, pvar, lpd, lpd_total, draws_used);
+  return rc == RMHMC_OK ? rc : fail(nullptr, rc, rc == RMHMC_ERR_NOMEM ? "pred_finish: out of memory" : "pred_finish: need k >= 1, R >= 1 and no NULL partial");
 }
 
 }  // extern "C"
