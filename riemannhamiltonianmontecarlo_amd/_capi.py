@@ -224,6 +224,24 @@ PRED_SIGNATURES = {
 PRED_KEYS = ("prob", "pvar", "lpd", "lpd_total", "draws_used")   # what pred_finish returns besides the merged partial
 PRED_MAX_D = 256     # widest draw of rmhmc_pred_partial_dev
 
+# include/rmhmc_smc.h: the log marginal likelihood by adaptive sequential Monte Carlo (conditional-ESS ladder, systematic resampling on
+# integers) on top of the tempered sampler of rmhmc_ais.h, HIP library only as well
+SMC_SIGNATURES = {
+    "rmhmc_smc_cess_dev": (C.c_int, [C.c_void_p, _vp, _vp, C.c_int64, C.c_int32, _dp, _vp]),
+    "rmhmc_smc_cess_finish": (C.c_int, [_dpp, C.c_int32, C.c_int32, _dp, _dp]),
+    "rmhmc_smc_choose_delta_dev": (C.c_int, [C.c_void_p, _vp, _vp, C.c_int64, C.c_double, C.c_double, _dp, _dp, _ip]),
+    "rmhmc_smc_reweight_dev": (C.c_int, [C.c_void_p, _vp, _vp, C.c_int64, C.c_double]),
+    "rmhmc_smc_quantise_dev": (C.c_int, [C.c_void_p, _vp, C.c_int64, C.c_double, _vp]),
+    "rmhmc_smc_ancestors_dev": (C.c_int, [C.c_void_p, _vp, C.c_int64, C.c_uint32, _vp]),
+    "rmhmc_smc_run": (C.c_int, [C.c_void_p, _dp, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int64, C.c_int64, _dp, C.c_int32, C.c_double,
+                                C.c_uint64, C.c_int64, _ip, _dp, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+}
+SMC_MAX_J = 32            # most candidates of one smc_cess call (RMHMC_SMC_MAX_J)
+SMC_J, SMC_ROUNDS = 16, 3     # the search: candidates per round, rounds (RMHMC_SMC_J, RMHMC_SMC_ROUNDS)
+SMC_MAX_N = 2 ** 20       # most particles of smc_ancestors (RMHMC_SMC_MAX_N)
+SMC_QBITS = 40            # q = 2^40 at the largest weight (RMHMC_SMC_QBITS)
+SMC_LAST, SMC_FLOOR, SMC_RESAMPLED = 1, 2, 4      # flags of a stage
+
 
 def ais_schedule(n_temps, ladder="power4", mass_every=1, iters_per_temp=1):
     """(beta [T], stage_len [T], stage_mass [T]) of an annealing run of T = n_temps stages (csrc/ais.h): ladder "power<q>" is
@@ -378,6 +396,12 @@ class RmhmcLib:
         self.has_pred = all(hasattr(self.lib, name) for name in PRED_SIGNATURES)
         if self.has_pred:
             for name, (res, args) in PRED_SIGNATURES.items():
+                fn = getattr(self.lib, name)
+                fn.restype = res
+                fn.argtypes = args
+        self.has_smc = all(hasattr(self.lib, name) for name in SMC_SIGNATURES)
+        if self.has_smc:
+            for name, (res, args) in SMC_SIGNATURES.items():
                 fn = getattr(self.lib, name)
                 fn.restype = res
                 fn.argtypes = args
@@ -796,6 +820,110 @@ class Context:
                                         _ptr(part), C.cast(C.byref(secs), _dp)))
         out = dict(logw=logw, theta=theta, accept_trace=trace, partial=part, seconds=secs.value)
         out.update(ais_finish([part], lib=self.rl))
+        return out
+
+    # ---- the evidence by adaptive sequential Monte Carlo (include/rmhmc_smc.h) -----------
+    def _need_smc(self):
+        if not self.rl.has_smc:
+            raise RmhmcError(-4, "%s does not export adaptive sequential Monte Carlo (include/rmhmc_smc.h)" % self.rl.path)
+
+    def _smc_vec(self, who, x, dtype=None):
+        """a contiguous 1-d torch tensor on the context's GPU, n >= 1 (float64 unless dtype says otherwise); torch's current stream is
+        synchronised, as in ess_dev"""
+        import torch
+        if self.rl.on_gpu and not x.is_cuda:
+            raise ValueError("%s: a tensor on the context's GPU is required" % who)
+        x = x.contiguous()
+        if x.dtype != (dtype or torch.float64) or x.dim() != 1 or x.numel() < 1:
+            raise ValueError("%s: %s tensor [n], n >= 1, required" % (who, str(dtype or torch.float64).replace("torch.", "")))
+        if x.is_cuda:
+            torch.cuda.current_stream(x.device).synchronize()
+        return x
+
+    def smc_cess(self, logw, loglik, delta):
+        """The mergeable conditional-ESS partial [2 + 4 J] = (a0, S0, then per candidate a1, S1, a2, S2) (include/rmhmc_smc.h) of the log
+        weights and log-likelihoods (float64 torch tensors [n] on the context's GPU) at the J <= 32 candidate steps delta (host)."""
+        import torch
+        self._need_smc()
+        lw, ll = self._smc_vec("smc_cess", logw), self._smc_vec("smc_cess", loglik)
+        d = _f64(delta).reshape(-1)
+        if ll.shape != lw.shape or not 1 <= d.size <= SMC_MAX_J:
+            raise ValueError("smc_cess: logw and loglik of one length and 1 .. %d candidates required" % SMC_MAX_J)
+        part = torch.empty(2 + 4 * d.size, dtype=torch.float64, device=lw.device)
+        self._ck(self.lib.rmhmc_smc_cess_dev(self._h, lw.data_ptr(), ll.data_ptr(), lw.numel(), d.size, _ptr(d), part.data_ptr()))
+        return part
+
+    def smc_choose_delta(self, logw, loglik, remaining, rho):
+        """the search for the next temperature step (include/rmhmc_smc.h section 2): dict(delta, frac, flags)"""
+        self._need_smc()
+        lw, ll = self._smc_vec("smc_choose_delta", logw), self._smc_vec("smc_choose_delta", loglik)
+        if ll.shape != lw.shape:
+            raise ValueError("smc_choose_delta: logw and loglik of one length required")
+        d = C.c_double(0.0); f = C.c_double(0.0); fl = C.c_int32(0)
+        self._ck(self.lib.rmhmc_smc_choose_delta_dev(self._h, lw.data_ptr(), ll.data_ptr(), lw.numel(), float(remaining), float(rho),
+                                                     C.cast(C.byref(d), _dp), C.cast(C.byref(f), _dp), C.cast(C.byref(fl), _ip)))
+        return dict(delta=d.value, frac=f.value, flags=fl.value)
+
+    def smc_reweight(self, logw, loglik, delta):
+        """logw += delta loglik in place where loglik is finite, -inf where it is not (NaN stays); returns logw"""
+        self._need_smc()
+        ll = self._smc_vec("smc_reweight", loglik)
+        if not logw.is_contiguous() or self._smc_vec("smc_reweight", logw).shape != ll.shape:
+            raise ValueError("smc_reweight: contiguous logw and loglik of one length required")
+        self._ck(self.lib.rmhmc_smc_reweight_dev(self._h, logw.data_ptr(), ll.data_ptr(), logw.numel(), float(delta)))
+        return logw
+
+    def smc_quantise(self, logw, a):
+        """q [n] (int64 tensor holding the uint64 values, all <= 2^40) = floor(2^40 exp(min(logw - a, 0))), 0 for NaN and -inf"""
+        import torch
+        self._need_smc()
+        lw = self._smc_vec("smc_quantise", logw)
+        q = torch.empty(lw.numel(), dtype=torch.int64, device=lw.device)
+        self._ck(self.lib.rmhmc_smc_quantise_dev(self._h, lw.data_ptr(), lw.numel(), float(a), q.data_ptr()))
+        return q
+
+    def smc_ancestors(self, q, U, out=None):
+        """anc [n] (int32 tensor) of systematic resampling on the integers q [n] (int64 tensor, entries 0 .. 2^40) with the 32-bit offset U
+        (include/rmhmc_smc.h section 4); out: the tensor to write into"""
+        import torch
+        self._need_smc()
+        q = self._smc_vec("smc_ancestors", q, torch.int64)
+        if int(U) != U or not 0 <= U < 2 ** 32:
+            raise ValueError("smc_ancestors: U is a 32-bit unsigned")
+        anc = out if out is not None else torch.empty(q.numel(), dtype=torch.int32, device=q.device)
+        if anc.dtype != torch.int32 or anc.shape != q.shape or anc.device != q.device or not anc.is_contiguous():
+            raise ValueError("smc_ancestors: out must be a contiguous int32 tensor [n] beside q")
+        if anc.is_cuda:
+            torch.cuda.current_stream(anc.device).synchronize()
+        self._ck(self.lib.rmhmc_smc_ancestors_dev(self._h, q.data_ptr(), q.numel(), int(U), anc.data_ptr()))
+        return anc
+
+    def smc_run(self, rho=0.9, tau=0.5, T_max=10000, stage_len=1, mass_every=1, H_lik=None, L=6, eps=0.5, *, beta0=0.0, seed=0, chain_offset=0,
+                theta0=None):
+        """rmhmc_smc_run: the annealing of ais_run on a ladder chosen stage by stage so that the conditional ESS of the step is rho n,
+        resampling (systematic, on integers) when the weight-ESS falls below tau n; mass_every 0: no stage installs a mass.  Returns
+        dict(T, beta [T], cess [T], ess [T], flags [T], accept_trace [T], logw [n], theta [n][D], log_z (NaN if T_max stages did not
+        reach beta = 1), se (NaN if a stage resampled), partial [5], seconds, and the AIS_KEYS of ais_finish on the partial)."""
+        self._need_smc()
+        n, D = self.n, self.D
+        if int(T_max) != T_max or not 1 <= T_max < 2 ** 31:
+            raise ValueError("smc_run: T_max must be a number of stages >= 1")
+        T_max = int(T_max)
+        H = None if H_lik is None else _f64(H_lik, (D, D))
+        th = None if theta0 is None else _f64(np.broadcast_to(theta0, (n, D)))
+        T = C.c_int32(0); lz = C.c_double(0.0); se = C.c_double(0.0); secs = C.c_double(0.0)
+        beta = np.full(T_max, np.nan); cess = np.full(T_max, np.nan); ess = np.full(T_max, np.nan); trace = np.full(T_max, np.nan)
+        flags = np.zeros(T_max, dtype=np.int32)
+        logw = np.empty(n); theta = np.empty((n, D)); part = np.empty(5)
+        self._ck(self.lib.rmhmc_smc_run(self._h, _ptr(th), float(beta0), float(rho), float(tau), T_max, int(stage_len), int(mass_every), _ptr(H),
+                                        int(L), float(eps), int(seed) % 2 ** 64, int(chain_offset), C.cast(C.byref(T), _ip), _ptr(beta),
+                                        _ptr(cess), _ptr(ess), _ptr(flags, _ip), _ptr(trace), _ptr(logw), _ptr(theta),
+                                        C.cast(C.byref(lz), _dp), C.cast(C.byref(se), _dp), _ptr(part), C.cast(C.byref(secs), _dp)))
+        k = T.value
+        out = dict(T=k, beta=beta[:k].copy(), cess=cess[:k].copy(), ess=ess[:k].copy(), flags=flags[:k].copy(), accept_trace=trace[:k].copy(),
+                   logw=logw, theta=theta, log_z=lz.value, partial=part, seconds=secs.value)
+        out.update(ais_finish([part], lib=self.rl))
+        out["se"] = se.value
         return out
 
     # ---- posterior predictive probabilities of new rows (include/rmhmc_pred.h) -----------
@@ -1317,6 +1445,34 @@ def ais_finish(partials, lib=None):
     if rc != 0:
         raise RmhmcError(rc, lib.lib.rmhmc_last_error(None).decode())
     return dict(log_mean_w=lm.value, se=se.value, weight_ess=ess.value, m=m.value, n_nan=nn.value, merged=merged)
+
+
+def smc_cess_finish(partials, lib=None):
+    """rmhmc_smc_cess_finish (include/rmhmc_smc.h): the conditional-ESS partials ([2 + 4 J] each: torch tensors on any device or NumPy
+    arrays) merged in the order given and finished on the host.  Returns dict(frac [J]: cess / n of every candidate, merged)."""
+    lib = lib if lib is not None else load_hip_library()
+    if not lib.has_smc:
+        raise RmhmcError(-4, "%s does not export adaptive sequential Monte Carlo (include/rmhmc_smc.h)" % lib.path)
+    parts = [_f64(p if isinstance(p, np.ndarray) else p.detach().cpu().numpy()) for p in partials]
+    if (not parts or parts[0].ndim != 1 or any(p.shape != parts[0].shape for p in parts) or (parts[0].size - 2) % 4
+            or not 1 <= (parts[0].size - 2) // 4 <= SMC_MAX_J):
+        raise ValueError("smc_cess_finish: partials of one shape [2 + 4 J], 1 <= J <= %d, required" % SMC_MAX_J)
+    J = (parts[0].size - 2) // 4
+    ptrs = (_dp * len(parts))(*[_ptr(p) for p in parts])
+    merged = np.empty(2 + 4 * J); frac = np.empty(J)
+    rc = lib.lib.rmhmc_smc_cess_finish(ptrs, len(parts), J, _ptr(merged), _ptr(frac))
+    if rc != 0:
+        raise RmhmcError(rc, lib.lib.rmhmc_last_error(None).decode())
+    return dict(frac=frac, merged=merged)
+
+
+def smc_resample_u(seed, k):
+    """the 32-bit offset of the resampling of stage k of rmhmc_smc_run: the high half of splitmix64(seed + 0x9E3779B97F4A7C15 (k + 1))"""
+    m = 2 ** 64 - 1
+    z = (int(seed) + 0x9E3779B97F4A7C15 * (int(k) + 1) + 0x9E3779B97F4A7C15) & m
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+    return (z ^ (z >> 31)) >> 32
 
 
 def pred_finish(partials, lib=None):

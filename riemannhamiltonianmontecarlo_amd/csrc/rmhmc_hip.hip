@@ -15,6 +15,7 @@
 #include "../../include/rmhmc_adapt.h"
 #include "../../include/rmhmc_ais.h"
 #include "../../include/rmhmc_pred.h"
+#include "../../include/rmhmc_smc.h"
 #include "plan.h"
 #include "mass.h"
 #include "kernels.hip.h"
@@ -31,6 +32,7 @@
 #include "adapt.hip.h"
 #include "ais.hip.h"
 #include "pred.hip.h"
+#include "smc.hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -3156,6 +3158,264 @@ int rmhmc_pred_finish(const double* const* partials, int32_t k, int64_t R, doubl
                       double* lpd_total, int64_t* draws_used) {
   const int rc = pred_finish(partials, k, R, merged, prob, pvar, lpd, lpd_total, draws_used);
   return rc == RMHMC_OK ? rc : fail(nullptr, rc, rc == RMHMC_ERR_NOMEM ? "pred_finish: out of memory" : "pred_finish: need k >= 1, R >= 1 and no NULL partial");
+}
+
+}  // extern "C"
+
+// ---- the evidence by adaptive sequential Monte Carlo (include/rmhmc_smc.h, smc.h, smc.hip.h) ------------------------------------------------
+namespace {
+
+// a device buffer of one call
+struct SmcScratch {
+  void* p = nullptr;
+  ~SmcScratch() { if (p) (void)hipFree(p); }
+};
+
+// doubles of scratch that smc_cess needs for J candidates: blk [nb][NQ], sums [nb][NQ][2]
+size_t smc_cess_scratch(size_t n, int J) {
+  int64_t nb, pb;
+  ais_plan((int64_t)n, &nb, &pb);
+  const int JT = J <= 1 ? 1 : J <= 4 ? 4 : J <= 16 ? 16 : 32;
+  return 3 * (size_t)nb * (size_t)(1 + 2 * JT);
+}
+// the conditional-ESS partial of (logw, ll) [n] at the J candidates delta (checked) -> d_partial [2 + 4 J], all in device memory; d_scr:
+// smc_cess_scratch doubles, or nullptr: the call's own; synchronises, unless the caller owns the scratch and waits for the stream itself
+int smc_cess(rmhmc_ctx* ctx, const double* d_lw, const double* d_ll, size_t n, int J, const double* delta, double* d_partial, double* d_scr = nullptr) {
+  const bool wait = d_scr == nullptr;
+  int64_t nb, pb;
+  ais_plan((int64_t)n, &nb, &pb);
+  const int JT = J <= 1 ? 1 : J <= 4 ? 4 : J <= 16 ? 16 : 32;
+  const int NQ = 1 + 2 * JT;
+  SmcDeltas dl;
+  for (int j = 0; j < RMHMC_SMC_MAX_J; ++j) dl.d[j] = delta[j < J ? j : J - 1];
+  SmcScratch scr;
+  if (!d_scr) {
+    HIPCK(hipMalloc(&scr.p, sizeof(double) * smc_cess_scratch(n, J)));
+    d_scr = (double*)scr.p;
+  }
+  double* d_blk = d_scr;
+  double* d_sums = d_blk + (size_t)nb * NQ;
+  launch(ctx, "smc", [&](hipStream_t st) {
+    switch (JT) {
+#define SMC_CASE(JT_)                                                                                                                        \
+  case JT_:                                                                                                                                  \
+    hipLaunchKernelGGL(k_smc_cess_max<JT_>, dim3((unsigned)nb), dim3(256), 0, st, d_lw, d_ll, n, (size_t)pb, dl, d_blk);                        \
+    hipLaunchKernelGGL(k_smc_cess_sums<JT_>, dim3((unsigned)nb), dim3(256), 0, st, d_lw, d_ll, n, (size_t)pb, dl, (const double*)d_blk, (int)nb, \
+                       d_sums);                                                                                                              \
+    break
+      SMC_CASE(1); SMC_CASE(4); SMC_CASE(16);
+      default: SMC_CASE(32);
+#undef SMC_CASE
+    }
+    hipLaunchKernelGGL(k_smc_cess_fin, dim3(1), dim3(128), 0, st, (const double*)d_blk, (const double*)d_sums, (int)nb, NQ, 1 + 2 * J, d_partial);
+  });
+  const hipError_t e = hipGetLastError();
+  const int rs = wait ? sync(ctx) : RMHMC_OK;
+  if (e != hipSuccess) return fail(ctx, RMHMC_ERR_RUNTIME, std::string(hipGetErrorString(e)) + " in smc_cess");
+  return rs;
+}
+
+// the search of include/rmhmc_smc.h section 2 (arguments checked); d_part: device scratch of 2 + 4 RMHMC_SMC_J doubles followed by
+// smc_cess_scratch(n, RMHMC_SMC_J) more
+int smc_choose_delta(rmhmc_ctx* ctx, const double* d_lw, const double* d_ll, size_t n, double remaining, double rho, double* d_part, double* delta_out,
+                     double* frac_out, int32_t* flags_out) {
+  smc_search s;
+  smc_search_init(&s, remaining, rho);
+  double grid[RMHMC_SMC_J], frac[RMHMC_SMC_J], part[2 + 4 * RMHMC_SMC_J];
+  const double* parts[1] = {part};
+  while (!s.done) {
+    smc_search_grid(&s, grid);
+    RC(smc_cess(ctx, d_lw, d_ll, n, RMHMC_SMC_J, grid, d_part, d_part + 2 + 4 * RMHMC_SMC_J));
+    RC(download(ctx, part, (const double*)d_part, (size_t)(2 + 4 * RMHMC_SMC_J)));
+    RC(sync(ctx));
+    (void)smc_cess_finish(parts, 1, RMHMC_SMC_J, nullptr, frac);
+    smc_search_step(&s, grid, frac);
+  }
+  if (delta_out) *delta_out = s.delta;
+  if (frac_out) *frac_out = s.frac;
+  if (flags_out) *flags_out = s.flags;
+  return RMHMC_OK;
+}
+
+// wait = false: queued on the stream, for a caller that goes on in it
+int smc_reweight(rmhmc_ctx* ctx, double* d_lw, const double* d_ll, size_t n, double delta, bool wait = true) {
+  launch(ctx, "smc", [&](hipStream_t st) {
+    hipLaunchKernelGGL(k_smc_reweight, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_lw, d_ll, n, delta);
+  });
+  HIPCK(hipGetLastError());
+  return wait ? sync(ctx) : RMHMC_OK;
+}
+
+int smc_quantise(rmhmc_ctx* ctx, const double* d_lw, size_t n, double a, uint64_t* d_q, bool wait = true) {
+  launch(ctx, "smc", [&](hipStream_t st) {
+    hipLaunchKernelGGL(k_smc_quantise, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_lw, n, a, (unsigned long long*)d_q);
+  });
+  HIPCK(hipGetLastError());
+  return wait ? sync(ctx) : RMHMC_OK;
+}
+
+// anc of include/rmhmc_smc.h section 4 (1 <= n <= 2^20 checked); a refusal leaves d_anc untouched
+int smc_ancestors(rmhmc_ctx* ctx, const uint64_t* d_q, size_t n, uint32_t U, int32_t* d_anc) {
+  int64_t nb, pb;
+  smc_scan_plan((int64_t)n, &nb, &pb);
+  SmcScratch scr;  // C [n], blk_sum [nb], blk_bad [nb], off [nb], head [2]
+  HIPCK(hipMalloc(&scr.p, sizeof(unsigned long long) * (n + 3 * (size_t)nb + 2)));
+  unsigned long long* d_C = (unsigned long long*)scr.p;
+  unsigned long long *d_sum = d_C + n, *d_bad = d_sum + nb, *d_off = d_bad + nb, *d_head = d_off + nb;
+  launch(ctx, "smc", [&](hipStream_t st) {
+    hipLaunchKernelGGL(k_smc_scan_blocks, dim3((unsigned)nb), dim3(256), 0, st, (const unsigned long long*)d_q, n, d_C, d_sum, d_bad);
+    hipLaunchKernelGGL(k_smc_scan_offsets, dim3(1), dim3(256), 0, st, (const unsigned long long*)d_sum, (const unsigned long long*)d_bad, (int)nb, d_off,
+                       d_head);
+  });
+  HIPCK(hipGetLastError());
+  unsigned long long head[2] = {0ull, 0ull};
+  RC(download(ctx, head, (const unsigned long long*)d_head, (size_t)2));
+  RC(sync(ctx));
+  if (head[1] != 0ull) return fail(ctx, RMHMC_ERR_INVALID, "smc_ancestors: an entry of q is above 2^40");
+  if (head[0] == 0ull) return fail(ctx, RMHMC_ERR_INVALID, "smc_ancestors: every q is 0 (Q = 0)");
+  launch(ctx, "smc", [&](hipStream_t st) {
+    hipLaunchKernelGGL(k_smc_ancestors, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const unsigned long long*)d_C, (const unsigned long long*)d_off,
+                       n, (unsigned int)U, head[0], (int*)d_anc);
+  });
+  HIPCK(hipGetLastError());
+  return sync(ctx);
+}
+
+}  // namespace
+
+extern "C" {
+
+int rmhmc_smc_cess_dev(rmhmc_ctx* ctx, const double* logw_dev, const double* ll_dev, int64_t n, int32_t J, const double* delta, double* partial_dev) {
+  if (!ctx || !logw_dev || !ll_dev || !partial_dev) return fail(ctx, RMHMC_ERR_INVALID, "smc_cess_dev: need a context, logw, ll and a partial");
+  if (const char* why = smc_check_cess(n, J, delta)) return fail(ctx, RMHMC_ERR_INVALID, std::string("smc_cess_dev: ") + why);
+  HIPCK(hipSetDevice(ctx->device));
+  return smc_cess(ctx, logw_dev, ll_dev, (size_t)n, J, delta, partial_dev);
+}
+
+int rmhmc_smc_cess_finish(const double* const* partials, int32_t k, int32_t J, double* merged, double* frac) {
+  const int rc = smc_cess_finish(partials, k, J, merged, frac);
+  return rc == RMHMC_OK ? rc : fail(nullptr, rc, "smc_cess_finish: need k >= 1, 1 <= J <= 32 and no NULL partial");
+}
+
+int rmhmc_smc_choose_delta_dev(rmhmc_ctx* ctx, const double* logw_dev, const double* ll_dev, int64_t n, double remaining, double rho, double* delta_out,
+                               double* frac_out, int32_t* flags_out) {
+  if (!ctx || !logw_dev || !ll_dev) return fail(ctx, RMHMC_ERR_INVALID, "smc_choose_delta_dev: need a context, logw and ll");
+  if (const char* why = smc_check_search(n, remaining, rho)) return fail(ctx, RMHMC_ERR_INVALID, std::string("smc_choose_delta_dev: ") + why);
+  HIPCK(hipSetDevice(ctx->device));
+  SmcScratch part;
+  HIPCK(hipMalloc(&part.p, sizeof(double) * (2 + 4 * RMHMC_SMC_J + smc_cess_scratch((size_t)n, RMHMC_SMC_J))));
+  return smc_choose_delta(ctx, logw_dev, ll_dev, (size_t)n, remaining, rho, (double*)part.p, delta_out, frac_out, flags_out);
+}
+
+int rmhmc_smc_reweight_dev(rmhmc_ctx* ctx, double* logw_dev, const double* ll_dev, int64_t n, double delta) {
+  if (!ctx || !logw_dev || !ll_dev || n < 1 || !std::isfinite(delta))
+    return fail(ctx, RMHMC_ERR_INVALID, "smc_reweight_dev: need a context, logw, ll, n >= 1 and a finite delta");
+  HIPCK(hipSetDevice(ctx->device));
+  return smc_reweight(ctx, logw_dev, ll_dev, (size_t)n, delta);
+}
+
+int rmhmc_smc_quantise_dev(rmhmc_ctx* ctx, const double* logw_dev, int64_t n, double a, uint64_t* q_dev) {
+  if (!ctx || !logw_dev || !q_dev || n < 1 || a != a) return fail(ctx, RMHMC_ERR_INVALID, "smc_quantise_dev: need a context, logw, q, n >= 1 and a maximum");
+  HIPCK(hipSetDevice(ctx->device));
+  return smc_quantise(ctx, logw_dev, (size_t)n, a, q_dev);
+}
+
+int rmhmc_smc_ancestors_dev(rmhmc_ctx* ctx, const uint64_t* q_dev, int64_t n, uint32_t U, int32_t* anc_dev) {
+  if (!ctx || !q_dev || !anc_dev) return fail(ctx, RMHMC_ERR_INVALID, "smc_ancestors_dev: need a context, q and anc");
+  if (const int rc = smc_check_ancestors(n))
+    return fail(ctx, rc, rc == RMHMC_ERR_UNSUPPORTED ? "smc_ancestors_dev: n <= 2^20" : "smc_ancestors_dev: need n >= 1");
+  HIPCK(hipSetDevice(ctx->device));
+  return smc_ancestors(ctx, q_dev, (size_t)n, U, anc_dev);
+}
+
+int rmhmc_smc_run(rmhmc_ctx* ctx, const double* theta0, double beta0, double rho, double tau, int32_t T_max, int64_t stage_len, int64_t mass_every,
+                  const double* H_lik, int32_t L, double eps, uint64_t seed, int64_t chain_offset, int32_t* T_out, double* beta_out, double* cess_out,
+                  double* ess_out, int32_t* flags_out, double* accept_trace, double* logw_out, double* theta_out, double* log_z_out, double* se_out,
+                  double* partial_out, double* seconds_out) {
+  NEED_DATA(ctx);
+  const auto t_start = std::chrono::steady_clock::now();
+  if (const char* why = smc_check_run(theta0 != nullptr, beta0, rho, tau, T_max, stage_len, mass_every, H_lik != nullptr, L))
+    return fail(ctx, RMHMC_ERR_INVALID, std::string("smc_run: ") + why);
+  if (!ctx->have_mass) return fail(ctx, RMHMC_ERR_INVALID, "smc_run: rmhmc_phmc_set_mass has not been called");
+  if (tau > 0.0 && ctx->n > RMHMC_SMC_MAX_N) return fail(ctx, RMHMC_ERR_UNSUPPORTED, "smc_run: resampling needs n <= 2^20 chains");
+  ctx->chains_ready = false;
+  RC(ais_buffers(ctx));
+  const size_t n = ctx->n;
+  Group& g = ctx->batch;
+  SmcScratch scr;  // the weight partial [5], the conditional-ESS partial [2 + 4 J] and its scratch, q [n], anc [n]
+  const size_t head = 5 + 2 + 4 * RMHMC_SMC_J + smc_cess_scratch(n, RMHMC_SMC_J);
+  HIPCK(hipMalloc(&scr.p, sizeof(double) * (head + n) + sizeof(int32_t) * n));
+  double* d_part = (double*)scr.p;
+  double* d_cess = d_part + 5;
+  uint64_t* d_q = (uint64_t*)(d_part + head);
+  int32_t* d_anc = (int32_t*)(d_q + n);
+  HIPCK(hipMemsetAsync(ctx->d_ais_logw, 0, sizeof(double) * n, ctx->stream));
+  if (theta0) RC(upload_vec(ctx, g.ch.trj.w, theta0));
+  else launch_ais_prior(ctx, seed, chain_offset, g.ch.trj.w, ctx->DP);
+  RC(tphmc_init_dev(ctx, beta0, nullptr, 0.0));  // loglik at the start -> d_ais_ll; trj -> cur
+  std::vector<long long> acc(accept_trace ? n : 0);
+  std::vector<double> mass, Lm, Mi;
+  double part[5], log_mean_w = NAN, ess = NAN, se = NAN;
+  const double* parts[1] = {part};
+  auto weight_partial = [&]() -> int {
+    RC(ais_partial(ctx, ctx->d_ais_logw, n, d_part));
+    RC(download(ctx, part, (const double*)d_part, (size_t)5));
+    RC(sync(ctx));
+    return ais_finish(parts, 1, nullptr, &log_mean_w, &se, &ess, nullptr, nullptr);
+  };
+  double beta = beta0, logz_acc = 0.0;
+  bool resampled_any = false;
+  int32_t k = 0;
+  for (; beta < 1.0 && k < T_max; ++k) {
+    double delta = 0.0, frac = NAN;
+    int32_t flags = 0;
+    RC(smc_choose_delta(ctx, ctx->d_ais_logw, ctx->d_ais_ll, n, 1.0 - beta, rho, d_cess, &delta, &frac, &flags));
+    const double bk = (flags & RMHMC_SMC_LAST) ? 1.0 : beta + delta;
+    RC(smc_reweight(ctx, ctx->d_ais_logw, ctx->d_ais_ll, n, delta, false));
+    RC(weight_partial());
+    if (ess < tau * (double)n) {
+      logz_acc += log_mean_w;
+      RC(smc_quantise(ctx, ctx->d_ais_logw, n, part[2], d_q, false));
+      RC(smc_ancestors(ctx, d_q, n, smc_resample_u(seed, k), d_anc));
+      launch(ctx, "smc", [&](hipStream_t st) {
+        hipLaunchKernelGGL(k_smc_gather, dim3((unsigned)n), dim3(64), 0, st, (const double*)g.ch.cur.w, g.ch.trj.w, (const int*)d_anc, ctx->DP);
+      });
+      HIPCK(hipGetLastError());
+      HIPCK(hipMemsetAsync(ctx->d_ais_logw, 0, sizeof(double) * n, ctx->stream));
+      flags |= RMHMC_SMC_RESAMPLED;
+      resampled_any = true;
+    } else {
+      HIPCK(hipMemcpyAsync(g.ch.trj.w, g.ch.cur.w, sizeof(double) * n * ctx->DP, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    if (smc_stage_mass(k, mass_every, flags)) {  // (a refusal keeps the previous mass, as in rmhmc_ais_run)
+      const char* why = "";
+      if (ais_stage_mass_images(bk, H_lik, ctx->D, ctx->DP, ctx->dd.inv_alpha, mass, Lm, Mi, &why) == RMHMC_OK) RC(install_mass_images(ctx, Lm, Mi));
+    }
+    RC(tphmc_init_dev(ctx, bk, nullptr, 0.0));
+    Run run{TPHMC, L, 0, eps, seed + 1 + (uint64_t)k, chain_offset, nullptr};
+    run.beta = bk;
+    RC(hmc_sample_run(ctx, run, stage_len, 0, nullptr, nullptr));
+    if (accept_trace) {
+      RC(download(ctx, acc.data(), g.ch.accepted, n));
+      RC(sync(ctx));
+      accept_trace[k] = adapt_accept((const int64_t*)acc.data(), (int64_t)n, stage_len);
+    }
+    if (beta_out) beta_out[k] = bk;
+    if (cess_out) cess_out[k] = frac;
+    if (ess_out) ess_out[k] = ess;
+    if (flags_out) flags_out[k] = flags;
+    beta = bk;
+  }
+  RC(weight_partial());
+  if (T_out) *T_out = k;
+  if (logw_out) RC(download(ctx, logw_out, (const double*)ctx->d_ais_logw, n));
+  if (theta_out) RC(download_vec(ctx, theta_out, g.ch.cur.w));
+  RC(sync(ctx));
+  if (log_z_out) *log_z_out = beta < 1.0 ? NAN : logz_acc + log_mean_w;
+  if (se_out) *se_out = resampled_any ? NAN : se;
+  if (partial_out) std::copy(part, part + 5, partial_out);
+  if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+  return RMHMC_OK;
 }
 
 }  // extern "C"
