@@ -242,6 +242,21 @@ SMC_MAX_N = 2 ** 20       # most particles of smc_ancestors (RMHMC_SMC_MAX_N)
 SMC_QBITS = 40            # q = 2^40 at the largest weight (RMHMC_SMC_QBITS)
 SMC_LAST, SMC_FLOOR, SMC_RESAMPLED = 1, 2, 4      # flags of a stage
 
+# the optional headers: key (RmhmcLib.has_<key>, RmhmcLib.need(key)) -> (the header's signatures, what it is called in the "does not
+# export ..." message).  A library has a feature when it exports every symbol of the header.
+FEATURES = {
+    "amh": (AMH_SIGNATURES, "the AMH sampler (include/rmhmc_amh.h)"),
+    "iwls": (IWLS_SIGNATURES, "the IWLS sampler (include/rmhmc_iwls.h)"),
+    "gibbs": (GIBBS_SIGNATURES, "the Gibbs sampler (include/rmhmc_gibbs.h)"),
+    "out": (OUT_SIGNATURES, "the output descriptor (include/rmhmc_out.h)"),
+    "diag": (DIAG_SIGNATURES, "the cross-chain diagnostics (include/rmhmc_diag.h)"),
+    "phmc": (PHMC_SIGNATURES, "the fixed-metric HMC sampler (include/rmhmc_phmc.h)"),
+    "adapt": (ADAPT_SIGNATURES, "the warm-up of the fixed-metric HMC sampler (include/rmhmc_adapt.h)"),
+    "ais": (AIS_SIGNATURES, "annealed importance sampling (include/rmhmc_ais.h)"),
+    "pred": (PRED_SIGNATURES, "the posterior predictive probabilities (include/rmhmc_pred.h)"),
+    "smc": (SMC_SIGNATURES, "adaptive sequential Monte Carlo (include/rmhmc_smc.h)"),
+}
+
 
 def ais_schedule(n_temps, ladder="power4", mass_every=1, iters_per_temp=1):
     """(beta [T], stage_len [T], stage_mass [T]) of an annealing run of T = n_temps stages (csrc/ais.h): ladder "power<q>" is
@@ -341,72 +356,30 @@ class RmhmcLib:
             raise FileNotFoundError("rmhmc library not built: %s (run `python -c 'import __graft_entry__ as g; g.build()'`)" % path)
         self.path = path
         self.lib = C.CDLL(path, mode=C.RTLD_LOCAL)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(self.lib, name)  # AttributeError if a declared symbol is missing
-            fn.restype = res
-            fn.argtypes = args
-        self.has_amh = all(hasattr(self.lib, name) for name in AMH_SIGNATURES)
-        if self.has_amh:
-            for name, (res, args) in AMH_SIGNATURES.items():
-                fn = getattr(self.lib, name)
-                fn.restype = res
-                fn.argtypes = args
-        self.has_iwls = all(hasattr(self.lib, name) for name in IWLS_SIGNATURES)
-        if self.has_iwls:
-            for name, (res, args) in IWLS_SIGNATURES.items():
-                fn = getattr(self.lib, name)
-                fn.restype = res
-                fn.argtypes = args
-        self.has_gibbs = all(hasattr(self.lib, name) for name in GIBBS_SIGNATURES)
-        if self.has_gibbs:
-            for name, (res, args) in GIBBS_SIGNATURES.items():
-                fn = getattr(self.lib, name)
-                fn.restype = res
-                fn.argtypes = args
-        self.has_out = all(hasattr(self.lib, name) for name in OUT_SIGNATURES)
-        if self.has_out:
-            for name, (res, args) in OUT_SIGNATURES.items():
-                fn = getattr(self.lib, name)
-                fn.restype = res
-                fn.argtypes = args
-        self.has_diag = all(hasattr(self.lib, name) for name in DIAG_SIGNATURES)
-        if self.has_diag:
-            for name, (res, args) in DIAG_SIGNATURES.items():
-                fn = getattr(self.lib, name)
-                fn.restype = res
-                fn.argtypes = args
-        self.has_phmc = all(hasattr(self.lib, name) for name in PHMC_SIGNATURES)
-        if self.has_phmc:
-            for name, (res, args) in PHMC_SIGNATURES.items():
-                fn = getattr(self.lib, name)
-                fn.restype = res
-                fn.argtypes = args
-        self.has_adapt = all(hasattr(self.lib, name) for name in ADAPT_SIGNATURES)
-        if self.has_adapt:
-            for name, (res, args) in ADAPT_SIGNATURES.items():
-                fn = getattr(self.lib, name)
-                fn.restype = res
-                fn.argtypes = args
-        self.has_ais = all(hasattr(self.lib, name) for name in AIS_SIGNATURES)
-        if self.has_ais:
-            for name, (res, args) in AIS_SIGNATURES.items():
-                fn = getattr(self.lib, name)
-                fn.restype = res
-                fn.argtypes = args
-        self.has_pred = all(hasattr(self.lib, name) for name in PRED_SIGNATURES)
-        if self.has_pred:
-            for name, (res, args) in PRED_SIGNATURES.items():
-                fn = getattr(self.lib, name)
-                fn.restype = res
-                fn.argtypes = args
-        self.has_smc = all(hasattr(self.lib, name) for name in SMC_SIGNATURES)
-        if self.has_smc:
-            for name, (res, args) in SMC_SIGNATURES.items():
-                fn = getattr(self.lib, name)
-                fn.restype = res
-                fn.argtypes = args
+        self._bind(SIGNATURES)   # AttributeError if a declared symbol is missing
+        for key, (sigs, _) in FEATURES.items():
+            has = all(hasattr(self.lib, name) for name in sigs)
+            setattr(self, "has_" + key, has)
+            if has:
+                self._bind(sigs)
         # the HIP library writes its _dev outputs through device pointers of its own GPU; the CPU oracle's "device" is the host
         self.on_gpu = "gfx950" in self.version()
+
+    def _bind(self, sigs):
+        for name, (res, args) in sigs.items():
+            fn = getattr(self.lib, name)
+            fn.restype = res
+            fn.argtypes = args
+
+    def need(self, key):
+        """RmhmcError -4 unless the library has the optional feature `key` of FEATURES"""
+        if not getattr(self, "has_" + key):
+            raise RmhmcError(-4, "%s does not export %s" % (self.path, FEATURES[key][1]))
+
+    def ck(self, rc):
+        """RmhmcError from a failed call that has no context (rmhmc_last_error(NULL))"""
+        if rc != 0:
+            raise RmhmcError(rc, self.lib.rmhmc_last_error(None).decode())
 
     def version(self):
         return self.lib.rmhmc_version().decode()
@@ -429,8 +402,7 @@ class Context:
             rc = self.lib.rmhmc_create_opts(C.byref(self._h), device, self.M, self.D, self.n, F64, self.flags, arr, len(options))
         else:
             rc = self.lib.rmhmc_create(C.byref(self._h), device, self.M, self.D, self.n, F64, self.flags)
-        if rc != 0:
-            raise RmhmcError(rc, self.lib.rmhmc_last_error(None).decode())
+        rl.ck(rc)
 
     def close(self):
         if self._h:
@@ -569,6 +541,22 @@ class Context:
         import torch
         return [torch.empty(shape, dtype=dt, device=device) for shape, dt in shapes]
 
+    def _dev_tensor(self, who, x, what, rank=None, dtype=None):
+        """x as the contiguous torch tensor a <name>_dev entry point reads: on the context's GPU (anywhere for the CPU oracle), of
+        `dtype` (float64 unless it says otherwise) and of `rank` dimensions (None: any), a vector not empty.  ValueError "<who>: <dtype>
+        tensor<what> required" otherwise.  torch's current stream on the tensor's device is synchronised: the library reads the tensor
+        at once on a stream of its own, so whatever produced it must have finished."""
+        import torch
+        dtype = dtype or torch.float64
+        if self.rl.on_gpu and not x.is_cuda:
+            raise ValueError("%s: a tensor on the context's GPU is required" % who)
+        x = x.contiguous()
+        if x.dtype != dtype or (rank is not None and x.dim() != rank) or (rank == 1 and x.numel() < 1):
+            raise ValueError("%s: %s tensor%s required" % (who, str(dtype).replace("torch.", ""), what))
+        if x.is_cuda:
+            torch.cuda.current_stream(x.device).synchronize()
+        return x
+
     def chains_state_dev(self, device):
         import torch
         w, it, acc = self._out_tensors([((self.n, self.D), torch.float64), ((self.n,), torch.int64), ((self.n,), torch.int64)], device)
@@ -648,20 +636,16 @@ class Context:
         return samples, acc, steps, secs.value
 
     # ---- HMC with a fixed dense mass matrix shared by all chains (include/rmhmc_phmc.h) -----------
-    def _need_phmc(self):
-        if not self.rl.has_phmc:
-            raise RmhmcError(-4, "%s does not export the fixed-metric HMC sampler (include/rmhmc_phmc.h)" % self.rl.path)
-
     def phmc_set_mass(self, mass=None):
         """the context's mass matrix: (D, D) symmetric positive definite (the lower triangle is read), None: the identity"""
-        self._need_phmc()
+        self.rl.need("phmc")
         m = None if mass is None else _f64(mass, (self.D, self.D))
         self._ck(self.lib.rmhmc_phmc_set_mass(self._h, _ptr(m)))
 
     def phmc_mode(self, w0=None, max_iter=50, tol=1e-10):
         """posterior mode by damped Newton from w0 (None: zeros): dict(w [D], G [D][D] the metric at w, iters, step: max|s| of the
         last Newton step, converged: step <= tol * max(1, max|w|))"""
-        self._need_phmc()
+        self.rl.need("phmc")
         D = self.D
         w0 = None if w0 is None else _f64(w0, (D,))
         w = np.empty(D); G = np.empty((D, D))
@@ -672,7 +656,7 @@ class Context:
                     converged=bool(step.value <= float(tol) * max(1.0, float(np.abs(w).max()))))
 
     def phmc_transition(self, w, z, u_len, u_acc, L=6, eps=0.5):
-        self._need_phmc()
+        self.rl.need("phmc")
         n, D = self.n, self.D
         w = _f64(w, (n, D)).copy()
         z = _f64(z, (n, D)); u_len = _f64(u_len, (n,)); u_acc = _f64(u_acc, (n,))
@@ -686,30 +670,20 @@ class Context:
                        seed=0, chain_offset=0, theta0=None):
         """One run of the sampler with the context's mass matrix, written out as sample_to writes the others: the requested outputs,
         the counters accepted and leapfrog_steps (same memory space) and seconds."""
-        self._need_phmc()
-        self._need_out()
+        self.rl.need("phmc")
+        self.rl.need("out")
         return self._call_sample_to("rmhmc_phmc_sample_to", PHMC_COUNTERS, (int(L), float(eps)), n_iter, burn_in, where, device, samples,
                                     stats, run_mean, seed, chain_offset, theta0)
 
     # ---- warm-up of the fixed-metric HMC sampler (include/rmhmc_adapt.h) -----------
-    def _need_adapt(self):
-        if not self.rl.has_adapt:
-            raise RmhmcError(-4, "%s does not export the warm-up of the fixed-metric HMC sampler (include/rmhmc_adapt.h)" % self.rl.path)
-
     def cov_partial(self, samples):
         """The mergeable partial [(2 + P), P] (include/rmhmc_adapt.h) of a float64 torch tensor [n][S][P] already on the context's GPU,
         reduced there.  torch's current stream is synchronised first, as in ess_dev."""
         import torch
-        self._need_adapt()
-        if self.rl.on_gpu and not samples.is_cuda:
-            raise ValueError("cov_partial: a tensor on the context's GPU is required")
-        x = samples.contiguous()
-        if x.dtype != torch.float64 or x.dim() != 3:
-            raise ValueError("cov_partial: float64 tensor [n][S][P] required")
+        self.rl.need("adapt")
+        x = self._dev_tensor("cov_partial", samples, " [n][S][P]", 3)
         n, S, P = x.shape
         part = torch.empty((2 + P, P), dtype=torch.float64, device=x.device)
-        if x.is_cuda:
-            torch.cuda.current_stream(x.device).synchronize()
         self._ck(self.lib.rmhmc_cov_partial_dev(self._h, x.data_ptr(), n, S, P, part.data_ptr()))
         return part
 
@@ -727,7 +701,7 @@ class Context:
         schedule).  min_rows: pooled rows a mass update needs, default 10 D.  Returns dict(step_size, mass [D][D] or None when no
         update happened, theta [n][D] the last positions, eps_trace, accept_trace, mass_updated [W], seconds).  The context is left
         with the adapted mass."""
-        self._need_adapt()
+        self.rl.need("adapt")
         n, D = self.n, self.D
         wl = np.ascontiguousarray(win_len, dtype=np.int64).reshape(-1)
         wk = np.ascontiguousarray(win_kind, dtype=np.int32).reshape(-1)
@@ -747,13 +721,9 @@ class Context:
                     accept_trace=acc_trace, mass_updated=upd, seconds=secs.value)
 
     # ---- annealed importance sampling with tempered fixed-metric HMC (include/rmhmc_ais.h) -----------
-    def _need_ais(self):
-        if not self.rl.has_ais:
-            raise RmhmcError(-4, "%s does not export annealed importance sampling (include/rmhmc_ais.h)" % self.rl.path)
-
     def tphmc_transition(self, w, z, u_len, u_acc, L=6, eps=0.5, beta=1.0):
         """phmc_transition on the target tempered by beta; the dict gains loglik0 (at the start) and loglik (at the returned w)"""
-        self._need_ais()
+        self.rl.need("ais")
         n, D = self.n, self.D
         w = _f64(w, (n, D)).copy()
         z = _f64(z, (n, D)); u_len = _f64(u_len, (n,)); u_acc = _f64(u_acc, (n,))
@@ -768,8 +738,8 @@ class Context:
                         run_mean=False, seed=0, chain_offset=0, theta0=None):
         """phmc_sample_to on the target tempered by beta (the power posterior p(t|w)^beta p(w)); the result gains loglik0 [n] (the
         log-likelihood at theta0) and loglik [n] (at the last state), host arrays whatever `where` says"""
-        self._need_ais()
-        self._need_out()
+        self.rl.need("ais")
+        self.rl.need("out")
         ll0 = np.empty(self.n); ll = np.empty(self.n)
         res = self._call_sample_to("rmhmc_tphmc_sample_to", PHMC_COUNTERS, (int(L), float(eps)), n_iter, burn_in, where, device, samples,
                                    stats, run_mean, seed, chain_offset, theta0, back=(float(beta), _ptr(ll0), _ptr(ll)))
@@ -778,7 +748,7 @@ class Context:
 
     def ais_prior(self, seed=0, chain_offset=0):
         """exact draws from the prior N(0, alpha I), [n][D]: the start of an annealing run"""
-        self._need_ais()
+        self.rl.need("ais")
         th = np.empty((self.n, self.D))
         self._ck(self.lib.rmhmc_ais_prior(self._h, int(seed) % 2 ** 64, int(chain_offset), _ptr(th)))
         return th
@@ -787,15 +757,9 @@ class Context:
         """The mergeable partial [5] = (m, n_nan, max, S1, S2) (include/rmhmc_ais.h) of a float64 torch tensor [n] of log weights already
         on the context's GPU, reduced there.  torch's current stream is synchronised first, as in ess_dev."""
         import torch
-        self._need_ais()
-        if self.rl.on_gpu and not logw.is_cuda:
-            raise ValueError("ais_partial: a tensor on the context's GPU is required")
-        x = logw.contiguous()
-        if x.dtype != torch.float64 or x.dim() != 1 or x.numel() < 1:
-            raise ValueError("ais_partial: float64 tensor [n], n >= 1, required")
+        self.rl.need("ais")
+        x = self._dev_tensor("ais_partial", logw, " [n], n >= 1,", 1)
         part = torch.empty(5, dtype=torch.float64, device=x.device)
-        if x.is_cuda:
-            torch.cuda.current_stream(x.device).synchronize()
         self._ck(self.lib.rmhmc_ais_partial_dev(self._h, x.data_ptr(), x.numel(), part.data_ptr()))
         return part
 
@@ -805,7 +769,7 @@ class Context:
         from the prior (beta0 must be 0).  ais_schedule builds the usual (beta, stage_len, stage_mass).  Returns dict(logw [n], theta
         [n][D] the last positions, accept_trace [T], partial [5], seconds, and the AIS_KEYS of ais_finish on the partial).  The context
         is left with the last mass installed."""
-        self._need_ais()
+        self.rl.need("ais")
         n, D = self.n, self.D
         b = _f64(beta).reshape(-1)
         sl = np.ascontiguousarray(stage_len, dtype=np.int64).reshape(-1)
@@ -823,28 +787,14 @@ class Context:
         return out
 
     # ---- the evidence by adaptive sequential Monte Carlo (include/rmhmc_smc.h) -----------
-    def _need_smc(self):
-        if not self.rl.has_smc:
-            raise RmhmcError(-4, "%s does not export adaptive sequential Monte Carlo (include/rmhmc_smc.h)" % self.rl.path)
-
     def _smc_vec(self, who, x, dtype=None):
-        """a contiguous 1-d torch tensor on the context's GPU, n >= 1 (float64 unless dtype says otherwise); torch's current stream is
-        synchronised, as in ess_dev"""
-        import torch
-        if self.rl.on_gpu and not x.is_cuda:
-            raise ValueError("%s: a tensor on the context's GPU is required" % who)
-        x = x.contiguous()
-        if x.dtype != (dtype or torch.float64) or x.dim() != 1 or x.numel() < 1:
-            raise ValueError("%s: %s tensor [n], n >= 1, required" % (who, str(dtype or torch.float64).replace("torch.", "")))
-        if x.is_cuda:
-            torch.cuda.current_stream(x.device).synchronize()
-        return x
+        return self._dev_tensor(who, x, " [n], n >= 1,", 1, dtype)
 
     def smc_cess(self, logw, loglik, delta):
         """The mergeable conditional-ESS partial [2 + 4 J] = (a0, S0, then per candidate a1, S1, a2, S2) (include/rmhmc_smc.h) of the log
         weights and log-likelihoods (float64 torch tensors [n] on the context's GPU) at the J <= 32 candidate steps delta (host)."""
         import torch
-        self._need_smc()
+        self.rl.need("smc")
         lw, ll = self._smc_vec("smc_cess", logw), self._smc_vec("smc_cess", loglik)
         d = _f64(delta).reshape(-1)
         if ll.shape != lw.shape or not 1 <= d.size <= SMC_MAX_J:
@@ -855,7 +805,7 @@ class Context:
 
     def smc_choose_delta(self, logw, loglik, remaining, rho):
         """the search for the next temperature step (include/rmhmc_smc.h section 2): dict(delta, frac, flags)"""
-        self._need_smc()
+        self.rl.need("smc")
         lw, ll = self._smc_vec("smc_choose_delta", logw), self._smc_vec("smc_choose_delta", loglik)
         if ll.shape != lw.shape:
             raise ValueError("smc_choose_delta: logw and loglik of one length required")
@@ -866,7 +816,7 @@ class Context:
 
     def smc_reweight(self, logw, loglik, delta):
         """logw += delta loglik in place where loglik is finite, -inf where it is not (NaN stays); returns logw"""
-        self._need_smc()
+        self.rl.need("smc")
         ll = self._smc_vec("smc_reweight", loglik)
         if not logw.is_contiguous() or self._smc_vec("smc_reweight", logw).shape != ll.shape:
             raise ValueError("smc_reweight: contiguous logw and loglik of one length required")
@@ -876,7 +826,7 @@ class Context:
     def smc_quantise(self, logw, a):
         """q [n] (int64 tensor holding the uint64 values, all <= 2^40) = floor(2^40 exp(min(logw - a, 0))), 0 for NaN and -inf"""
         import torch
-        self._need_smc()
+        self.rl.need("smc")
         lw = self._smc_vec("smc_quantise", logw)
         q = torch.empty(lw.numel(), dtype=torch.int64, device=lw.device)
         self._ck(self.lib.rmhmc_smc_quantise_dev(self._h, lw.data_ptr(), lw.numel(), float(a), q.data_ptr()))
@@ -886,7 +836,7 @@ class Context:
         """anc [n] (int32 tensor) of systematic resampling on the integers q [n] (int64 tensor, entries 0 .. 2^40) with the 32-bit offset U
         (include/rmhmc_smc.h section 4); out: the tensor to write into"""
         import torch
-        self._need_smc()
+        self.rl.need("smc")
         q = self._smc_vec("smc_ancestors", q, torch.int64)
         if int(U) != U or not 0 <= U < 2 ** 32:
             raise ValueError("smc_ancestors: U is a 32-bit unsigned")
@@ -904,7 +854,7 @@ class Context:
         resampling (systematic, on integers) when the weight-ESS falls below tau n; mass_every 0: no stage installs a mass.  Returns
         dict(T, beta [T], cess [T], ess [T], flags [T], accept_trace [T], logw [n], theta [n][D], log_z (NaN if T_max stages did not
         reach beta = 1), se (NaN if a stage resampled), partial [5], seconds, and the AIS_KEYS of ais_finish on the partial)."""
-        self._need_smc()
+        self.rl.need("smc")
         n, D = self.n, self.D
         if int(T_max) != T_max or not 1 <= T_max < 2 ** 31:
             raise ValueError("smc_run: T_max must be a number of stages >= 1")
@@ -927,21 +877,13 @@ class Context:
         return out
 
     # ---- posterior predictive probabilities of new rows (include/rmhmc_pred.h) -----------
-    def _need_pred(self):
-        if not self.rl.has_pred:
-            raise RmhmcError(-4, "%s does not export the posterior predictive probabilities (include/rmhmc_pred.h)" % self.rl.path)
-
     def predict_partial(self, samples, xnew, tnew=None):
         """The mergeable partial [4, R] = (m, S1, S2, SQ) (include/rmhmc_pred.h) of the draws of a float64 torch tensor [n][S][D] already
         on the context's GPU for the rows xnew [R][D] (host) and the held-out labels tnew [R] (host, 0 or 1) or None, reduced there.
         torch's current stream is synchronised first, as in ess_dev."""
         import torch
-        self._need_pred()
-        if self.rl.on_gpu and not samples.is_cuda:
-            raise ValueError("predict_partial: a tensor on the context's GPU is required")
-        w = samples.contiguous()
-        if w.dtype != torch.float64 or w.dim() != 3:
-            raise ValueError("predict_partial: float64 tensor [n][S][D] required")
+        self.rl.need("pred")
+        w = self._dev_tensor("predict_partial", samples, " [n][S][D]", 3)
         n, S, D = w.shape
         x = _f64(xnew)
         if x.ndim != 2 or x.shape[1] != D:
@@ -951,8 +893,6 @@ class Context:
         if t is not None and t.shape[0] != R:
             raise ValueError("predict_partial: tnew must have R entries")
         part = torch.empty((4, R), dtype=torch.float64, device=w.device)
-        if w.is_cuda:
-            torch.cuda.current_stream(w.device).synchronize()
         self._ck(self.lib.rmhmc_pred_partial_dev(self._h, w.data_ptr(), n, S, D, _ptr(x), _ptr(t), R, part.data_ptr()))
         return part
 
@@ -968,13 +908,9 @@ class Context:
         return res
 
     # ---- adaptive Metropolis (code/metropolis.py, include/rmhmc_amh.h) -----------
-    def _need_amh(self):
-        if not self.rl.has_amh:
-            raise RmhmcError(-4, "%s does not export the AMH sampler (include/rmhmc_amh.h)" % self.rl.path)
-
     def amh_sample(self, n_iter, burn_in, seed=0, chain_offset=0, theta0=None):
         """returns (samples [n][n_iter-burn_in][D], accepted proposals [n], final ProposalSD [n][D], seconds after burn-in)"""
-        self._need_amh()
+        self.rl.need("amh")
         n, D = self.n, self.D
         S = int(n_iter) - int(burn_in)
         if S <= 0 or int(burn_in) < 0:
@@ -988,7 +924,7 @@ class Context:
     def amh_replay(self, n_iter, burn_in, z, u, theta0=None):
         """z, u: [n][n_iter][D] recorded draws (u NaN where none was drawn).  Returns dict(w [n][n_iter][D], ljl [n][n_iter],
         sd [n][D], accepted / u_read [n][n_iter][D] bool)"""
-        self._need_amh()
+        self.rl.need("amh")
         n, D, T = self.n, self.D, int(n_iter)
         z = _f64(z, (n, T, D)); u = _f64(u, (n, T, D))
         th = None if theta0 is None else _f64(np.broadcast_to(theta0, (n, D)))
@@ -998,13 +934,9 @@ class Context:
         return dict(w=w, ljl=ljl, sd=sd, accepted=(dec & 1) != 0, u_read=(dec & 2) != 0)
 
     # ---- IWLS Metropolis-Hastings (code/iwls.py, include/rmhmc_iwls.h) ----------
-    def _need_iwls(self):
-        if not self.rl.has_iwls:
-            raise RmhmcError(-4, "%s does not export the IWLS sampler (include/rmhmc_iwls.h)" % self.rl.path)
-
     def iwls_sample(self, n_iter, burn_in, compat=True, seed=0, chain_offset=0, theta0=None):
         """returns (samples [n][n_iter-burn_in][D], accepted proposals [n], saturated proposals [n], seconds from iteration burn_in)"""
-        self._need_iwls()
+        self.rl.need("iwls")
         n, D = self.n, self.D
         S = int(n_iter) - int(burn_in)
         if S <= 0 or int(burn_in) < 0:
@@ -1018,7 +950,7 @@ class Context:
     def iwls_replay(self, w_prop, u, compat=True, theta0=None):
         """w_prop [n][T][D] given proposals, u [n][T] uniforms (NaN where none was drawn).  Returns dict(w, mean [n][T][D], ljl,
         ratio [n][T] after every iteration, accepted / u_read / saturated [n][T] bool)"""
-        self._need_iwls()
+        self.rl.need("iwls")
         n, D = self.n, self.D
         w_prop = _f64(w_prop)
         T = w_prop.size // (n * D)
@@ -1031,15 +963,11 @@ class Context:
         return dict(w=w, mean=mean, ljl=ljl, ratio=ratio, accepted=(dec & 1) != 0, u_read=(dec & 2) != 0, saturated=(dec & 4) != 0)
 
     # ---- auxiliary-variable Gibbs sampler (code/gibbs_sampler.py, include/rmhmc_gibbs.h) ----------
-    def _need_gibbs(self):
-        if not self.rl.has_gibbs:
-            raise RmhmcError(-4, "%s does not export the Gibbs sampler (include/rmhmc_gibbs.h)" % self.rl.path)
-
     def gibbs_sample(self, n_iter, burn_in, seed=0, chain_offset=0, state=False):
         """returns dict(samples [n][n_iter-burn_in][D], capped [n]: rows that reached a bound (expected 0), stopped [n]: -1, or the
         iteration at which the chain stopped where the reference would have (include/rmhmc_gibbs.h; its later rows are NaN), seconds
         from iteration burn_in; state=True adds Z and lam [n][N] after the last iteration)"""
-        self._need_gibbs()
+        self.rl.need("gibbs")
         n, D = self.n, self.D
         S = int(n_iter) - int(burn_in)
         if S <= 0 or int(burn_in) < 0:
@@ -1058,7 +986,7 @@ class Context:
         """Recorded draws per chain: u_init [n][N], u_sweep [n][T][N], T [n][T][D], ks_draws [n][total][3], ks_offset [n][T][N+1].
         Returns dict(beta, B [n][T][D] after every iteration (B before the T term), attempts [n][T][N], Z, lam [n][N] after the last
         one, capped [n], status [n]: 1 where the tape ran out of attempts, 2 where a lam_j was not positive and finite: the chain stopped)"""
-        self._need_gibbs()
+        self.rl.need("gibbs")
         n, D, N = self.n, self.D, self.M
         u_init = _f64(u_init, (n, N))
         u_sweep = _f64(u_sweep); Tn = u_sweep.size // (n * N)
@@ -1072,10 +1000,6 @@ class Context:
         return dict(beta=beta, B=B, attempts=att, Z=Z, lam=lam, capped=capped, status=status)
 
     # ---- output descriptor: every sampler to host or device memory, raw or reduced (include/rmhmc_out.h) ----------
-    def _need_out(self):
-        if not self.rl.has_out:
-            raise RmhmcError(-4, "%s does not export the output descriptor (include/rmhmc_out.h)" % self.rl.path)
-
     def sample_to(self, sampler, n_iter, burn_in, *, where="host", device=None, samples=False, stats=False, run_mean=False,
                   L=None, eps=None, K=None, compat=None, seed=0, chain_offset=0, theta0=None, diagnostics=False, max_lag=None):
         """One run of `sampler` (a key of SAMPLERS_TO) written out as asked: samples [n][S][D]; stats: mean, var, ess [n][D]; run_mean:
@@ -1089,7 +1013,7 @@ class Context:
         ess_pooled, pairs, chains_used as host NumPy arrays [D], and diag_partial, the device tensor a sharded job merges.  The sampler
         then writes its samples to a device tensor whatever `where` and `samples` say (they are returned only if asked, and outputs
         asked on the host are copied there); samples and counters are those of the same call without the keyword, bit for bit."""
-        self._need_out()
+        self.rl.need("out")
         if diagnostics:
             return self._sample_to_diag(sampler, n_iter, burn_in, where, device, samples, max_lag,
                                         dict(stats=stats, run_mean=run_mean, L=L, eps=eps, K=K, compat=compat, seed=seed,
@@ -1163,44 +1087,28 @@ class Context:
         (ess, mean, var) tensors [n][P] on the same device.  torch's current stream on that device is synchronised first: the
         library reads the tensor at once on a stream of its own, so whatever produced it must have finished."""
         import torch
-        self._need_out()
-        if self.rl.on_gpu and not samples.is_cuda:
-            raise ValueError("ess_dev: a tensor on the context's GPU is required")
-        x = samples.contiguous()
-        if x.dtype != torch.float64:
-            raise ValueError("ess_dev: float64 tensor required")
+        self.rl.need("out")
+        x = self._dev_tensor("ess_dev", samples, "")
         if x.dim() == 2:
             x = x[None]
         n, S, P = x.shape
         ess, mean, var = self._out_tensors([((n, P), torch.float64)] * 3, x.device)
-        if x.is_cuda:
-            torch.cuda.current_stream(x.device).synchronize()
         self._ck(self.lib.rmhmc_ess_dev(self._h, x.data_ptr(), n, S, P, ess.data_ptr(), mean.data_ptr(), var.data_ptr()))
         return ess, mean, var
 
     # ---- cross-chain diagnostics: split R-hat and the pooled ESS (include/rmhmc_diag.h) ----------
-    def _need_diag(self):
-        if not self.rl.has_diag:
-            raise RmhmcError(-4, "%s does not export the cross-chain diagnostics (include/rmhmc_diag.h)" % self.rl.path)
-
     def diag_partial(self, samples, max_lag=None):
         """The mergeable partial [(4 + T), P] (include/rmhmc_diag.h) of a float64 torch tensor [n][S][P] already on the context's GPU,
         reduced there; T = max_lag + 1, max_lag None or 0: every lag, S // 2 - 1.  torch's current stream is synchronised first, as in
         ess_dev."""
         import torch
-        self._need_diag()
-        if self.rl.on_gpu and not samples.is_cuda:
-            raise ValueError("diag_partial: a tensor on the context's GPU is required")
-        x = samples.contiguous()
-        if x.dtype != torch.float64 or x.dim() != 3:
-            raise ValueError("diag_partial: float64 tensor [n][S][P] required")
+        self.rl.need("diag")
+        x = self._dev_tensor("diag_partial", samples, " [n][S][P]", 3)
         n, S, P = x.shape
         max_lag = 0 if max_lag is None else int(max_lag)
         H = S // 2
         T = (max_lag if max_lag else H - 1) + 1 if 0 <= max_lag < H else 1   # (out of range: the library refuses the call)
         part = torch.empty((4 + T, P), dtype=torch.float64, device=x.device)
-        if x.is_cuda:
-            torch.cuda.current_stream(x.device).synchronize()
         self._ck(self.lib.rmhmc_diag_partial_dev(self._h, x.data_ptr(), n, S, P, max_lag, part.data_ptr()))
         return part
 
@@ -1214,7 +1122,7 @@ class Context:
 
     def _sample_to_diag(self, sampler, n_iter, burn_in, where, device, samples, max_lag, kw):
         import torch
-        self._need_diag()
+        self.rl.need("diag")
         diag_lags(int(n_iter) - int(burn_in), max_lag)   # refused before any sampling work
         host = where in ("host", OUT_HOST)
         if host:
@@ -1339,23 +1247,39 @@ class Context:
         return s.value, k.value
 
 
+def _lib_with(lib, key):
+    """lib, or the product library where it is None; either must have the optional feature `key`"""
+    lib = lib if lib is not None else load_hip_library()
+    lib.need(key)
+    return lib
+
+
+def _finish_call(name, key, partials, lib, ok, refusal):
+    """What the *_finish functions share around their own outputs.  The library (_lib_with) must have the feature `key`.  The partials
+    (torch tensors on any device or NumPy arrays) become float64 host arrays, refused with ValueError(refusal) unless there is one,
+    ok(the first) holds and all have its shape.  Returns (the shape of a partial, call): call(*rest) runs the library's
+    `name`(the pointers to the partials, their number, *rest) and raises RmhmcError where that fails."""
+    lib = _lib_with(lib, key)
+    parts = [_f64(p if isinstance(p, np.ndarray) else p.detach().cpu().numpy()) for p in partials]
+    if not parts or not ok(parts[0]) or any(p.shape != parts[0].shape for p in parts):
+        raise ValueError(refusal)
+    ptrs = (_dp * len(parts))(*[_ptr(p) for p in parts])
+
+    def call(*rest):
+        lib.ck(getattr(lib.lib, name)(ptrs, len(parts), *rest))   # (the closure keeps the arrays behind ptrs alive)
+    return parts[0].shape, call
+
+
 def diag_finish(partials, H, lib=None):
     """rmhmc_diag_finish (include/rmhmc_diag.h): the partials ([(4 + T), P] each: torch tensors on any device or NumPy arrays, all of the
     same shape, from series of H rows) merged in the order given and finished on the host.  Returns dict(rhat, ess_pooled, pairs,
     chains_used: NumPy arrays [P]; merged: the merged partial [(4 + T), P])."""
-    lib = lib if lib is not None else load_hip_library()
-    if not lib.has_diag:
-        raise RmhmcError(-4, "%s does not export the cross-chain diagnostics (include/rmhmc_diag.h)" % lib.path)
-    parts = [_f64(p if isinstance(p, np.ndarray) else p.detach().cpu().numpy()) for p in partials]
-    if not parts or parts[0].ndim != 2 or any(p.shape != parts[0].shape for p in parts):
-        raise ValueError("diag_finish: partials of one shape [(4 + T), P] required")
-    T, P = parts[0].shape[0] - 4, parts[0].shape[1]
-    ptrs = (_dp * len(parts))(*[_ptr(p) for p in parts])
+    shape, call = _finish_call("rmhmc_diag_finish", "diag", partials, lib, lambda p: p.ndim == 2,
+                               "diag_finish: partials of one shape [(4 + T), P] required")
+    T, P = shape[0] - 4, shape[1]
     merged = np.empty((4 + T, P)); rhat = np.empty(P); ess = np.empty(P)
     pairs = np.zeros(P, dtype=np.int64); used = np.zeros(P, dtype=np.int64)
-    rc = lib.lib.rmhmc_diag_finish(ptrs, len(parts), int(H), T, P, _ptr(merged), _ptr(rhat), _ptr(ess), _ptr(pairs, _lp), _ptr(used, _lp))
-    if rc != 0:
-        raise RmhmcError(rc, lib.lib.rmhmc_last_error(None).decode())
+    call(int(H), T, P, _ptr(merged), _ptr(rhat), _ptr(ess), _ptr(pairs, _lp), _ptr(used, _lp))
     return dict(rhat=rhat, ess_pooled=ess, pairs=pairs, chains_used=used, merged=merged)
 
 
@@ -1369,33 +1293,21 @@ def diag_identity(T, P):
     return np.zeros((4 + int(T), int(P)))
 
 
-def _adapt_lib(lib):
-    lib = lib if lib is not None else load_hip_library()
-    if not lib.has_adapt:
-        raise RmhmcError(-4, "%s does not export the warm-up of the fixed-metric HMC sampler (include/rmhmc_adapt.h)" % lib.path)
-    return lib
-
-
 def cov_finish(partials, lib=None):
     """rmhmc_cov_finish (include/rmhmc_adapt.h): the partials ([(2 + P), P] each: torch tensors on any device or NumPy arrays) merged in
     the order given and finished on the host.  Returns dict(mean [P], cov [P][P] (NaN for fewer than 2 rows), rows_used, merged)."""
-    lib = _adapt_lib(lib)
-    parts = [_f64(p if isinstance(p, np.ndarray) else p.detach().cpu().numpy()) for p in partials]
-    if not parts or parts[0].ndim != 2 or parts[0].shape[0] != parts[0].shape[1] + 2 or any(p.shape != parts[0].shape for p in parts):
-        raise ValueError("cov_finish: partials of one shape [(2 + P), P] required")
-    P = parts[0].shape[1]
-    ptrs = (_dp * len(parts))(*[_ptr(p) for p in parts])
+    shape, call = _finish_call("rmhmc_cov_finish", "adapt", partials, lib, lambda p: p.ndim == 2 and p.shape[0] == p.shape[1] + 2,
+                               "cov_finish: partials of one shape [(2 + P), P] required")
+    P = shape[1]
     merged = np.empty((2 + P, P)); mean = np.empty(P); cov = np.empty((P, P)); used = C.c_int64(0)
-    rc = lib.lib.rmhmc_cov_finish(ptrs, len(parts), P, _ptr(merged), _ptr(mean), _ptr(cov), C.cast(C.byref(used), _lp))
-    if rc != 0:
-        raise RmhmcError(rc, lib.lib.rmhmc_last_error(None).decode())
+    call(P, _ptr(merged), _ptr(mean), _ptr(cov), C.cast(C.byref(used), _lp))
     return dict(mean=mean, cov=cov, rows_used=used.value, merged=merged)
 
 
 def adapt_mass(cov, rows_used, lib=None):
     """rmhmc_adapt_mass: the inverse of the shrunk covariance m / (m + 5) cov + 1e-3 * 5 / (m + 5) I, or None where the library refuses
     it (fewer than 2 rows, not finite, not positive definite): the caller keeps its mass"""
-    lib = _adapt_lib(lib)
+    lib = _lib_with(lib, "adapt")
     cov = _f64(cov)
     if cov.ndim != 2 or cov.shape[0] != cov.shape[1]:
         raise ValueError("adapt_mass: a square covariance required")
@@ -1407,62 +1319,43 @@ def adapt_mass(cov, rows_used, lib=None):
 def adapt_init(eps, factor=10.0, lib=None):
     """rmhmc_adapt_init: the dual-averaging state (t, Hbar, log epsbar, mu = log(factor eps)) of a (re)start at step size eps; the
     warm-up starts with factor 10 and restarts with factor 1 after a mass update"""
-    lib = _adapt_lib(lib)
+    lib = _lib_with(lib, "adapt")
     state = np.empty(4)
-    rc = lib.lib.rmhmc_adapt_init(_ptr(state), float(eps), float(factor))
-    if rc != 0:
-        raise RmhmcError(rc, lib.lib.rmhmc_last_error(None).decode())
+    lib.ck(lib.lib.rmhmc_adapt_init(_ptr(state), float(eps), float(factor)))
     return state
 
 
 def adapt_step(state, accept, delta=0.8, gamma=0.05, t0=10.0, kappa=0.75, lib=None):
     """rmhmc_adapt_step: one dual-averaging update of `state` (a float64 array of 4, updated in place) with the acceptance statistic
     of a window.  Returns (eps_next, eps_bar)."""
-    lib = _adapt_lib(lib)
+    lib = _lib_with(lib, "adapt")
     if not (isinstance(state, np.ndarray) and state.dtype == np.float64 and state.shape == (4,) and state.flags.c_contiguous):
         raise ValueError("adapt_step: the state is a contiguous float64 array of 4")
     e = C.c_double(0.0); eb = C.c_double(0.0)
-    rc = lib.lib.rmhmc_adapt_step(_ptr(state), float(accept), float(delta), float(gamma), float(t0), float(kappa),
-                                  C.cast(C.byref(e), _dp), C.cast(C.byref(eb), _dp))
-    if rc != 0:
-        raise RmhmcError(rc, lib.lib.rmhmc_last_error(None).decode())
+    lib.ck(lib.lib.rmhmc_adapt_step(_ptr(state), float(accept), float(delta), float(gamma), float(t0), float(kappa),
+                                    C.cast(C.byref(e), _dp), C.cast(C.byref(eb), _dp)))
     return e.value, eb.value
 
 
 def ais_finish(partials, lib=None):
     """rmhmc_ais_finish (include/rmhmc_ais.h): the weight partials ([5] each: torch tensors on any device or NumPy arrays) merged in the
     order given and finished on the host.  Returns dict(log_mean_w, se (NaN for m < 2), weight_ess, m, n_nan, merged [5])."""
-    lib = lib if lib is not None else load_hip_library()
-    if not lib.has_ais:
-        raise RmhmcError(-4, "%s does not export annealed importance sampling (include/rmhmc_ais.h)" % lib.path)
-    parts = [_f64(p if isinstance(p, np.ndarray) else p.detach().cpu().numpy()) for p in partials]
-    if not parts or any(p.shape != (5,) for p in parts):
-        raise ValueError("ais_finish: partials of shape [5] required")
-    ptrs = (_dp * len(parts))(*[_ptr(p) for p in parts])
+    _, call = _finish_call("rmhmc_ais_finish", "ais", partials, lib, lambda p: p.shape == (5,), "ais_finish: partials of shape [5] required")
     merged = np.empty(5); lm = C.c_double(0.0); se = C.c_double(0.0); ess = C.c_double(0.0); m = C.c_int64(0); nn = C.c_int64(0)
-    rc = lib.lib.rmhmc_ais_finish(ptrs, len(parts), _ptr(merged), C.cast(C.byref(lm), _dp), C.cast(C.byref(se), _dp),
-                                  C.cast(C.byref(ess), _dp), C.cast(C.byref(m), _lp), C.cast(C.byref(nn), _lp))
-    if rc != 0:
-        raise RmhmcError(rc, lib.lib.rmhmc_last_error(None).decode())
+    call(_ptr(merged), C.cast(C.byref(lm), _dp), C.cast(C.byref(se), _dp), C.cast(C.byref(ess), _dp), C.cast(C.byref(m), _lp),
+         C.cast(C.byref(nn), _lp))
     return dict(log_mean_w=lm.value, se=se.value, weight_ess=ess.value, m=m.value, n_nan=nn.value, merged=merged)
 
 
 def smc_cess_finish(partials, lib=None):
     """rmhmc_smc_cess_finish (include/rmhmc_smc.h): the conditional-ESS partials ([2 + 4 J] each: torch tensors on any device or NumPy
     arrays) merged in the order given and finished on the host.  Returns dict(frac [J]: cess / n of every candidate, merged)."""
-    lib = lib if lib is not None else load_hip_library()
-    if not lib.has_smc:
-        raise RmhmcError(-4, "%s does not export adaptive sequential Monte Carlo (include/rmhmc_smc.h)" % lib.path)
-    parts = [_f64(p if isinstance(p, np.ndarray) else p.detach().cpu().numpy()) for p in partials]
-    if (not parts or parts[0].ndim != 1 or any(p.shape != parts[0].shape for p in parts) or (parts[0].size - 2) % 4
-            or not 1 <= (parts[0].size - 2) // 4 <= SMC_MAX_J):
-        raise ValueError("smc_cess_finish: partials of one shape [2 + 4 J], 1 <= J <= %d, required" % SMC_MAX_J)
-    J = (parts[0].size - 2) // 4
-    ptrs = (_dp * len(parts))(*[_ptr(p) for p in parts])
+    shape, call = _finish_call("rmhmc_smc_cess_finish", "smc", partials, lib,
+                               lambda p: p.ndim == 1 and (p.size - 2) % 4 == 0 and 1 <= (p.size - 2) // 4 <= SMC_MAX_J,
+                               "smc_cess_finish: partials of one shape [2 + 4 J], 1 <= J <= %d, required" % SMC_MAX_J)
+    J = (shape[0] - 2) // 4
     merged = np.empty(2 + 4 * J); frac = np.empty(J)
-    rc = lib.lib.rmhmc_smc_cess_finish(ptrs, len(parts), J, _ptr(merged), _ptr(frac))
-    if rc != 0:
-        raise RmhmcError(rc, lib.lib.rmhmc_last_error(None).decode())
+    call(J, _ptr(merged), _ptr(frac))
     return dict(frac=frac, merged=merged)
 
 
@@ -1478,19 +1371,11 @@ def smc_resample_u(seed, k):
 def pred_finish(partials, lib=None):
     """rmhmc_pred_finish (include/rmhmc_pred.h): the partials ([4, R] each: torch tensors on any device or NumPy arrays) merged in the
     order given and finished on the host.  Returns dict(prob, pvar, lpd [R], lpd_total, draws_used, merged [4, R])."""
-    lib = lib if lib is not None else load_hip_library()
-    if not lib.has_pred:
-        raise RmhmcError(-4, "%s does not export the posterior predictive probabilities (include/rmhmc_pred.h)" % lib.path)
-    parts = [_f64(p if isinstance(p, np.ndarray) else p.detach().cpu().numpy()) for p in partials]
-    if not parts or parts[0].ndim != 2 or parts[0].shape[0] != 4 or any(p.shape != parts[0].shape for p in parts):
-        raise ValueError("pred_finish: partials of one shape [4, R] required")
-    R = parts[0].shape[1]
-    ptrs = (_dp * len(parts))(*[_ptr(p) for p in parts])
+    shape, call = _finish_call("rmhmc_pred_finish", "pred", partials, lib, lambda p: p.ndim == 2 and p.shape[0] == 4,
+                               "pred_finish: partials of one shape [4, R] required")
+    R = shape[1]
     merged = np.empty((4, R)); prob = np.empty(R); pvar = np.empty(R); lpd = np.empty(R); total = C.c_double(0.0); used = C.c_int64(0)
-    rc = lib.lib.rmhmc_pred_finish(ptrs, len(parts), R, _ptr(merged), _ptr(prob), _ptr(pvar), _ptr(lpd), C.cast(C.byref(total), _dp),
-                                   C.cast(C.byref(used), _lp))
-    if rc != 0:
-        raise RmhmcError(rc, lib.lib.rmhmc_last_error(None).decode())
+    call(R, _ptr(merged), _ptr(prob), _ptr(pvar), _ptr(lpd), C.cast(C.byref(total), _dp), C.cast(C.byref(used), _lp))
     return dict(prob=prob, pvar=pvar, lpd=lpd, lpd_total=total.value, draws_used=used.value, merged=merged)
 
 

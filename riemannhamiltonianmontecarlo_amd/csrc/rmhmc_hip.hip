@@ -182,6 +182,25 @@ int dalloc(rmhmc_ctx* ctx, T** p, size_t count) {
   return RMHMC_OK;
 }
 
+// The device memory of one call (dalloc's lives as long as the context): every buffer it hands out is freed when it goes out of
+// scope, on every path.  Freeing is all it does: the function that declares it leaves the stream idle before it returns successfully.
+struct CallMem {
+  rmhmc_ctx* ctx;
+  std::vector<void*> held;
+  explicit CallMem(rmhmc_ctx* c) : ctx(c) {}
+  CallMem(const CallMem&) = delete;
+  CallMem& operator=(const CallMem&) = delete;
+  ~CallMem() { for (void* q : held) (void)hipFree(q); }
+  template <typename T>
+  int alloc(T** p, size_t bytes) {  // (uninitialised, unlike dalloc's)
+    void* q = nullptr;
+    HIPCK(hipMalloc(&q, bytes));
+    held.push_back(q);
+    *p = (T*)q;
+    return RMHMC_OK;
+  }
+};
+
 // hipFuncAttributeMaxDynamicSharedMemorySize of one kernel (MAX_LDS above: per function and device, so never lowered)
 template <typename K>
 int raise_lds(rmhmc_ctx* ctx, K kernel, int bytes) {
@@ -1599,19 +1618,20 @@ int write_out(rmhmc_ctx* ctx, const double* d_samples, size_t n, size_t S, size_
   const auto t0 = std::chrono::steady_clock::now();
   const hipMemcpyKind kind = out_kind(out);
   const size_t nd = n * D, sd = S * D;
-  double* d_st = nullptr;  // [3][n][D]: ess, mean, var
-  double* d_rm = nullptr;  // [S][D] run mean, then [D] its ess
-  const int rc = [&]() -> int {
+  CallMem mem(ctx);
+  const int rc = [&]() -> int {  // (a lambda: the time below is taken on every path, before mem frees)
     if (out.samples && out.samples != d_samples) HIPCK(hipMemcpyAsync(out.samples, d_samples, sizeof(double) * n * sd, kind, ctx->stream));
     if (out.mean || out.var || out.ess) {
-      HIPCK(hipMalloc((void**)&d_st, sizeof(double) * 3 * nd));
+      double* d_st = nullptr;  // [3][n][D]: ess, mean, var
+      RC(mem.alloc(&d_st, sizeof(double) * 3 * nd));
       RC(launch_ess(ctx, d_samples, (long long)n, (long long)S, (int)D, d_st, d_st + nd, d_st + 2 * nd));
       if (out.ess) HIPCK(hipMemcpyAsync(out.ess, d_st, sizeof(double) * nd, kind, ctx->stream));
       if (out.mean) HIPCK(hipMemcpyAsync(out.mean, d_st + nd, sizeof(double) * nd, kind, ctx->stream));
       if (out.var) HIPCK(hipMemcpyAsync(out.var, d_st + 2 * nd, sizeof(double) * nd, kind, ctx->stream));
     }
     if (out.run_mean || out.run_ess) {
-      HIPCK(hipMalloc((void**)&d_rm, sizeof(double) * (sd + D)));
+      double* d_rm = nullptr;  // [S][D] run mean, then [D] its ess
+      RC(mem.alloc(&d_rm, sizeof(double) * (sd + D)));
       hipLaunchKernelGGL(k_run_mean, dim3((unsigned)((sd + 255) / 256)), dim3(256), 0, ctx->stream, d_samples, n, sd, d_rm);
       if (out.run_ess) RC(launch_ess(ctx, d_rm, 1, (long long)S, (int)D, d_rm + sd, nullptr, nullptr));
       if (out.run_mean) HIPCK(hipMemcpyAsync(out.run_mean, d_rm, sizeof(double) * sd, kind, ctx->stream));
@@ -1620,8 +1640,6 @@ int write_out(rmhmc_ctx* ctx, const double* d_samples, size_t n, size_t S, size_
     return sync(ctx);
   }();
   ctx->write_out_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  if (d_st) (void)hipFree(d_st);
-  if (d_rm) (void)hipFree(d_rm);
   return rc;
 }
 
@@ -1639,14 +1657,11 @@ template <typename F>
 int sample_to(rmhmc_ctx* ctx, int64_t S, const rmhmc_out& out, F&& core) {
   const size_t n = ctx->n, D = ctx->D;
   const bool direct = out.where == RMHMC_OUT_DEVICE && out.samples;
+  CallMem mem(ctx);
   double* d_samples = direct ? out.samples : nullptr;
-  if (!direct) HIPCK(hipMalloc((void**)&d_samples, sizeof(double) * n * (size_t)S * D));
-  const int rc = [&]() -> int {
-    RC(core(d_samples));
-    return write_out(ctx, d_samples, n, (size_t)S, D, out);
-  }();
-  if (!direct) (void)hipFree(d_samples);
-  return rc;
+  if (!direct) RC(mem.alloc(&d_samples, sizeof(double) * n * (size_t)S * D));
+  RC(core(d_samples));
+  return write_out(ctx, d_samples, n, (size_t)S, D, out);
 }
 
 }  // namespace
@@ -1773,18 +1788,14 @@ int rmhmc_ess(rmhmc_ctx* ctx, const double* samples, int64_t n, int64_t S, int32
   if (!ctx || !samples || !ess_out || n < 1 || P < 1 || n * (int64_t)P > 0x7fffffffLL) return fail(ctx, RMHMC_ERR_INVALID, "ess: bad argument");
   RC(ess_range(ctx, S));  // before the buffers below are sized by S
   HIPCK(hipSetDevice(ctx->device));
+  CallMem mem(ctx);
   double *d_s = nullptr, *d_e = nullptr;
-  HIPCK(hipMalloc((void**)&d_s, sizeof(double) * (size_t)n * S * P));
-  int rc = [&]() -> int {
-    HIPCK(hipMalloc((void**)&d_e, sizeof(double) * (size_t)n * P));
-    HIPCK(hipMemcpyAsync(d_s, samples, sizeof(double) * (size_t)n * S * P, hipMemcpyHostToDevice, ctx->stream));
-    RC(launch_ess(ctx, d_s, n, S, P, d_e, nullptr, nullptr));
-    HIPCK(hipMemcpyAsync(ess_out, d_e, sizeof(double) * (size_t)n * P, hipMemcpyDeviceToHost, ctx->stream));
-    return sync(ctx);
-  }();
-  (void)hipFree(d_s);
-  if (d_e) (void)hipFree(d_e);
-  return rc;
+  RC(mem.alloc(&d_s, sizeof(double) * (size_t)n * S * P));
+  RC(mem.alloc(&d_e, sizeof(double) * (size_t)n * P));
+  HIPCK(hipMemcpyAsync(d_s, samples, sizeof(double) * (size_t)n * S * P, hipMemcpyHostToDevice, ctx->stream));
+  RC(launch_ess(ctx, d_s, n, S, P, d_e, nullptr, nullptr));
+  HIPCK(hipMemcpyAsync(ess_out, d_e, sizeof(double) * (size_t)n * P, hipMemcpyDeviceToHost, ctx->stream));
+  return sync(ctx);
 }
 
 int rmhmc_ess_dev(rmhmc_ctx* ctx, const double* samples_dev, int64_t n, int64_t S, int32_t P, double* ess_dev, double* mean_dev, double* var_dev) {
@@ -2737,10 +2748,9 @@ int launch_diag_acov(rmhmc_ctx* ctx, dim3 grid, size_t lds, const double* d_samp
   return RMHMC_OK;
 }
 
-// samples [n][S][P] -> the partial [(4 + T)][P], all in device memory; queued on the stream, its two scratch buffers returned for the
-// caller to free once the stream is idle
-int launch_diag(rmhmc_ctx* ctx, const double* d_samples, long long n, long long S, int P, long long T, double* d_partial, double** d_blk,
-                double** d_means) {
+// samples [n][S][P] -> the partial [(4 + T)][P], all in device memory; queued on the stream, its two scratch buffers taken from mem,
+// which the caller keeps until the stream is idle
+int launch_diag(rmhmc_ctx* ctx, const double* d_samples, long long n, long long S, int P, long long T, double* d_partial, CallMem& mem) {
   const long long H = S / 2;
   const int tw = diag_tile_width(H, P);
   const long long nblocks = (n + DIAG_CHAINS - 1) / DIAG_CHAINS;
@@ -2750,23 +2760,24 @@ int launch_diag(rmhmc_ctx* ctx, const double* d_samples, long long n, long long 
   if (T > nq * diag_lags_per_block(tw)) return fail(ctx, RMHMC_ERR_UNSUPPORTED, "diag: more lags than a workgroup holds");  // (never: diag.h)
   if (nblocks > 65535 || ntiles > 0x7fffffffLL) return fail(ctx, RMHMC_ERR_UNSUPPORTED, "diag: at most 65535 * 32 chains per call");
   const size_t rowlen = (size_t)(2 + T) * P;
-  HIPCK(hipMalloc((void**)d_blk, sizeof(double) * (size_t)nblocks * rowlen));
-  HIPCK(hipMalloc((void**)d_means, sizeof(double) * 2 * (size_t)n * P));
+  double *d_blk = nullptr, *d_means = nullptr;
+  RC(mem.alloc(&d_blk, sizeof(double) * (size_t)nblocks * rowlen));
+  RC(mem.alloc(&d_means, sizeof(double) * 2 * (size_t)n * P));
   const dim3 grid((unsigned)ntiles, (unsigned)nblocks);
   const size_t lds = (size_t)diag_lds_bytes(H, tw);
   const int rows = (int)diag_lds_rows(H);
 #define DIAG_CASE(TW)                                                                                                      \
   case TW:                                                                                                                 \
-    if (nq == 1) RC((launch_diag_acov<TW, 1>(ctx, grid, lds, d_samples, n, S, P, (int)H, (int)T, rows, *d_blk, *d_means)));   \
-    else RC((launch_diag_acov<TW, DIAG_NQ>(ctx, grid, lds, d_samples, n, S, P, (int)H, (int)T, rows, *d_blk, *d_means)));     \
+    if (nq == 1) RC((launch_diag_acov<TW, 1>(ctx, grid, lds, d_samples, n, S, P, (int)H, (int)T, rows, d_blk, d_means)));     \
+    else RC((launch_diag_acov<TW, DIAG_NQ>(ctx, grid, lds, d_samples, n, S, P, (int)H, (int)T, rows, d_blk, d_means)));       \
     break
   switch (tw) {
     DIAG_CASE(1); DIAG_CASE(2); DIAG_CASE(4); DIAG_CASE(8); DIAG_CASE(16); DIAG_CASE(32); DIAG_CASE(64);
     default: return fail(ctx, RMHMC_ERR_RUNTIME, "diag: no kernel for this tile width");
   }
 #undef DIAG_CASE
-  hipLaunchKernelGGL(k_diag_reduce, dim3((unsigned)((rowlen + 255) / 256)), dim3(256), 0, ctx->stream, *d_blk, nblocks, P, (int)H, (int)T, d_partial);
-  hipLaunchKernelGGL(k_diag_m2, dim3((unsigned)((P + 15) / 16)), dim3(1024), 0, ctx->stream, *d_means, 2 * n, P, d_partial);
+  hipLaunchKernelGGL(k_diag_reduce, dim3((unsigned)((rowlen + 255) / 256)), dim3(256), 0, ctx->stream, d_blk, nblocks, P, (int)H, (int)T, d_partial);
+  hipLaunchKernelGGL(k_diag_m2, dim3((unsigned)((P + 15) / 16)), dim3(1024), 0, ctx->stream, d_means, 2 * n, P, d_partial);
   HIPCK(hipGetLastError());
   return RMHMC_OK;
 }
@@ -2782,11 +2793,9 @@ int rmhmc_diag_partial_dev(rmhmc_ctx* ctx, const double* samples_dev, int64_t n,
   if (max_lag > H - 1) return fail(ctx, RMHMC_ERR_INVALID, "diag_partial_dev: max_lag must be 0 (every lag) or 1 .. S/2 - 1");
   const int64_t T = (max_lag ? max_lag : H - 1) + 1;
   HIPCK(hipSetDevice(ctx->device));
-  double *d_blk = nullptr, *d_means = nullptr;
-  int rc = launch_diag(ctx, samples_dev, n, S, P, T, partial_dev, &d_blk, &d_means);
+  CallMem mem(ctx);
+  const int rc = launch_diag(ctx, samples_dev, n, S, P, T, partial_dev, mem);
   const int rs = sync(ctx);
-  if (d_blk) (void)hipFree(d_blk);
-  if (d_means) (void)hipFree(d_means);
   return rc != RMHMC_OK ? rc : rs;
 }
 
@@ -2803,16 +2812,16 @@ int rmhmc_diag_finish(const double* const* partials, int32_t k, int64_t H, int64
 // adapt.hip.h) ------------------------------------------------------------------------------------------------------------------------
 namespace {
 
-// samples [N][P] -> the partial [(2 + P)][P], all in device memory; queued on the stream, its scratch buffer returned for the caller to
-// free once the stream is idle
-int launch_cov(rmhmc_ctx* ctx, const double* d_x, size_t N, int P, double* d_partial, void** d_scratch) {
+// samples [N][P] -> the partial [(2 + P)][P], all in device memory; queued on the stream, its scratch buffer taken from mem, which the
+// caller keeps until the stream is idle
+int launch_cov(rmhmc_ctx* ctx, const double* d_x, size_t N, int P, double* d_partial, CallMem& mem) {
   int64_t nb1, rpb1, nb2, rpb2;
   cov_plan_sums((int64_t)N, &nb1, &rpb1);
   cov_plan((int64_t)N, P, &nb2, &rpb2);
   const size_t p = (size_t)P, nt = (p + 15) / 16;
   const size_t doubles = (size_t)nb1 * 3 * p + 2 * p + (size_t)nb2 * p * p;
-  HIPCK(hipMalloc(d_scratch, sizeof(double) * doubles + N));
-  double* blk = (double*)*d_scratch;
+  double* blk = nullptr;
+  RC(mem.alloc(&blk, sizeof(double) * doubles + N));
   double* ctr = blk + (size_t)nb1 * 3 * p;
   double* scr = ctr + 2 * p;
   unsigned char* valid = (unsigned char*)(scr + (size_t)nb2 * p * p);
@@ -2827,10 +2836,9 @@ int launch_cov(rmhmc_ctx* ctx, const double* d_x, size_t N, int P, double* d_par
 }
 
 int cov_partial(rmhmc_ctx* ctx, const double* d_x, size_t N, int P, double* d_partial) {
-  void* d_scratch = nullptr;
-  const int rc = launch_cov(ctx, d_x, N, P, d_partial, &d_scratch);
+  CallMem mem(ctx);
+  const int rc = launch_cov(ctx, d_x, N, P, d_partial, mem);
   const int rs = sync(ctx);
-  if (d_scratch) (void)hipFree(d_scratch);
   return rc != RMHMC_OK ? rc : rs;
 }
 
@@ -2890,52 +2898,47 @@ int rmhmc_phmc_warmup(rmhmc_ctx* ctx, const double* theta0, int32_t L, double ep
   std::vector<long long> acc(n);
   if (theta0) theta.assign(theta0, theta0 + n * D);
   double eps = eps0, eps_bar = eps0;
+  CallMem mem(ctx);
   double *d_win = nullptr, *d_part = nullptr;  // the samples of one window [n][K][D]; its partial
-  HIPCK(hipMalloc((void**)&d_win, sizeof(double) * n * (size_t)Kmax * D));
-  const int rc = [&]() -> int {
-    HIPCK(hipMalloc((void**)&d_part, sizeof(double) * plen));
-    for (int32_t w = 0; w < W; ++w) {
-      const int64_t K = win_len[w];
-      ctx->chains_ready = false;
-      const Run run{PHMC, L, 0, eps, seed + 1 + (uint64_t)w, chain_offset, nullptr};
-      RC(hmc_sample_core(ctx, run, K, 0, theta.empty() ? nullptr : theta.data(), d_win, nullptr));
-      RC(download(ctx, acc.data(), ctx->batch.ch.accepted, n));
-      theta.resize(n * D);
-      HIPCK(hipMemcpy2DAsync(theta.data(), D * sizeof(double), d_win + (size_t)(K - 1) * D, (size_t)K * D * sizeof(double), D * sizeof(double), n,
-                             hipMemcpyDeviceToHost, ctx->stream));
-      RC(sync(ctx));
-      const double a = adapt_accept((const int64_t*)acc.data(), (int64_t)n, K);
-      if (eps_trace) eps_trace[w] = eps;
-      if (accept_trace) accept_trace[w] = a;
-      if (mass_updated) mass_updated[w] = 0;
-      double eps_next = eps;
-      if (adapt_step(state, a, delta, gamma, t0, kappa, &eps_next, &eps_bar) != RMHMC_OK)
-        return fail(ctx, RMHMC_ERR_INVALID, "phmc_warmup: the step size has left the finite positive numbers (dual averaging constants?)");
-      eps = eps_next;
-      if (win_kind[w] != 1) continue;
-      RC(cov_partial(ctx, d_win, n * (size_t)K, (int)D, d_part));
-      RC(download(ctx, wpart.data(), d_part, plen));
-      RC(sync(ctx));
-      const double* const two[2] = {running.data(), wpart.data()};
-      int64_t m = 0;
-      RC(cov_finish(two, 2, (int32_t)D, merged.data(), nullptr, cov.data(), &m));
-      running = merged;
-      if (m < min_rows) continue;
-      const char* why = "";
-      if (adapt_mass(cov.data(), m, (int32_t)D, mass.data(), &why) == RMHMC_OK && rmhmc_phmc_set_mass(ctx, mass.data()) == RMHMC_OK) {
-        mass_last = mass;
-        std::fill(running.begin(), running.end(), 0.0);
-        (void)adapt_init(state, eps, ADAPT_FACTOR_RESTART);
-        if (mass_updated) mass_updated[w] = 1;
-      } else {  // refused: the previous mass stays
-        if (mass_updated) mass_updated[w] = -1;
-      }
+  RC(mem.alloc(&d_win, sizeof(double) * n * (size_t)Kmax * D));
+  RC(mem.alloc(&d_part, sizeof(double) * plen));
+  for (int32_t w = 0; w < W; ++w) {
+    const int64_t K = win_len[w];
+    ctx->chains_ready = false;
+    const Run run{PHMC, L, 0, eps, seed + 1 + (uint64_t)w, chain_offset, nullptr};
+    RC(hmc_sample_core(ctx, run, K, 0, theta.empty() ? nullptr : theta.data(), d_win, nullptr));
+    RC(download(ctx, acc.data(), ctx->batch.ch.accepted, n));
+    theta.resize(n * D);
+    HIPCK(hipMemcpy2DAsync(theta.data(), D * sizeof(double), d_win + (size_t)(K - 1) * D, (size_t)K * D * sizeof(double), D * sizeof(double), n,
+                           hipMemcpyDeviceToHost, ctx->stream));
+    RC(sync(ctx));
+    const double a = adapt_accept((const int64_t*)acc.data(), (int64_t)n, K);
+    if (eps_trace) eps_trace[w] = eps;
+    if (accept_trace) accept_trace[w] = a;
+    if (mass_updated) mass_updated[w] = 0;
+    double eps_next = eps;
+    if (adapt_step(state, a, delta, gamma, t0, kappa, &eps_next, &eps_bar) != RMHMC_OK)
+      return fail(ctx, RMHMC_ERR_INVALID, "phmc_warmup: the step size has left the finite positive numbers (dual averaging constants?)");
+    eps = eps_next;
+    if (win_kind[w] != 1) continue;
+    RC(cov_partial(ctx, d_win, n * (size_t)K, (int)D, d_part));
+    RC(download(ctx, wpart.data(), d_part, plen));
+    RC(sync(ctx));
+    const double* const two[2] = {running.data(), wpart.data()};
+    int64_t m = 0;
+    RC(cov_finish(two, 2, (int32_t)D, merged.data(), nullptr, cov.data(), &m));
+    running = merged;
+    if (m < min_rows) continue;
+    const char* why = "";
+    if (adapt_mass(cov.data(), m, (int32_t)D, mass.data(), &why) == RMHMC_OK && rmhmc_phmc_set_mass(ctx, mass.data()) == RMHMC_OK) {
+      mass_last = mass;
+      std::fill(running.begin(), running.end(), 0.0);
+      (void)adapt_init(state, eps, ADAPT_FACTOR_RESTART);
+      if (mass_updated) mass_updated[w] = 1;
+    } else {  // refused: the previous mass stays
+      if (mass_updated) mass_updated[w] = -1;
     }
-    return RMHMC_OK;
-  }();
-  (void)hipFree(d_win);
-  if (d_part) (void)hipFree(d_part);
-  if (rc != RMHMC_OK) return rc;
+  }
   if (eps_out) *eps_out = eps_bar;
   if (mass_out) std::copy(mass_last.begin(), mass_last.end(), mass_out);
   if (theta_out) std::copy(theta.begin(), theta.end(), theta_out);
@@ -2952,8 +2955,9 @@ namespace {
 int ais_partial(rmhmc_ctx* ctx, const double* d_lw, size_t n, double* d_partial) {
   int64_t nb, pb;
   ais_plan((int64_t)n, &nb, &pb);
+  CallMem mem(ctx);
   double* d_scr = nullptr;  // blk [nb][3], sums [nb][4]
-  HIPCK(hipMalloc((void**)&d_scr, sizeof(double) * 7 * (size_t)nb));
+  RC(mem.alloc(&d_scr, sizeof(double) * 7 * (size_t)nb));
   launch(ctx, "ais", [&](hipStream_t st) {
     hipLaunchKernelGGL(k_ais_max, dim3((unsigned)nb), dim3(256), 0, st, d_lw, n, (size_t)pb, d_scr);
     hipLaunchKernelGGL(k_ais_sums, dim3((unsigned)nb), dim3(256), 0, st, d_lw, n, (size_t)pb, (const double*)d_scr, (int)nb, d_scr + 3 * (size_t)nb);
@@ -2961,7 +2965,6 @@ int ais_partial(rmhmc_ctx* ctx, const double* d_lw, size_t n, double* d_partial)
   });
   const hipError_t e = hipGetLastError();
   const int rs = sync(ctx);
-  (void)hipFree(d_scr);
   if (e != hipSuccess) return fail(ctx, RMHMC_ERR_RUNTIME, std::string(hipGetErrorString(e)) + " in ais_partial");
   return rs;
 }
@@ -2996,6 +2999,63 @@ int tphmc_sample_body(rmhmc_ctx* ctx, const char* who, int64_t n_iter, int64_t b
   });
 }
 
+// ---- what the two annealing runs share (rmhmc_ais_run; rmhmc_smc_run below): their opening, a stage's mass and its tail, the weight summary.
+// Their stage heads differ (a given ladder; a search, reweighting and resampling) and stay with them.
+struct Anneal {  // the arguments every stage of one run has in common, and its host staging
+  const double* H_lik;
+  int32_t L;
+  double eps;
+  uint64_t seed;
+  int64_t chain_offset;
+  double* accept_trace;  // [stages] or NULL
+  std::vector<long long> acc;
+  std::vector<double> mass, Lm, Mi;
+};
+
+// the opening: the per-chain buffers, log weights of zero, and the starting positions in trj.w: theta0, or draws from the prior
+int anneal_open(rmhmc_ctx* ctx, const Anneal& a, const double* theta0) {
+  ctx->chains_ready = false;
+  RC(ais_buffers(ctx));
+  HIPCK(hipMemsetAsync(ctx->d_ais_logw, 0, sizeof(double) * ctx->n, ctx->stream));
+  if (theta0) return upload_vec(ctx, ctx->batch.ch.trj.w, theta0);
+  launch_ais_prior(ctx, a.seed, a.chain_offset, ctx->batch.ch.trj.w, ctx->DP);
+  return RMHMC_OK;
+}
+
+// the mass bk H_lik + I / alpha of a stage that installs one; a refusal - a matrix that is not finite or not positive definite - keeps
+// the previous mass.  Synchronises.
+int anneal_mass(rmhmc_ctx* ctx, Anneal& a, double bk) {
+  const char* why = "";
+  if (ais_stage_mass_images(bk, a.H_lik, ctx->D, ctx->DP, ctx->dd.inv_alpha, a.mass, a.Lm, a.Mi, &why) != RMHMC_OK) return RMHMC_OK;
+  return install_mass_images(ctx, a.Lm, a.Mi);
+}
+
+// The tail of stage k at temperature bk, from the positions in trj.w: the initial record (which, with logw, adds dbeta loglik to it),
+// stage_len tempered iterations under the key seed + 1 + k, and the stage's entry of the acceptance trace.
+int anneal_stage(rmhmc_ctx* ctx, Anneal& a, int32_t k, double bk, int64_t stage_len, double* logw, double dbeta) {
+  RC(tphmc_init_dev(ctx, bk, logw, dbeta));
+  Run run{TPHMC, a.L, 0, a.eps, a.seed + 1 + (uint64_t)k, a.chain_offset, nullptr};
+  run.beta = bk;
+  RC(hmc_sample_run(ctx, run, stage_len, 0, nullptr, nullptr));  // (no sample buffer: the positions stay in the records)
+  if (a.accept_trace) {
+    a.acc.resize(ctx->n);
+    RC(download(ctx, a.acc.data(), ctx->batch.ch.accepted, ctx->n));
+    RC(sync(ctx));
+    a.accept_trace[k] = adapt_accept((const int64_t*)a.acc.data(), (int64_t)ctx->n, stage_len);
+  }
+  return RMHMC_OK;
+}
+
+// the weight summary: the partial of the log weights through d_part (device, [5]) into part (host, [5]), and what ais_finish makes of
+// it (every output may be NULL); synchronises
+int anneal_weights(rmhmc_ctx* ctx, double* d_part, double part[5], double* log_mean_w, double* se, double* ess) {
+  RC(ais_partial(ctx, ctx->d_ais_logw, ctx->n, d_part));
+  RC(download(ctx, part, (const double*)d_part, (size_t)5));
+  RC(sync(ctx));
+  const double* parts[1] = {part};
+  return ais_finish(parts, 1, nullptr, log_mean_w, se, ess, nullptr, nullptr);
+}
+
 }  // namespace
 
 extern "C" {
@@ -3024,16 +3084,13 @@ int rmhmc_ais_prior(rmhmc_ctx* ctx, uint64_t seed, int64_t chain_offset, double*
   if (!ctx || !theta_out) return fail(ctx, RMHMC_ERR_INVALID, "ais_prior: need a context and theta_out");
   HIPCK(hipSetDevice(ctx->device));
   const size_t nd = (size_t)ctx->n * ctx->D;
+  CallMem mem(ctx);
   double* d_th = nullptr;
-  HIPCK(hipMalloc((void**)&d_th, sizeof(double) * nd));
-  const int rc = [&]() -> int {
-    launch_ais_prior(ctx, seed, chain_offset, d_th, ctx->D);
-    HIPCK(hipGetLastError());
-    RC(download(ctx, theta_out, d_th, nd));
-    return sync(ctx);
-  }();
-  (void)hipFree(d_th);
-  return rc;
+  RC(mem.alloc(&d_th, sizeof(double) * nd));
+  launch_ais_prior(ctx, seed, chain_offset, d_th, ctx->D);
+  HIPCK(hipGetLastError());
+  RC(download(ctx, theta_out, d_th, nd));
+  return sync(ctx);
 }
 
 int rmhmc_ais_partial_dev(rmhmc_ctx* ctx, const double* logw_dev, int64_t n, double* partial_dev) {
@@ -3056,44 +3113,25 @@ int rmhmc_ais_run(rmhmc_ctx* ctx, const double* theta0, double beta0, int32_t T,
   if (const char* why = ais_check_run(theta0 != nullptr, beta0, T, beta, stage_len, stage_mass, H_lik != nullptr, L))
     return fail(ctx, RMHMC_ERR_INVALID, std::string("ais_run: ") + why);
   if (!ctx->have_mass) return fail(ctx, RMHMC_ERR_INVALID, "ais_run: rmhmc_phmc_set_mass has not been called");
-  ctx->chains_ready = false;
-  RC(ais_buffers(ctx));
   const size_t n = ctx->n;
   Group& g = ctx->batch;
-  HIPCK(hipMemsetAsync(ctx->d_ais_logw, 0, sizeof(double) * n, ctx->stream));
-  if (theta0) RC(upload_vec(ctx, g.ch.trj.w, theta0));
-  else launch_ais_prior(ctx, seed, chain_offset, g.ch.trj.w, ctx->DP);
-  std::vector<long long> acc(accept_trace ? n : 0);
-  std::vector<double> mass, Lm, Mi;
+  Anneal a{H_lik, L, eps, seed, chain_offset, accept_trace};
+  RC(anneal_open(ctx, a, theta0));
   double prev = beta0;
   for (int32_t k = 0; k < T; ++k) {
-    if (stage_mass && stage_mass[k]) {  // (a refusal - a beta H_lik + I / alpha that is not finite or not positive definite - keeps the previous mass)
-      const char* why = "";
-      if (ais_stage_mass_images(beta[k], H_lik, ctx->D, ctx->DP, ctx->dd.inv_alpha, mass, Lm, Mi, &why) == RMHMC_OK) RC(install_mass_images(ctx, Lm, Mi));
-    }
+    if (stage_mass && stage_mass[k]) RC(anneal_mass(ctx, a, beta[k]));
     // the last positions of the previous stage are the current points of its chains
     if (k > 0) HIPCK(hipMemcpyAsync(g.ch.trj.w, g.ch.cur.w, sizeof(double) * n * ctx->DP, hipMemcpyDeviceToDevice, ctx->stream));
-    RC(tphmc_init_dev(ctx, beta[k], ctx->d_ais_logw, beta[k] - prev));
-    Run run{TPHMC, L, 0, eps, seed + 1 + (uint64_t)k, chain_offset, nullptr};
-    run.beta = beta[k];
-    RC(hmc_sample_run(ctx, run, stage_len[k], 0, nullptr, nullptr));  // (no sample buffer: the positions stay in the records)
-    if (accept_trace) {
-      RC(download(ctx, acc.data(), g.ch.accepted, n));
-      RC(sync(ctx));
-      accept_trace[k] = adapt_accept((const int64_t*)acc.data(), (int64_t)n, stage_len[k]);
-    }
+    RC(anneal_stage(ctx, a, k, beta[k], stage_len[k], ctx->d_ais_logw, beta[k] - prev));
     prev = beta[k];
   }
   if (logw_out) RC(download(ctx, logw_out, ctx->d_ais_logw, n));
   if (theta_out) RC(download_vec(ctx, theta_out, g.ch.cur.w));
+  CallMem mem(ctx);
   if (partial_out) {
     double* d_part = nullptr;
-    HIPCK(hipMalloc((void**)&d_part, sizeof(double) * 5));
-    int rc = ais_partial(ctx, ctx->d_ais_logw, n, d_part);
-    if (rc == RMHMC_OK) rc = download(ctx, partial_out, d_part, (size_t)5);
-    if (rc == RMHMC_OK) rc = sync(ctx);
-    (void)hipFree(d_part);
-    RC(rc);
+    RC(mem.alloc(&d_part, sizeof(double) * 5));
+    RC(anneal_weights(ctx, d_part, partial_out, nullptr, nullptr, nullptr));
   }
   RC(sync(ctx));
   if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
@@ -3108,9 +3146,9 @@ namespace {
 // draws [N][D] (device), xnew [R][D] and tnew [R] | NULL (host, checked) -> the partial [4][R] (device); synchronises
 int pred_partial(rmhmc_ctx* ctx, const double* d_w, size_t N, int D, const double* xnew, const double* tnew, size_t R, double* d_partial) {
   const pred_plan_t pl = pred_plan((int64_t)N, (int64_t)R, D);
-  void* d_scratch = nullptr;
-  HIPCK(hipMalloc(&d_scratch, (size_t)pl.scratch_bytes));
-  double* rec = (double*)d_scratch;
+  CallMem mem(ctx);
+  double* rec = nullptr;
+  RC(mem.alloc(&rec, (size_t)pl.scratch_bytes));
   double* cnt = rec + pl.rec_doubles;
   double* d_x = cnt + pl.cnt_doubles;
   double* d_t = d_x + R * (size_t)D;
@@ -3135,7 +3173,6 @@ int pred_partial(rmhmc_ctx* ctx, const double* d_w, size_t N, int D, const doubl
     return RMHMC_OK;
   }();
   const int rs = sync(ctx);
-  (void)hipFree(d_scratch);
   return rc != RMHMC_OK ? rc : rs;
 }
 
@@ -3165,12 +3202,6 @@ int rmhmc_pred_finish(const double* const* partials, int32_t k, int64_t R, doubl
 // ---- the evidence by adaptive sequential Monte Carlo (include/rmhmc_smc.h, smc.h, smc.hip.h) ------------------------------------------------
 namespace {
 
-// a device buffer of one call
-struct SmcScratch {
-  void* p = nullptr;
-  ~SmcScratch() { if (p) (void)hipFree(p); }
-};
-
 // doubles of scratch that smc_cess needs for J candidates: blk [nb][NQ], sums [nb][NQ][2]
 size_t smc_cess_scratch(size_t n, int J) {
   int64_t nb, pb;
@@ -3188,11 +3219,8 @@ int smc_cess(rmhmc_ctx* ctx, const double* d_lw, const double* d_ll, size_t n, i
   const int NQ = 1 + 2 * JT;
   SmcDeltas dl;
   for (int j = 0; j < RMHMC_SMC_MAX_J; ++j) dl.d[j] = delta[j < J ? j : J - 1];
-  SmcScratch scr;
-  if (!d_scr) {
-    HIPCK(hipMalloc(&scr.p, sizeof(double) * smc_cess_scratch(n, J)));
-    d_scr = (double*)scr.p;
-  }
+  CallMem mem(ctx);
+  if (!d_scr) RC(mem.alloc(&d_scr, sizeof(double) * smc_cess_scratch(n, J)));
   double* d_blk = d_scr;
   double* d_sums = d_blk + (size_t)nb * NQ;
   launch(ctx, "smc", [&](hipStream_t st) {
@@ -3258,9 +3286,9 @@ int smc_quantise(rmhmc_ctx* ctx, const double* d_lw, size_t n, double a, uint64_
 int smc_ancestors(rmhmc_ctx* ctx, const uint64_t* d_q, size_t n, uint32_t U, int32_t* d_anc) {
   int64_t nb, pb;
   smc_scan_plan((int64_t)n, &nb, &pb);
-  SmcScratch scr;  // C [n], blk_sum [nb], blk_bad [nb], off [nb], head [2]
-  HIPCK(hipMalloc(&scr.p, sizeof(unsigned long long) * (n + 3 * (size_t)nb + 2)));
-  unsigned long long* d_C = (unsigned long long*)scr.p;
+  CallMem mem(ctx);
+  unsigned long long* d_C = nullptr;  // C [n], blk_sum [nb], blk_bad [nb], off [nb], head [2]
+  RC(mem.alloc(&d_C, sizeof(unsigned long long) * (n + 3 * (size_t)nb + 2)));
   unsigned long long *d_sum = d_C + n, *d_bad = d_sum + nb, *d_off = d_bad + nb, *d_head = d_off + nb;
   launch(ctx, "smc", [&](hipStream_t st) {
     hipLaunchKernelGGL(k_smc_scan_blocks, dim3((unsigned)nb), dim3(256), 0, st, (const unsigned long long*)d_q, n, d_C, d_sum, d_bad);
@@ -3302,9 +3330,10 @@ int rmhmc_smc_choose_delta_dev(rmhmc_ctx* ctx, const double* logw_dev, const dou
   if (!ctx || !logw_dev || !ll_dev) return fail(ctx, RMHMC_ERR_INVALID, "smc_choose_delta_dev: need a context, logw and ll");
   if (const char* why = smc_check_search(n, remaining, rho)) return fail(ctx, RMHMC_ERR_INVALID, std::string("smc_choose_delta_dev: ") + why);
   HIPCK(hipSetDevice(ctx->device));
-  SmcScratch part;
-  HIPCK(hipMalloc(&part.p, sizeof(double) * (2 + 4 * RMHMC_SMC_J + smc_cess_scratch((size_t)n, RMHMC_SMC_J))));
-  return smc_choose_delta(ctx, logw_dev, ll_dev, (size_t)n, remaining, rho, (double*)part.p, delta_out, frac_out, flags_out);
+  CallMem mem(ctx);
+  double* d_part = nullptr;
+  RC(mem.alloc(&d_part, sizeof(double) * (2 + 4 * RMHMC_SMC_J + smc_cess_scratch((size_t)n, RMHMC_SMC_J))));
+  return smc_choose_delta(ctx, logw_dev, ll_dev, (size_t)n, remaining, rho, d_part, delta_out, frac_out, flags_out);
 }
 
 int rmhmc_smc_reweight_dev(rmhmc_ctx* ctx, double* logw_dev, const double* ll_dev, int64_t n, double delta) {
@@ -3338,31 +3367,19 @@ int rmhmc_smc_run(rmhmc_ctx* ctx, const double* theta0, double beta0, double rho
     return fail(ctx, RMHMC_ERR_INVALID, std::string("smc_run: ") + why);
   if (!ctx->have_mass) return fail(ctx, RMHMC_ERR_INVALID, "smc_run: rmhmc_phmc_set_mass has not been called");
   if (tau > 0.0 && ctx->n > RMHMC_SMC_MAX_N) return fail(ctx, RMHMC_ERR_UNSUPPORTED, "smc_run: resampling needs n <= 2^20 chains");
-  ctx->chains_ready = false;
-  RC(ais_buffers(ctx));
   const size_t n = ctx->n;
   Group& g = ctx->batch;
-  SmcScratch scr;  // the weight partial [5], the conditional-ESS partial [2 + 4 J] and its scratch, q [n], anc [n]
+  Anneal a{H_lik, L, eps, seed, chain_offset, accept_trace};
+  RC(anneal_open(ctx, a, theta0));
+  CallMem mem(ctx);
+  double* d_part = nullptr;  // the weight partial [5], the conditional-ESS partial [2 + 4 J] and its scratch, q [n], anc [n]
   const size_t head = 5 + 2 + 4 * RMHMC_SMC_J + smc_cess_scratch(n, RMHMC_SMC_J);
-  HIPCK(hipMalloc(&scr.p, sizeof(double) * (head + n) + sizeof(int32_t) * n));
-  double* d_part = (double*)scr.p;
+  RC(mem.alloc(&d_part, sizeof(double) * (head + n) + sizeof(int32_t) * n));
   double* d_cess = d_part + 5;
   uint64_t* d_q = (uint64_t*)(d_part + head);
   int32_t* d_anc = (int32_t*)(d_q + n);
-  HIPCK(hipMemsetAsync(ctx->d_ais_logw, 0, sizeof(double) * n, ctx->stream));
-  if (theta0) RC(upload_vec(ctx, g.ch.trj.w, theta0));
-  else launch_ais_prior(ctx, seed, chain_offset, g.ch.trj.w, ctx->DP);
   RC(tphmc_init_dev(ctx, beta0, nullptr, 0.0));  // loglik at the start -> d_ais_ll; trj -> cur
-  std::vector<long long> acc(accept_trace ? n : 0);
-  std::vector<double> mass, Lm, Mi;
   double part[5], log_mean_w = NAN, ess = NAN, se = NAN;
-  const double* parts[1] = {part};
-  auto weight_partial = [&]() -> int {
-    RC(ais_partial(ctx, ctx->d_ais_logw, n, d_part));
-    RC(download(ctx, part, (const double*)d_part, (size_t)5));
-    RC(sync(ctx));
-    return ais_finish(parts, 1, nullptr, &log_mean_w, &se, &ess, nullptr, nullptr);
-  };
   double beta = beta0, logz_acc = 0.0;
   bool resampled_any = false;
   int32_t k = 0;
@@ -3372,7 +3389,7 @@ int rmhmc_smc_run(rmhmc_ctx* ctx, const double* theta0, double beta0, double rho
     RC(smc_choose_delta(ctx, ctx->d_ais_logw, ctx->d_ais_ll, n, 1.0 - beta, rho, d_cess, &delta, &frac, &flags));
     const double bk = (flags & RMHMC_SMC_LAST) ? 1.0 : beta + delta;
     RC(smc_reweight(ctx, ctx->d_ais_logw, ctx->d_ais_ll, n, delta, false));
-    RC(weight_partial());
+    RC(anneal_weights(ctx, d_part, part, &log_mean_w, &se, &ess));
     if (ess < tau * (double)n) {
       logz_acc += log_mean_w;
       RC(smc_quantise(ctx, ctx->d_ais_logw, n, part[2], d_q, false));
@@ -3387,26 +3404,15 @@ int rmhmc_smc_run(rmhmc_ctx* ctx, const double* theta0, double beta0, double rho
     } else {
       HIPCK(hipMemcpyAsync(g.ch.trj.w, g.ch.cur.w, sizeof(double) * n * ctx->DP, hipMemcpyDeviceToDevice, ctx->stream));
     }
-    if (smc_stage_mass(k, mass_every, flags)) {  // (a refusal keeps the previous mass, as in rmhmc_ais_run)
-      const char* why = "";
-      if (ais_stage_mass_images(bk, H_lik, ctx->D, ctx->DP, ctx->dd.inv_alpha, mass, Lm, Mi, &why) == RMHMC_OK) RC(install_mass_images(ctx, Lm, Mi));
-    }
-    RC(tphmc_init_dev(ctx, bk, nullptr, 0.0));
-    Run run{TPHMC, L, 0, eps, seed + 1 + (uint64_t)k, chain_offset, nullptr};
-    run.beta = bk;
-    RC(hmc_sample_run(ctx, run, stage_len, 0, nullptr, nullptr));
-    if (accept_trace) {
-      RC(download(ctx, acc.data(), g.ch.accepted, n));
-      RC(sync(ctx));
-      accept_trace[k] = adapt_accept((const int64_t*)acc.data(), (int64_t)n, stage_len);
-    }
+    if (smc_stage_mass(k, mass_every, flags)) RC(anneal_mass(ctx, a, bk));
+    RC(anneal_stage(ctx, a, k, bk, stage_len, nullptr, 0.0));
     if (beta_out) beta_out[k] = bk;
     if (cess_out) cess_out[k] = frac;
     if (ess_out) ess_out[k] = ess;
     if (flags_out) flags_out[k] = flags;
     beta = bk;
   }
-  RC(weight_partial());
+  RC(anneal_weights(ctx, d_part, part, &log_mean_w, &se, &ess));
   if (T_out) *T_out = k;
   if (logw_out) RC(download(ctx, logw_out, (const double*)ctx->d_ais_logw, n));
   if (theta_out) RC(download_vec(ctx, theta_out, g.ch.cur.w));

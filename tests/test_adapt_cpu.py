@@ -9,7 +9,6 @@ inverse of a matrix of condition < 1e4); dual averaging 4 ulp (five operations a
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 import sys
 
@@ -22,6 +21,7 @@ from riemannhamiltonianmontecarlo_amd import PHMC, _capi
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
 import adapt_ref as A  # noqa: E402
 import phmc_ref as R  # noqa: E402
+from probe_build import probe_exe  # noqa: E402
 
 SYMBOLS = {"rmhmc_cov_partial_dev", "rmhmc_cov_finish", "rmhmc_adapt_mass", "rmhmc_adapt_init", "rmhmc_adapt_step", "rmhmc_phmc_warmup"}
 _cache = {}
@@ -60,27 +60,6 @@ def test_library_exports_and_oracle_does_not(hip, oracle):
 
 
 # ---- csrc/adapt.h in a stand-alone program under AddressSanitizer and UBSan ----------------------------------------------------------------
-def _probe_exe(tmp_path_factory):
-    """adapt_probe.cpp built with the host compiler under ASan + UBSan.  The sanitizers' runtime is linked into the program itself, so
-    it starts whatever else the environment preloads; only beside a preloaded library that bears the ASan runtime's own name does
-    that runtime refuse to start, and there the default (shared) runtime is the one that starts."""
-    if "exe" not in _cache:
-        cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-        assert cxx, "no host C++ compiler"
-        tmp = tmp_path_factory.mktemp("adapt_probe")
-        clang = "clang" in subprocess.run([cxx, "--version"], capture_output=True, text=True).stdout
-        for name, runtime in (("static", ["-static-libsan"] if clang else ["-static-libasan", "-static-libubsan"]), ("shared", [])):
-            exe = str(tmp / ("adapt_probe_" + name))
-            subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                                   "-fno-sanitize-recover=all"] + runtime + ["-o", exe, os.path.join(ROOT, "tests", "helpers", "adapt_probe.cpp")])
-            start = subprocess.run([exe], input="", capture_output=True, text=True, timeout=60)   # no input: main returns 2
-            if "incompatible ASan runtimes" not in start.stderr:
-                break
-        assert start.returncode == 2 and not start.stderr, (name, start.returncode, start.stderr[-2000:])
-        _cache["exe"] = exe
-    return _cache["exe"]
-
-
 def _run(exe, text):
     r = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=60)
     assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr[-2000:])
@@ -117,7 +96,7 @@ def _close(got, want, rtol):
 
 
 def test_merge_and_finish_under_sanitizers(tmp_path_factory):
-    exe = _probe_exe(tmp_path_factory)
+    exe = probe_exe(tmp_path_factory, "adapt_probe")
     P = 5
     x = _rows(91, P, 0)
     whole = A.partial(x)
@@ -147,7 +126,7 @@ def _mass(exe, cov, m):
 
 
 def test_regularised_mass_under_sanitizers(tmp_path_factory):
-    exe = _probe_exe(tmp_path_factory)
+    exe = probe_exe(tmp_path_factory, "adapt_probe")
     P = 6
     cov = np.cov(_rows(40, P, 1).T)
     rc, mass = _mass(exe, cov, 40)
@@ -174,7 +153,7 @@ def _ulps(a, b):
 
 
 def test_dual_averaging_under_sanitizers(tmp_path_factory):
-    exe = _probe_exe(tmp_path_factory)
+    exe = probe_exe(tmp_path_factory, "adapt_probe")
     for eps0, da in ((0.5, A.DEFAULTS), (0.03, dict(delta=0.65, gamma=0.1, t0=5.0, kappa=0.6))):
         head = "da %s %s %s %s %s %d\n" % (float(eps0).hex(), float(da["delta"]).hex(), float(da["gamma"]).hex(), float(da["t0"]).hex(),
                                          float(da["kappa"]).hex(), len(ACCEPTS))
@@ -207,7 +186,7 @@ def test_dual_averaging_under_sanitizers(tmp_path_factory):
 
 @pytest.mark.parametrize("W", [3, 4, 10, 40])
 def test_schedule(tmp_path_factory, W):
-    exe = _probe_exe(tmp_path_factory)
+    exe = probe_exe(tmp_path_factory, "adapt_probe")
     want = {3: [0, 1, 0], 4: [0, 1, 1, 0], 10: [0, 0] + [1] * 7 + [0], 40: [0] * 6 + [1] * 30 + [0] * 4}[W]    # by hand
     for warmup, window in ((25 * W, 25), (7 * W + 6, 7)):
         length, kind = _capi.adapt_schedule(warmup, window)
@@ -224,7 +203,7 @@ def test_schedule(tmp_path_factory, W):
 def test_row_blocks(tmp_path_factory):
     """the row blocks of the covariance kernels, asked of csrc/adapt.h.  By hand: at least 256 rows per block; at most 1024 blocks and
     at most 4 MiB / (8 P^2) of them in the second pass (8 at P = 256, 128 at P = 64); rows per block of the second pass a multiple of 4"""
-    exe = _probe_exe(tmp_path_factory)
+    exe = probe_exe(tmp_path_factory, "adapt_probe")
     want = {(1, 1): (1, 4, 1, 1), (255, 5): (1, 256, 1, 255), (256, 64): (1, 256, 1, 256), (257, 64): (2, 132, 2, 129),
             (1000, 256): (4, 252, 4, 250), (204800, 64): (128, 1600, 800, 256), (204800, 256): (8, 25600, 800, 256),
             (163840000, 8): (1024, 160000, 1024, 160000)}

@@ -16,7 +16,6 @@ result of the size of a.  weight_ess = S1^2 / S2: 3 RTOL.  se^2 = (m S2 / S1^2 -
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 import sys
 
@@ -31,6 +30,7 @@ from riemannhamiltonianmontecarlo_amd.data import synthetic_logreg
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
 import ais_ref as A  # noqa: E402
 import phmc_ref as R  # noqa: E402
+from probe_build import probe_exe  # noqa: E402
 
 SYMBOLS = {"rmhmc_tphmc_transition", "rmhmc_tphmc_sample_to", "rmhmc_ais_prior", "rmhmc_ais_partial_dev", "rmhmc_ais_finish", "rmhmc_ais_run"}
 RTOL = 1500 * 2.0 ** -53
@@ -97,26 +97,6 @@ def test_sampler_tables_unchanged():
 
 
 # ---- csrc/ais.h in a stand-alone program under AddressSanitizer and UBSan ------------------------------------------------------------------
-def _probe_exe(tmp_path_factory):
-    """ais_probe.cpp built with the host compiler under ASan + UBSan, the runtime linked into the program itself (as
-    tests/test_adapt_cpu.py builds its probe)"""
-    if "exe" not in _cache:
-        cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-        assert cxx, "no host C++ compiler"
-        tmp = tmp_path_factory.mktemp("ais_probe")
-        clang = "clang" in subprocess.run([cxx, "--version"], capture_output=True, text=True).stdout
-        for name, runtime in (("static", ["-static-libsan"] if clang else ["-static-libasan", "-static-libubsan"]), ("shared", [])):
-            exe = str(tmp / ("ais_probe_" + name))
-            subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                                   "-fno-sanitize-recover=all"] + runtime + ["-o", exe, os.path.join(ROOT, "tests", "helpers", "ais_probe.cpp")])
-            start = subprocess.run([exe], input="", capture_output=True, text=True, timeout=60)   # no input: main returns 2
-            if "incompatible ASan runtimes" not in start.stderr:
-                break
-        assert start.returncode == 2 and not start.stderr, (name, start.returncode, start.stderr[-2000:])
-        _cache["exe"] = exe
-    return _cache["exe"]
-
-
 def _run(exe, text):
     r = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=60)
     assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr[-2000:])
@@ -155,7 +135,7 @@ def weight_cases():
 
 
 def test_merge_and_finish_under_sanitizers(tmp_path_factory):
-    exe = _probe_exe(tmp_path_factory)
+    exe = probe_exe(tmp_path_factory, "ais_probe")
     empty = np.array([0.0, 0.0, -np.inf, 0.0, 0.0])
     for name, lw in weight_cases().items():
         whole = A.partial(lw).astype(np.float64)
@@ -185,7 +165,7 @@ def test_merge_and_finish_under_sanitizers(tmp_path_factory):
 
 @pytest.mark.parametrize("T", [1, 2, 3, 1000])
 def test_schedules(tmp_path_factory, T):
-    exe = _probe_exe(tmp_path_factory)
+    exe = probe_exe(tmp_path_factory, "ais_probe")
     for cmd, arg, want, name in (("power", 4.0, A.ladder_power(T, 4.0), "power4"), ("power", 1.0, A.ladder_power(T, 1.0), "power1"),
                                  ("log", 1e-6, A.ladder_log(T, 1e-6), "log"), ("log", 0.01, A.ladder_log(T, 0.01), "log0.01")):
         lines = _run(exe, "%s %d %s\n" % (cmd, T, float(arg).hex()))
@@ -212,7 +192,7 @@ def test_schedules(tmp_path_factory, T):
 
 
 def test_refusals_and_stage_mass_under_sanitizers(tmp_path_factory):
-    exe = _probe_exe(tmp_path_factory)
+    exe = probe_exe(tmp_path_factory, "ais_probe")
     for line in ("power 0 4", "power 3 0", "power 3 -1", "power 3 nan", "power 3 inf", "log 0 0.5", "log 3 0", "log 3 1", "log 3 nan"):
         assert _run(exe, line + "\n") == ["ladder -1"], line
     for line in ("smass 0 1", "smass 3 0", "smass 3 -2"):

@@ -38,6 +38,30 @@ def test_oracle_exports_the_same_abi(oracle):
         assert hasattr(lib, s), s
 
 
+@pytest.mark.parametrize("key, phrase", [
+    ("amh", "the AMH sampler (include/rmhmc_amh.h)"),
+    ("iwls", "the IWLS sampler (include/rmhmc_iwls.h)"),
+    ("gibbs", "the Gibbs sampler (include/rmhmc_gibbs.h)"),
+    ("out", "the output descriptor (include/rmhmc_out.h)"),
+    ("diag", "the cross-chain diagnostics (include/rmhmc_diag.h)"),
+    ("phmc", "the fixed-metric HMC sampler (include/rmhmc_phmc.h)"),
+    ("adapt", "the warm-up of the fixed-metric HMC sampler (include/rmhmc_adapt.h)"),
+    ("ais", "annealed importance sampling (include/rmhmc_ais.h)"),
+    ("pred", "the posterior predictive probabilities (include/rmhmc_pred.h)"),
+    ("smc", "adaptive sequential Monte Carlo (include/rmhmc_smc.h)"),
+])
+def test_optional_feature_refusal(oracle, key, phrase):
+    optional = [v for k, v in vars(_capi).items() if k.endswith("_SIGNATURES")]   # (every table but the mandatory SIGNATURES)
+    assert len(optional) == len(_capi.FEATURES) and all(any(v is sigs for sigs, _ in _capi.FEATURES.values()) for v in optional)
+    assert _capi.FEATURES[key][1] == phrase
+    if getattr(oracle, "has_" + key):
+        assert oracle.need(key) is None
+    else:
+        with pytest.raises(_capi.RmhmcError) as e:
+            oracle.need(key)
+        assert e.value.code == -4 and str(e.value) == "rmhmc error -4: %s does not export %s" % (oracle.path, phrase)
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU failure mode")
 def test_no_gpu_fails_loudly(hip):
     with pytest.raises(_capi.RmhmcError) as e:

@@ -9,7 +9,6 @@ pairs and chains_used equal, where the reference's Geyer margin is above 1e-6.""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 import sys
 
@@ -21,6 +20,7 @@ from riemannhamiltonianmontecarlo_amd import _capi, experiment, multi_gpu
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
 import diag_ref as R  # noqa: E402
+from probe_build import probe_exe  # noqa: E402
 
 HEADER = os.path.join(ROOT, "include", "rmhmc_diag.h")
 MEAN_TOL = dict(rtol=1e-12, atol=1e-14)
@@ -166,7 +166,7 @@ def test_argument_checks_need_no_gpu(oracle):
             multi_gpu.sample_sharded(X, t, 4, sampler="HMC", diagnostics=True, **kw)
     with oracle.context(12, 3, 2) as ctx:                            # a library without the entry points says so
         with pytest.raises(_capi.RmhmcError, match="rmhmc_diag.h"):
-            ctx._need_diag()
+            ctx.rl.need("diag")
     with pytest.raises(_capi.RmhmcError, match="rmhmc_diag.h"):
         _capi.diag_finish([np.zeros((6, 2))], 3, lib=oracle)
 
@@ -206,27 +206,6 @@ def test_ar1_sanity(hip):
 
 
 # ---- csrc/diag.h in a stand-alone program under AddressSanitizer and UBSan ---------------------------------------------------------------
-def _probe_exe(tmp_path_factory):
-    """diag_probe.cpp built with the host compiler under ASan + UBSan.  The sanitizers' runtime is linked into the program itself, so it
-    starts whatever else the environment preloads; only beside a preloaded library that bears the ASan runtime's own name does that
-    runtime refuse to start, and there the default (shared) runtime is the one that starts."""
-    if "exe" not in _cache:
-        cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-        assert cxx, "no host C++ compiler"
-        tmp = tmp_path_factory.mktemp("diag_probe")
-        clang = "clang" in subprocess.run([cxx, "--version"], capture_output=True, text=True).stdout
-        for name, runtime in (("static", ["-static-libsan"] if clang else ["-static-libasan", "-static-libubsan"]), ("shared", [])):
-            exe = str(tmp / ("diag_probe_" + name))
-            subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                                   "-fno-sanitize-recover=all"] + runtime + ["-o", exe, os.path.join(ROOT, "tests", "helpers", "diag_probe.cpp")])
-            start = subprocess.run([exe], input="", capture_output=True, text=True, timeout=60)   # no input: main returns 2
-            if "incompatible ASan runtimes" not in start.stderr:
-                break
-        assert start.returncode == 2 and not start.stderr, (name, start.returncode, start.stderr[-2000:])
-        _cache["exe"] = exe
-    return _cache["exe"]
-
-
 def _probe(exe, parts, H, T, P, tiles=()):
     text = "%d %d %d %d\n" % (len(parts), H, T, P) + "\n".join(" ".join(float(v).hex() for v in np.ravel(p)) for p in parts) + "\n"
     text += "".join("%d %d\n" % hp for hp in tiles)
@@ -243,7 +222,7 @@ def _probe(exe, parts, H, T, P, tiles=()):
 
 
 def test_diag_header_under_sanitizers(hip, tmp_path_factory):
-    exe = _probe_exe(tmp_path_factory)
+    exe = probe_exe(tmp_path_factory, "diag_probe")
     c = case()
     empty = _capi.diag_identity(c["T"], 6)
     for parts in ([c["whole"]], c["pieces"], [empty] + c["pieces"] + [empty]):
@@ -266,5 +245,5 @@ def test_tile_shapes(tmp_path_factory):
     want = {(250, 64): (32, 306, 81408, 128), (250, 5): (8, 306, 22656, 512), (2, 1): (1, 51, 3480, 4096), (18, 33): (64, 68, 37888, 64),
             (30, 65): (64, 68, 37888, 64), (10000, 2): (1, 10659, 88344, 4096), (10000, 64): (1, 10659, 88344, 4096),
             (300, 64): (16, 357, 48768, 256), (251, 64): (32, 306, 81408, 128), (257, 64): (16, 323, 44416, 256), (5000, 3): (1, 5355, 45912, 4096)}
-    got = _probe(_probe_exe(tmp_path_factory), [np.zeros((6, 1))], 2, 2, 1, tiles=list(want))["tiles"]
+    got = _probe(probe_exe(tmp_path_factory, "diag_probe"), [np.zeros((6, 1))], 2, 2, 1, tiles=list(want))["tiles"]
     assert {g[:2]: g[2:] for g in got} == want

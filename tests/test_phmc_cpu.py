@@ -6,7 +6,6 @@ under AddressSanitizer and UBSan (tests/helpers/mass_probe.cpp, a child process:
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 import sys
 
@@ -19,10 +18,10 @@ from riemannhamiltonianmontecarlo_amd.data import synthetic_logreg
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
 import phmc_ref as R  # noqa: E402
+from probe_build import probe_exe  # noqa: E402
 
 HEADER = os.path.join(ROOT, "include", "rmhmc_phmc.h")
 SYMBOLS = {"rmhmc_phmc_set_mass", "rmhmc_phmc_mode", "rmhmc_phmc_transition", "rmhmc_phmc_sample_to"}
-_cache = {}
 
 
 def _header():
@@ -110,25 +109,6 @@ def test_restatement_mode_is_a_stationary_point():
 
 
 # ---- csrc/mass.h in a stand-alone program under AddressSanitizer and UBSan -----------------------------------------------------------
-def _probe_exe(tmp_path_factory):
-    """mass_probe.cpp built with the host compiler under ASan + UBSan, runtime linked into the program (see tests/test_diag_cpu.py)"""
-    if "exe" not in _cache:
-        cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-        assert cxx, "no host C++ compiler"
-        tmp = tmp_path_factory.mktemp("mass_probe")
-        clang = "clang" in subprocess.run([cxx, "--version"], capture_output=True, text=True).stdout
-        for name, runtime in (("static", ["-static-libsan"] if clang else ["-static-libasan", "-static-libubsan"]), ("shared", [])):
-            exe = str(tmp / ("mass_probe_" + name))
-            subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                                   "-fno-sanitize-recover=all"] + runtime + ["-o", exe, os.path.join(ROOT, "tests", "helpers", "mass_probe.cpp")])
-            start = subprocess.run([exe], input="", capture_output=True, text=True, timeout=60)   # no input: main returns 2
-            if "incompatible ASan runtimes" not in start.stderr:
-                break
-        assert start.returncode == 2 and not start.stderr, (name, start.returncode, start.stderr[-2000:])
-        _cache["exe"] = exe
-    return _cache["exe"]
-
-
 def _probe(exe, mass, D, DP):
     body = "identity" if mass is None else " ".join(float(v).hex() if np.isfinite(v) else repr(float(v)) for v in np.ravel(mass))
     r = subprocess.run([exe], input="%d %d\n%s\n" % (D, DP, body), capture_output=True, text=True, timeout=120)
@@ -143,7 +123,7 @@ def _probe(exe, mass, D, DP):
 
 @pytest.mark.parametrize("D,DP", [(1, 16), (7, 16), (64, 64), (256, 256), (65, 128)])
 def test_mass_header_under_sanitizers(tmp_path_factory, D, DP):
-    exe = _probe_exe(tmp_path_factory)
+    exe = probe_exe(tmp_path_factory, "mass_probe")
     rs = np.random.RandomState(D)
     A = rs.randn(D, 2 * D + 3)
     mass = A @ A.T / (2 * D + 3) + 0.5 * np.eye(D)      # condition number of a few tens: 1e-12 leaves room over D eps cond
@@ -160,7 +140,7 @@ def test_mass_header_under_sanitizers(tmp_path_factory, D, DP):
 
 
 def test_mass_header_refusals(tmp_path_factory):
-    exe = _probe_exe(tmp_path_factory)
+    exe = probe_exe(tmp_path_factory, "mass_probe")
     good = np.array([[4.0, 1.0, 0.5], [1.0, 3.0, 0.2], [0.5, 0.2, 2.0]])
     assert _probe(exe, good, 3, 16)[0] == 0
     nan = good.copy(); nan[2, 1] = np.nan

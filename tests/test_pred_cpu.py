@@ -14,7 +14,6 @@ allowances plus R u sum |lpd|."""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 import sys
 
@@ -28,10 +27,10 @@ from riemannhamiltonianmontecarlo_amd.data import synthetic_logreg
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
 import pred_ref as P  # noqa: E402
+from probe_build import probe_exe  # noqa: E402
 
 SYMBOLS = {"rmhmc_pred_partial_dev", "rmhmc_pred_finish"}
 U = 2.0 ** -53
-_cache = {}
 
 
 def _header():
@@ -107,26 +106,6 @@ def test_shim_argument_checks_need_no_library():
 
 
 # ---- csrc/pred.h in a stand-alone program under AddressSanitizer and UBSan -----------------------------------------------------------------
-def _probe_exe(tmp_path_factory):
-    """pred_probe.cpp built with the host compiler under ASan + UBSan, the runtime linked into the program itself (as
-    tests/test_ais_cpu.py builds its probe)"""
-    if "exe" not in _cache:
-        cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-        assert cxx, "no host C++ compiler"
-        tmp = tmp_path_factory.mktemp("pred_probe")
-        clang = "clang" in subprocess.run([cxx, "--version"], capture_output=True, text=True).stdout
-        for name, runtime in (("static", ["-static-libsan"] if clang else ["-static-libasan", "-static-libubsan"]), ("shared", [])):
-            exe = str(tmp / ("pred_probe_" + name))
-            subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                                   "-fno-sanitize-recover=all"] + runtime + ["-o", exe, os.path.join(ROOT, "tests", "helpers", "pred_probe.cpp")])
-            start = subprocess.run([exe], input="", capture_output=True, text=True, timeout=60)   # no input: main returns 2
-            if "incompatible ASan runtimes" not in start.stderr:
-                break
-        assert start.returncode == 2 and not start.stderr, (name, start.returncode, start.stderr[-2000:])
-        _cache["exe"] = exe
-    return _cache["exe"]
-
-
 def _run(exe, text):
     r = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=60)
     assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr[-2000:])
@@ -191,7 +170,7 @@ def _case(seed, n, S, D, R, scale=1.0):
 
 
 def test_merge_and_finish_under_sanitizers(tmp_path_factory):
-    exe = _probe_exe(tmp_path_factory)
+    exe = probe_exe(tmp_path_factory, "pred_probe")
     w, x, t = _case(0, 6, 11, 5, 9, scale=4.0)
     w[2, 3, 1] = np.nan                                    # an invalid draw: left out of m
     whole = P.partial(w, x, t).astype(np.float64)
@@ -252,7 +231,7 @@ def test_merge_and_finish_under_sanitizers(tmp_path_factory):
 
 
 def test_host_checks_under_sanitizers(tmp_path_factory):
-    exe = _probe_exe(tmp_path_factory)
+    exe = probe_exe(tmp_path_factory, "pred_probe")
     x = np.arange(6.0).reshape(2, 3) - 2.5
 
     def check(x, t):
@@ -286,7 +265,7 @@ def plans(exe, shapes):
 
 
 def test_plan_under_sanitizers(tmp_path_factory):
-    exe = _probe_exe(tmp_path_factory)
+    exe = probe_exe(tmp_path_factory, "pred_probe")
     c = _consts(exe)
     assert c["ROW_TILE"] % c["WAVE_ROWS"] == 0 and c["WAVE_ROWS"] == 16 and c["DRAWS"] % 16 == 0 and c["MAX_D"] == 256
     # by hand, from the rules in pred.h

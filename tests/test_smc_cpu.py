@@ -12,7 +12,6 @@ taken in longdouble by the test.  2 + 373 + 2 per merge, three merges: 1200 unit
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 import sys
 
@@ -27,12 +26,12 @@ from riemannhamiltonianmontecarlo_amd.data import synthetic_logreg
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
 import phmc_ref as R  # noqa: E402
 import smc_ref as S  # noqa: E402
+from probe_build import probe_exe  # noqa: E402
 from test_ais_cpu import PROBLEMS, _floats, _hex, quadrature  # noqa: E402
 
 SYMBOLS = {"rmhmc_smc_cess_dev", "rmhmc_smc_cess_finish", "rmhmc_smc_choose_delta_dev", "rmhmc_smc_reweight_dev", "rmhmc_smc_quantise_dev",
            "rmhmc_smc_ancestors_dev", "rmhmc_smc_run"}
 CESS_UNITS = 1200
-_cache = {}
 
 
 def _header():
@@ -79,26 +78,6 @@ def test_sampler_tables_unchanged():
 
 
 # ---- csrc/smc.h in a stand-alone program under AddressSanitizer and UBSan ------------------------------------------------------------------
-def _probe_exe(tmp_path_factory):
-    """smc_probe.cpp built with the host compiler under ASan + UBSan, the runtime linked into the program itself (as
-    tests/test_ais_cpu.py builds its probe)"""
-    if "exe" not in _cache:
-        cxx = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-        assert cxx, "no host C++ compiler"
-        tmp = tmp_path_factory.mktemp("smc_probe")
-        clang = "clang" in subprocess.run([cxx, "--version"], capture_output=True, text=True).stdout
-        for name, runtime in (("static", ["-static-libsan"] if clang else ["-static-libasan", "-static-libubsan"]), ("shared", [])):
-            exe = str(tmp / ("smc_probe_" + name))
-            subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                                   "-fno-sanitize-recover=all"] + runtime + ["-o", exe, os.path.join(ROOT, "tests", "helpers", "smc_probe.cpp")])
-            start = subprocess.run([exe], input="", capture_output=True, text=True, timeout=60)   # no input: main returns 2
-            if "incompatible ASan runtimes" not in start.stderr:
-                break
-        assert start.returncode == 2 and not start.stderr, (name, start.returncode, start.stderr[-2000:])
-        _cache["exe"] = exe
-    return _cache["exe"]
-
-
 def _run(exe, text):
     r = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=60)
     assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr[-2000:])
@@ -110,7 +89,7 @@ def _bits(a):
 
 
 def test_candidate_grids_bit_for_bit(tmp_path_factory):
-    exe = _probe_exe(tmp_path_factory)
+    exe = probe_exe(tmp_path_factory, "smc_probe")
     rs = np.random.RandomState(1)
     cases = [(0, rem, 0.0, rem) for rem in (1.0, 0.75, 1.0 / 3.0, 2.0 ** -53, 1.0 - 2.0 ** -53)]
     for _ in range(20):
@@ -142,7 +121,7 @@ def frac_sequences():
 
 
 def test_bracket_rule_on_recorded_sequences(tmp_path_factory):
-    exe = _probe_exe(tmp_path_factory)
+    exe = probe_exe(tmp_path_factory, "smc_probe")
     for name, (rem, rho, fracs) in frac_sequences().items():
         it = iter(fracs)
         want = S.search(lambda d: next(it), rem, rho)
@@ -173,7 +152,7 @@ def test_bracket_rule_on_recorded_sequences(tmp_path_factory):
 
 
 def test_resampling_offset(tmp_path_factory):
-    exe = _probe_exe(tmp_path_factory)
+    exe = probe_exe(tmp_path_factory, "smc_probe")
     cases = [(0, 0), (0, 1), (1, 0), (12345, 7), (2 ** 64 - 1, 0), (2 ** 64 - 1, 3), (2 ** 64 - 3, 9999), (2 ** 63, 2 ** 31 - 1)]
     lines = _run(exe, "".join("u %d %d\n" % c for c in cases))
     for (seed, k), line in zip(cases, lines):
@@ -205,7 +184,7 @@ def _cess(exe, parts, J):
 
 
 def test_cess_merge_and_finish_under_sanitizers(tmp_path_factory):
-    exe = _probe_exe(tmp_path_factory)
+    exe = probe_exe(tmp_path_factory, "smc_probe")
     deltas = {1: [0.37], 3: [1e-6, 1e-3, 0.5], 16: S.grid(0, 1.0, 0.0, 1.0), 32: np.linspace(1e-5, 1.0, 32)}
     tol = CESS_UNITS * 2.0 ** -53
     for name, (lw, ll) in particle_cases().items():
@@ -242,7 +221,7 @@ def test_cess_merge_and_finish_under_sanitizers(tmp_path_factory):
 
 
 def test_scan_plan_covers_every_entry_once(tmp_path_factory):
-    exe = _probe_exe(tmp_path_factory)
+    exe = probe_exe(tmp_path_factory, "smc_probe")
     sizes = [1, 2, 3, 4, 5, 255, 256, 257, 1023, 1024, 1025, 2047, 2048, 2049, 70001, 2 ** 20 - 1, 2 ** 20]
     lines = _run(exe, "".join("plan %d\ncover %d\n" % (n, n) for n in sizes))
     for i, n in enumerate(sizes):
@@ -259,7 +238,7 @@ def test_scan_plan_covers_every_entry_once(tmp_path_factory):
 
 
 def test_every_refusal_under_sanitizers(tmp_path_factory):
-    exe = _probe_exe(tmp_path_factory)
+    exe = probe_exe(tmp_path_factory, "smc_probe")
     ok = dict(have_theta0=0, beta0=0.0, rho=0.9, tau=0.5, T_max=10, stage_len=1, mass_every=1, have_H=1, L=6)
     cases = [ok, dict(ok, tau=0.0), dict(ok, tau=1.0), dict(ok, have_theta0=1, beta0=0.3), dict(ok, mass_every=0, have_H=0), dict(ok, mass_every=7),
              dict(ok, rho=0.0), dict(ok, rho=1.0), dict(ok, rho=np.nan), dict(ok, rho=-0.5), dict(ok, tau=-0.1), dict(ok, tau=1.1), dict(ok, tau=np.nan),
