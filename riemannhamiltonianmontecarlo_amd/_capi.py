@@ -242,6 +242,37 @@ SMC_MAX_N = 2 ** 20       # most particles of smc_ancestors (RMHMC_SMC_MAX_N)
 SMC_QBITS = 40            # q = 2^40 at the largest weight (RMHMC_SMC_QBITS)
 SMC_LAST, SMC_FLOOR, SMC_RESAMPLED = 1, 2, 4      # flags of a stage
 
+# include/rmhmc_quant.h: exact posterior quantiles by a radix select on mergeable integer histograms, HIP library only as well
+_up = C.POINTER(C.c_uint64)
+QUANT_SIGNATURES = {
+    "rmhmc_quant_hist_dev": (C.c_int, [C.c_void_p, _vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _up, C.c_int32, _vp]),
+    "rmhmc_quant_plan": (C.c_int, [_lp, _dp, C.c_int32, C.c_int32, _lp, _dp]),
+    "rmhmc_quant_step": (C.c_int, [_dpp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _up, _lp]),
+    "rmhmc_quant_finish": (C.c_int, [_up, _dp, _lp, C.c_int32, C.c_int32, _dp]),
+    "rmhmc_quant_dev": (C.c_int, [C.c_void_p, _vp, C.c_int64, C.c_int64, C.c_int32, _dp, C.c_int32, _dp, _lp]),
+}
+QUANT_MAX_K, QUANT_MAX_Q, QUANT_BINS, QUANT_ROUNDS = 16, 8, 256, 8    # RMHMC_QUANT_MAX_K, RMHMC_QUANT_MAX_Q; bins of a round, rounds
+QUANT_THREADS, QUANT_KEYS, QUANT_MAX_TILE = 256, 64, 64               # the kernel's workgroup, rows per thread, widest column tile (csrc/quant.h)
+QUANT_KEYS_OUT = ("quantiles", "quantile_draws")                      # what quantiles=probs adds to a sample_to result
+
+
+def quant_tile(P):
+    """(column tile, rows of a workgroup's row block) of the histogram kernel at P columns: quant_tile_width and quant_block_rows of
+    csrc/quant.h"""
+    tw = 1
+    while tw < int(P) and tw < QUANT_MAX_TILE:
+        tw *= 2
+    return tw, QUANT_THREADS // tw * QUANT_KEYS
+
+
+def quant_probs(probs):
+    """probs as the float64 vector the quantile calls take: one probability or a sequence of them, each in [0, 1].  ValueError otherwise."""
+    p = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+    if p.ndim != 1 or p.size < 1 or not ((p >= 0.0) & (p <= 1.0)).all():
+        raise ValueError("quantiles: probabilities in [0, 1] required, at least one")
+    return np.ascontiguousarray(p)
+
+
 # the optional headers: key (RmhmcLib.has_<key>, RmhmcLib.need(key)) -> (the header's signatures, what it is called in the "does not
 # export ..." message).  A library has a feature when it exports every symbol of the header.
 FEATURES = {
@@ -255,6 +286,7 @@ FEATURES = {
     "ais": (AIS_SIGNATURES, "annealed importance sampling (include/rmhmc_ais.h)"),
     "pred": (PRED_SIGNATURES, "the posterior predictive probabilities (include/rmhmc_pred.h)"),
     "smc": (SMC_SIGNATURES, "adaptive sequential Monte Carlo (include/rmhmc_smc.h)"),
+    "quant": (QUANT_SIGNATURES, "the posterior quantiles (include/rmhmc_quant.h)"),
 }
 
 
@@ -1001,7 +1033,8 @@ class Context:
 
     # ---- output descriptor: every sampler to host or device memory, raw or reduced (include/rmhmc_out.h) ----------
     def sample_to(self, sampler, n_iter, burn_in, *, where="host", device=None, samples=False, stats=False, run_mean=False,
-                  L=None, eps=None, K=None, compat=None, seed=0, chain_offset=0, theta0=None, diagnostics=False, max_lag=None):
+                  L=None, eps=None, K=None, compat=None, seed=0, chain_offset=0, theta0=None, diagnostics=False, max_lag=None,
+                  quantiles=None):
         """One run of `sampler` (a key of SAMPLERS_TO) written out as asked: samples [n][S][D]; stats: mean, var, ess [n][D]; run_mean:
         run_mean [S][D] and run_ess [D].  where="host": NumPy arrays; "device": torch tensors on `device`, the samples written by the
         sampler itself.  Returns a dict of the requested outputs, the sampler's counters (same memory space) and `seconds`.  The run
@@ -1012,8 +1045,18 @@ class Context:
         diagnostics=True adds the cross-chain diagnostics of the call's samples (include/rmhmc_diag.h; max_lag as in diag_partial): rhat,
         ess_pooled, pairs, chains_used as host NumPy arrays [D], and diag_partial, the device tensor a sharded job merges.  The sampler
         then writes its samples to a device tensor whatever `where` and `samples` say (they are returned only if asked, and outputs
-        asked on the host are copied there); samples and counters are those of the same call without the keyword, bit for bit."""
+        asked on the host are copied there); samples and counters are those of the same call without the keyword, bit for bit.
+
+        quantiles=probs (one probability or a sequence of them, each in [0, 1]) adds the exact posterior quantiles of the call's
+        samples over all chains (include/rmhmc_quant.h): quantiles [Q][D] and quantile_draws [D], host NumPy arrays.  The samples go to
+        a device tensor as for the diagnostics; a bad probability is refused before any sampling work."""
+        probs = None if quantiles is None else quant_probs(quantiles)   # refused before any sampling work
         self.rl.need("out")
+        if quantiles is not None:
+            self.rl.need("quant")
+            return self._sample_to_quant(sampler, n_iter, burn_in, where, device, samples, probs,
+                                         dict(stats=stats, run_mean=run_mean, L=L, eps=eps, K=K, compat=compat, seed=seed,
+                                              chain_offset=chain_offset, theta0=theta0, diagnostics=diagnostics, max_lag=max_lag))
         if diagnostics:
             return self._sample_to_diag(sampler, n_iter, burn_in, where, device, samples, max_lag,
                                         dict(stats=stats, run_mean=run_mean, L=L, eps=eps, K=K, compat=compat, seed=seed,
@@ -1135,6 +1178,58 @@ class Context:
             r = {k: v.cpu().numpy() if isinstance(v, torch.Tensor) else v for k, v in r.items()}
         r.update({k: dg[k] for k in DIAG_KEYS})
         r["diag_partial"] = dg["partial"]
+        return r
+
+    # ---- posterior quantiles: a radix select on mergeable integer histograms (include/rmhmc_quant.h) ----------
+    def quant_hist(self, samples, round, prefix=None, K=None):
+        """The histogram partial of one round of the select (include/rmhmc_quant.h) of a float64 torch tensor [n][S][P] already on the
+        context's GPU, counted there: a tensor [1][P][256] in round 0 (prefix None) and [K][P][256] afterwards, prefix a uint64 array
+        [K][P] (host; quant_step keeps it).  torch's current stream is synchronised first, as in ess_dev."""
+        import torch
+        self.rl.need("quant")
+        x = self._dev_tensor("quant_hist", samples, " [n][S][P]", 3)
+        n, S, P = x.shape
+        round = int(round)
+        pre = None
+        if prefix is not None:
+            pre = np.ascontiguousarray(prefix, dtype=np.uint64)
+            if pre.ndim != 2 or pre.shape[1] != P:
+                raise ValueError("quant_hist: prefix must be [K][P] with the P of the samples")
+            K = pre.shape[0]
+        K = 1 if K is None else int(K)
+        Kh = K if round > 0 and 1 <= K <= QUANT_MAX_K else 1   # (out of range: the library refuses the call)
+        hist = torch.empty((Kh, P, QUANT_BINS), dtype=torch.float64, device=x.device)
+        self._ck(self.lib.rmhmc_quant_hist_dev(self._h, x.data_ptr(), n, S, P, round, _ptr(pre, _up), K, hist.data_ptr()))
+        return hist
+
+    def quantiles(self, samples, probs):
+        """Exact quantiles (numpy's "linear" rule between the two exact order statistics) of every dimension of samples [n][S][P] on
+        the context's GPU over all n S rows, non-finite values left out of their own dimension: dict(quantiles [Q][P], draws_used [P]
+        the finite values per dimension), host NumPy arrays.  More than 8 probabilities run in groups of 8 (rmhmc_quant_dev)."""
+        self.rl.need("quant")
+        p = quant_probs(probs)
+        x = self._dev_tensor("quantiles", samples, " [n][S][P]", 3)
+        n, S, P = x.shape
+        out = np.empty((p.size, P)); used = np.zeros(P, dtype=np.int64)
+        for a in range(0, p.size, QUANT_MAX_Q):
+            pg = np.ascontiguousarray(p[a:a + QUANT_MAX_Q])
+            qg = np.empty((pg.size, P))
+            self._ck(self.lib.rmhmc_quant_dev(self._h, x.data_ptr(), n, S, P, _ptr(pg), pg.size, _ptr(qg), _ptr(used, _lp)))
+            out[a:a + pg.size] = qg
+        return dict(quantiles=out, draws_used=used)
+
+    def _sample_to_quant(self, sampler, n_iter, burn_in, where, device, samples, probs, kw):
+        import torch
+        host = where in ("host", OUT_HOST)
+        if host:
+            device = torch.device("cuda", self.device) if self.rl.on_gpu else torch.device("cpu")
+        r = self.sample_to(sampler, n_iter, burn_in, where="device" if host else where, device=device, samples=True, **kw)
+        q = self.quantiles(r["samples"], probs)
+        if not samples:
+            del r["samples"]
+        if host:
+            r = {k: v.cpu().numpy() if isinstance(v, torch.Tensor) and k != "diag_partial" else v for k, v in r.items()}
+        r["quantiles"], r["quantile_draws"] = q["quantiles"], q["draws_used"]
         return r
 
     # the three output modes of RMHMC (sample_dev, sample_stats, sample_stats_dev above) for the other five samplers: *_sample_dev
@@ -1291,6 +1386,74 @@ def diag_info(st, diagnostics):
 def diag_identity(T, P):
     """the partial of no series at all (an empty shard): the identity of the merge"""
     return np.zeros((4 + int(T), int(P)))
+
+
+def quant_identity(K, P):
+    """the histogram partial of no rows at all (an empty shard): the identity of the merge; K = 1 in round 0"""
+    return np.zeros((int(K), int(P), QUANT_BINS))
+
+
+def quant_plan(m, probs, lib=None):
+    """rmhmc_quant_plan (include/rmhmc_quant.h): m [P] finite values per dimension (int64), 1 .. 8 probabilities -> (rank int64 [2Q][P]:
+    rows 2j and 2j+1 the two order statistics of probs[j], -1 where m is 0; frac [Q][P]: the weight of the upper one)"""
+    lib = _lib_with(lib, "quant")
+    m = np.ascontiguousarray(m, dtype=np.int64).reshape(-1)
+    p = quant_probs(probs)
+    rank = np.zeros((2 * p.size, m.size), dtype=np.int64); frac = np.empty((p.size, m.size))
+    lib.ck(lib.lib.rmhmc_quant_plan(_ptr(m, _lp), _ptr(p), p.size, m.size, _ptr(rank, _lp), _ptr(frac)))
+    return rank, frac
+
+
+def quant_step(hists, round, prefix, rank, lib=None):
+    """rmhmc_quant_step: the histogram partials of one round ([Kh][P][256] each: torch tensors on any device or NumPy arrays, one per
+    shard) merged in the order given; prefix (uint64 [K][P]) and rank (int64 [K][P]), both contiguous NumPy arrays, are updated in
+    place.  RmhmcError -1, nothing written, for histograms that do not continue the previous round of these targets."""
+    if not (isinstance(prefix, np.ndarray) and prefix.dtype == np.uint64 and prefix.ndim == 2 and prefix.flags.c_contiguous
+            and isinstance(rank, np.ndarray) and rank.dtype == np.int64 and rank.shape == prefix.shape and rank.flags.c_contiguous):
+        raise ValueError("quant_step: prefix (uint64) and rank (int64) are contiguous arrays of one shape [K][P]")
+    K, P = prefix.shape
+    Kh = K if int(round) > 0 else 1
+    _, call = _finish_call("rmhmc_quant_step", "quant", hists, lib, lambda h: h.shape == (Kh, P, QUANT_BINS),
+                           "quant_step: histograms of one shape [K][P][256] ([1][P][256] in round 0) required")
+    call(P, K, int(round), _ptr(prefix, _up), _ptr(rank, _lp))
+
+
+def quant_finish(prefix, frac, m, lib=None):
+    """rmhmc_quant_finish: prefix (uint64 [2Q][P]) after round 7, frac [Q][P] and m [P] of quant_plan -> the quantiles [Q][P]"""
+    lib = _lib_with(lib, "quant")
+    frac = _f64(frac)
+    m = np.ascontiguousarray(m, dtype=np.int64).reshape(-1)
+    prefix = np.ascontiguousarray(prefix, dtype=np.uint64)
+    if frac.ndim != 2 or prefix.shape != (2 * frac.shape[0], frac.shape[1]) or m.size != frac.shape[1]:
+        raise ValueError("quant_finish: prefix [2Q][P], frac [Q][P] and m [P] required")
+    Q, P = frac.shape
+    out = np.empty((Q, P))
+    lib.ck(lib.lib.rmhmc_quant_finish(_ptr(prefix, _up), _ptr(frac), _ptr(m, _lp), Q, P, _ptr(out)))
+    return out
+
+
+def quant_totals(hists):
+    """the finite values per dimension, int64 [P]: the totals of the round-0 histograms of all shards"""
+    return sum(np.asarray(h if isinstance(h, np.ndarray) else h.detach().cpu().numpy(), dtype=np.float64)[0].sum(axis=1) for h in hists).astype(np.int64)
+
+
+def quant_select(hist, probs, P, lib=None):
+    """The eight rounds of the select around any source of histograms: hist(round, prefix, K) returns the list of the shards' partials of
+    that round (prefix None in round 0).  Every shard that runs this with the same (merged or gathered) histograms steps identically.
+    Returns dict(quantiles [Q][P], draws_used [P]); more than 8 probabilities run in groups of 8 on the one round-0 histogram."""
+    p = quant_probs(probs)
+    h0 = hist(0, None, 1)
+    m = quant_totals(h0)
+    out = np.empty((p.size, int(P)))
+    for a in range(0, p.size, QUANT_MAX_Q):
+        pg = p[a:a + QUANT_MAX_Q]
+        rank, frac = quant_plan(m, pg, lib=lib)
+        prefix = np.zeros(rank.shape, dtype=np.uint64)
+        quant_step(h0, 0, prefix, rank, lib=lib)
+        for r in range(1, QUANT_ROUNDS):
+            quant_step(hist(r, prefix, prefix.shape[0]), r, prefix, rank, lib=lib)
+        out[a:a + pg.size] = quant_finish(prefix, frac, m, lib=lib)
+    return dict(quantiles=out, draws_used=m)
 
 
 def cov_finish(partials, lib=None):

@@ -16,6 +16,7 @@
 #include "../../include/rmhmc_ais.h"
 #include "../../include/rmhmc_pred.h"
 #include "../../include/rmhmc_smc.h"
+#include "../../include/rmhmc_quant.h"
 #include "plan.h"
 #include "mass.h"
 #include "kernels.hip.h"
@@ -33,6 +34,7 @@
 #include "ais.hip.h"
 #include "pred.hip.h"
 #include "smc.hip.h"
+#include "quant.hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -2804,6 +2806,144 @@ int rmhmc_diag_finish(const double* const* partials, int32_t k, int64_t H, int64
   const int rc = diag_finish(partials, k, H, T, P, merged, rhat, ess, pairs, chains_used);
   return rc == RMHMC_OK ? rc : fail(nullptr, rc, rc == RMHMC_ERR_NOMEM ? "diag_finish: out of memory"
                                                                        : "diag_finish: need k >= 1, H >= 2, 2 <= T <= H, P >= 1 and no NULL partial");
+}
+
+}  // extern "C"
+
+// ---- posterior quantiles: the radix select on integer histograms (include/rmhmc_quant.h, quant.h, quant.hip.h) -----------------------
+namespace {
+
+template <int TW>
+int launch_quant_tw(rmhmc_ctx* ctx, dim3 grid, const double* d_samples, long long N, int P, int round, int Kh, const unsigned long long* d_prefix,
+                    const signed char* d_rep, unsigned long long* d_cnt) {
+  RC(raise_lds(ctx, k_quant_hist<TW>, MAX_LDS));  // per device: set where it is used
+  hipLaunchKernelGGL(k_quant_hist<TW>, grid, dim3(QUANT_THREADS), QUANT_LDS_BYTES, ctx->stream, d_samples, N, P, round, Kh, d_prefix, d_rep, d_cnt);
+  return RMHMC_OK;
+}
+
+// samples [N][P] -> the histogram partial [Kh][P][256] of `round`, all in device memory; queued on the stream, its buffers taken from mem,
+// which the caller keeps until the stream is idle.  prefix: host [K][P], unused in round 0
+int launch_quant_hist(rmhmc_ctx* ctx, const double* d_samples, long long N, int P, int round, const uint64_t* prefix, int K, double* d_hist,
+                      CallMem& mem) {
+  const int tw = quant_tile_width(P), Kh = round ? K : 1;
+  const long long nblocks = (N + quant_block_rows(tw) - 1) / quant_block_rows(tw), ntiles = ((long long)P + tw - 1) / tw;
+  if (nblocks > 0x7fffffffLL || ntiles > 65535) return fail(ctx, RMHMC_ERR_UNSUPPORTED, "quant: too many rows or columns for one launch");
+  const size_t targets = (size_t)Kh * P, total = targets * QUANT_BINS;
+  unsigned long long *d_cnt = nullptr, *d_prefix = nullptr;
+  signed char* d_rep = nullptr;
+  RC(mem.alloc(&d_cnt, sizeof(unsigned long long) * total));
+  HIPCK(hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * total, ctx->stream));
+  if (round) {
+    // a target whose top 8 round bits repeat those of an earlier target of its column is not counted again (k_quant_out copies)
+    std::vector<signed char> rep(targets);
+    for (int k = 0; k < K; ++k)
+      for (int d = 0; d < P; ++d) {
+        int first = 0;
+        while (!quant_match(prefix[(size_t)first * P + d], prefix[(size_t)k * P + d], round)) ++first;
+        rep[(size_t)k * P + d] = (signed char)first;
+      }
+    RC(mem.alloc(&d_prefix, sizeof(uint64_t) * targets));
+    RC(mem.alloc(&d_rep, targets));
+    HIPCK(hipMemcpyAsync(d_prefix, prefix, sizeof(uint64_t) * targets, hipMemcpyHostToDevice, ctx->stream));
+    HIPCK(hipMemcpyAsync(d_rep, rep.data(), targets, hipMemcpyHostToDevice, ctx->stream));
+    HIPCK(hipStreamSynchronize(ctx->stream));  // rep goes out of scope, and the caller's prefix is its own again
+  }
+  const dim3 grid((unsigned)nblocks, (unsigned)ntiles);
+  int rc = RMHMC_OK;
+  launch(ctx, "quant_hist", [&](hipStream_t) {
+#define QUANT_CASE(TW) case TW: rc = launch_quant_tw<TW>(ctx, grid, d_samples, N, P, round, Kh, d_prefix, d_rep, d_cnt); break
+    switch (tw) {
+      QUANT_CASE(1); QUANT_CASE(2); QUANT_CASE(4); QUANT_CASE(8); QUANT_CASE(16); QUANT_CASE(32); QUANT_CASE(64);
+      default: rc = fail(ctx, RMHMC_ERR_RUNTIME, "quant: no kernel for this tile width");
+    }
+#undef QUANT_CASE
+  });
+  RC(rc);
+  hipLaunchKernelGGL(k_quant_out, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, d_cnt, d_rep, P, total, d_hist);
+  HIPCK(hipGetLastError());
+  return RMHMC_OK;
+}
+
+const char* quant_hist_refusal(const rmhmc_ctx* ctx, const void* samples, int64_t n, int64_t S, int32_t P) {
+  if (!ctx || !samples || n < 1 || S < 1 || P < 1 || n > INT64_MAX / S) return "need a context, samples, n >= 1, S >= 1, P >= 1";
+  return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rmhmc_quant_hist_dev(rmhmc_ctx* ctx, const double* samples_dev, int64_t n, int64_t S, int32_t P, int32_t round, const uint64_t* prefix,
+                         int32_t K, double* hist_dev) {
+  if (const char* why = quant_hist_refusal(ctx, samples_dev, n, S, P)) return fail(ctx, RMHMC_ERR_INVALID, std::string("quant_hist_dev: ") + why);
+  if (!hist_dev || round < 0 || round > 7 || K < 1 || K > QUANT_MAX_K || (round && !prefix))
+    return fail(ctx, RMHMC_ERR_INVALID, "quant_hist_dev: need a histogram, 0 <= round <= 7, 1 <= K <= 16 and a prefix after round 0");
+  if ((int64_t)K * P > INT32_MAX / QUANT_BINS) return fail(ctx, RMHMC_ERR_UNSUPPORTED, "quant_hist_dev: K * P * 256 must fit 31 bits");
+  HIPCK(hipSetDevice(ctx->device));
+  CallMem mem(ctx);
+  const int rc = launch_quant_hist(ctx, samples_dev, n * S, P, round, prefix, K, hist_dev, mem);
+  const int rs = sync(ctx);
+  return rc != RMHMC_OK ? rc : rs;
+}
+
+int rmhmc_quant_plan(const int64_t* m, const double* probs, int32_t Q, int32_t P, int64_t* rank, double* frac) {
+  const int rc = quant_plan(m, probs, Q, P, rank, frac);
+  return rc == RMHMC_OK ? rc : fail(nullptr, rc, "quant_plan: need m >= 0, 1 <= Q <= 8 probabilities in [0, 1], P >= 1 and no NULL pointer");
+}
+
+int rmhmc_quant_step(const double* const* hists, int32_t k_parts, int32_t P, int32_t K, int32_t round, uint64_t* prefix, int64_t* rank) {
+  const int rc = quant_step(hists, k_parts, P, K, round, prefix, rank);
+  return rc == RMHMC_OK ? rc : fail(nullptr, rc, rc == RMHMC_ERR_NOMEM ? "quant_step: out of memory"
+                                                                       : "quant_step: bad argument, or a histogram that is not the one of this round of these targets");
+}
+
+int rmhmc_quant_finish(const uint64_t* prefix, const double* frac, const int64_t* m, int32_t Q, int32_t P, double* quant) {
+  const int rc = quant_finish(prefix, frac, m, Q, P, quant);
+  return rc == RMHMC_OK ? rc : fail(nullptr, rc, "quant_finish: need 1 <= Q <= 8, P >= 1 and no NULL pointer");
+}
+
+int rmhmc_quant_dev(rmhmc_ctx* ctx, const double* samples_dev, int64_t n, int64_t S, int32_t P, const double* probs, int32_t Q, double* quant,
+                    int64_t* draws_used) {
+  if (const char* why = quant_hist_refusal(ctx, samples_dev, n, S, P)) return fail(ctx, RMHMC_ERR_INVALID, std::string("quant_dev: ") + why);
+  if (!probs || !quant || Q < 1 || Q > QUANT_MAX_Q) return fail(ctx, RMHMC_ERR_INVALID, "quant_dev: need 1 <= Q <= 8 probabilities and an output");
+  for (int32_t j = 0; j < Q; ++j)
+    if (!(probs[j] >= 0.0 && probs[j] <= 1.0)) return fail(ctx, RMHMC_ERR_INVALID, "quant_dev: a probability is outside [0, 1]");
+  const int K = 2 * Q;
+  if ((int64_t)K * P > INT32_MAX / QUANT_BINS) return fail(ctx, RMHMC_ERR_UNSUPPORTED, "quant_dev: 2 Q * P * 256 must fit 31 bits");
+  HIPCK(hipSetDevice(ctx->device));
+  const size_t targets = (size_t)K * P;
+  std::vector<double> hist(targets * QUANT_BINS), frac((size_t)Q * P);
+  std::vector<uint64_t> prefix(targets, 0);
+  std::vector<int64_t> rank(targets), m((size_t)P);
+  CallMem mem(ctx);
+  double* d_hist = nullptr;
+  RC(mem.alloc(&d_hist, sizeof(double) * hist.size()));
+  for (int round = 0; round < 8; ++round) {
+    const size_t len = (round ? targets : (size_t)P) * QUANT_BINS;
+    int rc;
+    {
+      CallMem round_mem(ctx);
+      rc = launch_quant_hist(ctx, samples_dev, n * S, P, round, prefix.data(), K, d_hist, round_mem);
+      if (rc == RMHMC_OK) {
+        hipError_t e = hipMemcpyAsync(hist.data(), d_hist, sizeof(double) * len, hipMemcpyDeviceToHost, ctx->stream);
+        if (e != hipSuccess) rc = fail(ctx, RMHMC_ERR_RUNTIME, std::string(hipGetErrorString(e)) + " in quant_dev");
+      }
+      const int rs = sync(ctx);
+      if (rc == RMHMC_OK) rc = rs;
+    }
+    RC(rc);
+    if (round == 0) {
+      quant_totals(hist.data(), P, m.data());
+      RC(rmhmc_quant_plan(m.data(), probs, Q, P, rank.data(), frac.data()));
+    }
+    const double* one = hist.data();
+    const int rs = quant_step(&one, 1, P, K, round, prefix.data(), rank.data());
+    if (rs != RMHMC_OK) return fail(ctx, rs, "quant_dev: a round's histogram does not continue the previous round");
+  }
+  RC(rmhmc_quant_finish(prefix.data(), frac.data(), m.data(), Q, P, quant));
+  if (draws_used)
+    for (int32_t d = 0; d < P; ++d) draws_used[d] = m[(size_t)d];
+  return RMHMC_OK;
 }
 
 }  // extern "C"

@@ -93,7 +93,7 @@ def nanmin_rows(ess):
 
 def sample_sharded(XX, t, n_chains, NumOfIterations=6000, BurnIn=1000, NumOfLeapFrogSteps=6, StepSize=0.5,
                    NumOfNewtonSteps=4, *, seed=0, compat=True, theta0=None, alpha=100.0, gather="samples", lib=None, options=None,
-                   sampler="RMHMC", sampler_args=None, diagnostics=False, max_lag=None):
+                   sampler="RMHMC", sampler_args=None, diagnostics=False, max_lag=None, quantiles=None):
     """Run ``n_chains`` chains sharded over the ranks of the initialised process group.
 
     gather="samples": rank 0 returns (samples [n_chains,S,D], seconds, info); other ranks return None.
@@ -114,6 +114,10 @@ def sample_sharded(XX, t, n_chains, NumOfIterations=6000, BurnIn=1000, NumOfLeap
     gathered to rank 0 and merged there in rank order.  "RMHMC" then runs through rmhmc_sample_to as the other samplers do, which by the
     contract of include/rmhmc_out.h gives the same samples and counters.  The result does not depend on the number of ranks beyond
     rounding (the merge is exact arithmetic only for the counts).
+    ``quantiles=probs`` (every sampler, both gather modes; HIP library only): ``info`` gains quantiles (Q, D) and quantile_draws (D,), the
+    exact posterior quantiles over ALL n_chains chains (include/rmhmc_quant.h).  Every rank counts the histogram of a round on its GPU - an
+    empty shard contributes the identity without a launch -, one all_reduce(SUM) per round merges them, and every rank takes the same step
+    on the sum; no sample leaves its GPU.  Counts add exactly, so the result is the same to the bit for any number of ranks.
     """
     if sampler not in _SHARDED:   # (before any collective: every rank raises on its own)
         raise ValueError("unknown sampler %r: one of %s" % (sampler, sorted(_SHARDED)))
@@ -121,6 +125,10 @@ def sample_sharded(XX, t, n_chains, NumOfIterations=6000, BurnIn=1000, NumOfLeap
         raise ValueError("RMHMC takes its run arguments by name (NumOfLeapFrogSteps, StepSize, NumOfNewtonSteps), not in sampler_args")
     if diagnostics:
         _capi.diag_lags(NumOfIterations - BurnIn, max_lag)
+        if gather not in ("samples", "summary"):
+            raise ValueError('gather must be "samples" or "summary"')
+    if quantiles is not None:
+        quantiles = _capi.quant_probs(quantiles)
         if gather not in ("samples", "summary"):
             raise ValueError('gather must be "samples" or "summary"')
     if sampler != "RMHMC":
@@ -144,6 +152,8 @@ def sample_sharded(XX, t, n_chains, NumOfIterations=6000, BurnIn=1000, NumOfLeap
         raise _capi.RmhmcError(-4, "%s does not export the output descriptor (include/rmhmc_out.h): only RMHMC can be sharded" % lib.path)
     if diagnostics and not (lib.has_out and lib.has_diag):
         raise _capi.RmhmcError(-4, "%s does not export the cross-chain diagnostics (include/rmhmc_diag.h, include/rmhmc_out.h)" % lib.path)
+    if quantiles is not None and not (lib.has_out and lib.has_quant):
+        raise _capi.RmhmcError(-4, "%s does not export the posterior quantiles (include/rmhmc_quant.h, include/rmhmc_out.h)" % lib.path)
     # where the collective runs (HBM for RCCL, host memory for gloo) and where the sampler writes its outputs: the HIP library always
     # writes through device pointers of its own GPU, whatever the backend; with gloo those tensors take one hop to the host first
     cdev = _t.device("cuda", local_rank) if backend == "nccl" else _t.device("cpu")
@@ -157,11 +167,12 @@ def sample_sharded(XX, t, n_chains, NumOfIterations=6000, BurnIn=1000, NumOfLeap
     S = NumOfIterations - BurnIn
     if sampler != "RMHMC":
         return _sharded_to(sampler, dict(sampler_args or {}), XX, t, n_chains, NumOfIterations, BurnIn, seed, theta0, alpha, gather, lib,
-                           options, gpu, odev, cdev, start, end, counts, diagnostics=diagnostics, max_lag=max_lag)
-    if diagnostics:   # the same run through rmhmc_sample_to: its samples stay where the partial is computed
+                           options, gpu, odev, cdev, start, end, counts, diagnostics=diagnostics, max_lag=max_lag, quantiles=quantiles)
+    if diagnostics or quantiles is not None:   # the same run through rmhmc_sample_to: its samples stay where the partial is computed
         args = dict(L=NumOfLeapFrogSteps, eps=StepSize, K=NumOfNewtonSteps)
         return _sharded_to(sampler, args, XX, t, n_chains, NumOfIterations, BurnIn, seed, theta0, alpha, gather, lib, options, gpu, odev,
-                           cdev, start, end, counts, diagnostics=True, max_lag=max_lag, flags=_capi.COMPAT if compat else 0)
+                           cdev, start, end, counts, diagnostics=diagnostics, max_lag=max_lag, flags=_capi.COMPAT if compat else 0,
+                           quantiles=quantiles)
     if n_local > 0:
         th = None if theta0 is None else np.broadcast_to(theta0, (n_chains, D))[start:end]
         with lib.context(N, D, n_local, flags=(_capi.COMPAT if compat else 0) | _capi.auto_metric_flags(D, n_local, M=N), device=gpu,
@@ -202,9 +213,10 @@ def sample_sharded(XX, t, n_chains, NumOfIterations=6000, BurnIn=1000, NumOfLeap
 
 
 def _sharded_to(sampler, args, XX, t, n_chains, n_iter, burn_in, seed, theta0, alpha, gather, lib, options, gpu, odev, cdev, start, end,
-                counts, diagnostics=False, max_lag=None, flags=0):
+                counts, diagnostics=False, max_lag=None, flags=0, quantiles=None):
     """sample_sharded for the samplers that run through include/rmhmc_out.h: same shards, same gathers, the sampler's own counters;
-    diagnostics: one more gather, of every rank's partial (include/rmhmc_diag.h).  flags: context flags besides the metric's"""
+    diagnostics: one more gather, of every rank's partial (include/rmhmc_diag.h); quantiles: eight all_reduces of every rank's histogram
+    (include/rmhmc_quant.h), while the shard's samples and its context are there.  flags: context flags besides the metric's"""
     import torch as _t
     dist = _dist()
     rank, world = dist.get_rank(), dist.get_world_size()
@@ -218,8 +230,9 @@ def _sharded_to(sampler, args, XX, t, n_chains, n_iter, burn_in, seed, theta0, a
         flags |= _capi.auto_metric_flags(D, n_local, M=N) if has_metric else 0
         with lib.context(N, D, n_local, flags=flags, device=gpu, options=options) as ctx:
             ctx.set_data(XX, t, alpha)
-            st = ctx.sample_to(key, n_iter, burn_in, where="device", device=odev, samples=gather == "samples", stats=gather == "summary",
-                               seed=seed, chain_offset=start, diagnostics=diagnostics, max_lag=max_lag, **args)
+            st = ctx.sample_to(key, n_iter, burn_in, where="device", device=odev, samples=gather == "samples" or quantiles is not None,
+                               stats=gather == "summary", seed=seed, chain_offset=start, diagnostics=diagnostics, max_lag=max_lag, **args)
+            qt = _sharded_quantiles(ctx, st["samples"], quantiles, D, cdev, lib) if quantiles is not None else None
         part = st["diag_partial"] if diagnostics else None
         secs = st["seconds"]
         payload = st["samples"] if gather == "samples" else _t.cat([st["mean"], st["var"], nanmin_rows(st["ess"])], dim=1)
@@ -229,6 +242,7 @@ def _sharded_to(sampler, args, XX, t, n_chains, n_iter, burn_in, seed, theta0, a
         payload = _t.zeros((0, S, D) if gather == "samples" else (0, 2 * D + 1), dtype=_t.float64, device=odev)
         cnt = {k: _t.zeros((0, D) if vec else (0,), dtype=_t.float64 if vec else _t.int64, device=odev) for k, vec in counters}
         part = _t.from_numpy(_capi.diag_identity(_capi.diag_lags(S, max_lag)[1], D)).to(odev) if diagnostics else None
+        qt = _sharded_quantiles(None, None, quantiles, D, cdev, lib) if quantiles is not None else None
     tt = _t.tensor([secs], dtype=_t.float64, device=cdev)
     dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     ints = [k for k, vec in counters if not vec]
@@ -248,4 +262,20 @@ def _sharded_to(sampler, args, XX, t, n_chains, n_iter, burn_in, seed, theta0, a
     if diagnostics:
         dg = _capi.diag_finish(list(parts.cpu().numpy()), S // 2, lib=lib)
         info.update({k: dg[k] for k in _capi.DIAG_KEYS})
+    if quantiles is not None:
+        info.update(quantiles=qt["quantiles"], quantile_draws=qt["draws_used"])
     return g, float(tt.item()), info
+
+
+def _sharded_quantiles(ctx, samples, probs, D, cdev, lib):
+    """The select of include/rmhmc_quant.h over the shards: per round this rank's histogram (ctx None: an empty shard, the identity without
+    a launch) is summed over the ranks by one all_reduce where the collective runs, and every rank steps on the sum"""
+    import torch as _t
+    dist = _dist()
+
+    def hist(round, prefix, K):
+        h = ctx.quant_hist(samples, round, prefix) if ctx is not None else _t.from_numpy(_capi.quant_identity(K, D))
+        h = h.to(cdev)
+        dist.all_reduce(h, op=dist.ReduceOp.SUM)
+        return [h]
+    return _capi.quant_select(hist, probs, D, lib=lib)
