@@ -863,16 +863,17 @@ void fill_ll(rmhmc_ctx* ctx, long long* p, long long v, size_t n) {
   hipLaunchKernelGGL(k_fill_ll, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, p, v, n);
 }
 
-// host [n][D] -> device [n][DP] (padding stays zero) and back
-int upload_vec(rmhmc_ctx* ctx, double* dst, const double* src) {
-  HIPCK(hipMemcpy2DAsync(dst, ctx->DP * sizeof(double), src, ctx->D * sizeof(double), ctx->D * sizeof(double), ctx->n,
-                         hipMemcpyHostToDevice, ctx->stream));
+// the first `cols` doubles of each of `rows` rows, src [rows][src_cols] -> dst [rows][dst_cols]: how row padding is added or stripped
+int copy_rows(rmhmc_ctx* ctx, double* dst, size_t dst_cols, const double* src, size_t src_cols, size_t cols, size_t rows, hipMemcpyKind kind) {
+  HIPCK(hipMemcpy2DAsync(dst, dst_cols * sizeof(double), src, src_cols * sizeof(double), cols * sizeof(double), rows, kind, ctx->stream));
   return RMHMC_OK;
 }
+// host [n][D] -> device [n][DP] (padding stays zero) and back
+int upload_vec(rmhmc_ctx* ctx, double* dst, const double* src) {
+  return copy_rows(ctx, dst, ctx->DP, src, ctx->D, ctx->D, ctx->n, hipMemcpyHostToDevice);
+}
 int download_vec(rmhmc_ctx* ctx, double* dst, const double* src) {
-  HIPCK(hipMemcpy2DAsync(dst, ctx->D * sizeof(double), src, ctx->DP * sizeof(double), ctx->D * sizeof(double), ctx->n,
-                         hipMemcpyDeviceToHost, ctx->stream));
-  return RMHMC_OK;
+  return copy_rows(ctx, dst, ctx->D, src, ctx->DP, ctx->D, ctx->n, hipMemcpyDeviceToHost);
 }
 template <typename T>
 int download(rmhmc_ctx* ctx, T* dst, const T* src, size_t count) {
@@ -889,6 +890,12 @@ int sync(rmhmc_ctx* ctx) {
   HIPCK(hipStreamSynchronize(ctx->stream));
   HIPCK(hipGetLastError());
   return RMHMC_OK;
+}
+// ... after work that was queued with code rc, which may have failed half way: the stream is drained on every path, and the launcher's
+// code goes before the synchronise's
+int sync_after(rmhmc_ctx* ctx, int rc) {
+  const int rs = sync(ctx);
+  return rc != RMHMC_OK ? rc : rs;
 }
 
 #define RC(x) do { int rc_ = (x); if (rc_ != RMHMC_OK) return rc_; } while (0)
@@ -1343,6 +1350,26 @@ static int init_chains(rmhmc_ctx* ctx, const double* theta0_host /* [n][D] or NU
   return reset_chains(ctx);  // (synchronises: the theta0 staging vector goes out of scope)
 }
 
+// The read-back of a single transition, shared by rmhmc_transition, hmc_transition_body and rmhmc_mmala_transition: the current point
+// into w, the optional outputs (NULL: not wanted, or the sampler has none), then the synchronise, which also drains the downloads the
+// caller queued before it, and the accepted counter narrowed to int32.
+static int transition_out(rmhmc_ctx* ctx, double* w, int32_t* accepted_out, int32_t* nsteps_out, double* H_cur_out, double* H_prop_out,
+                          double* w_prop_out, double* p_prop_out, int32_t* status_out) {
+  const Chains& ch = ctx->batch.ch;
+  std::vector<long long> acc(ctx->n);
+  RC(download_vec(ctx, w, ch.cur.w));
+  RC(download(ctx, acc.data(), ch.accepted, ctx->n));
+  if (nsteps_out) RC(download(ctx, nsteps_out, ch.nsteps_last, ctx->n));
+  if (H_cur_out) RC(download(ctx, H_cur_out, ch.Hcur, ctx->n));
+  if (H_prop_out) RC(download(ctx, H_prop_out, ch.Hprop, ctx->n));
+  if (w_prop_out) RC(download_vec(ctx, w_prop_out, ch.trj.w));
+  if (p_prop_out) RC(download_vec(ctx, p_prop_out, ch.p));
+  if (status_out) RC(download(ctx, status_out, ch.status, ctx->n));
+  RC(sync(ctx));
+  if (accepted_out) for (int64_t c = 0; c < ctx->n; ++c) accepted_out[c] = (int32_t)acc[c];
+  return RMHMC_OK;
+}
+
 int rmhmc_transition(rmhmc_ctx* ctx, double* w, const double* z, const double* u_len, const double* g_dir, const double* u_acc,
                      int32_t L, double eps, int32_t K, int32_t* accepted_out, int32_t* nsteps_out, double* H_cur_out,
                      double* H_prop_out, double* w_prop_out, double* p_prop_out, double* half_logdet_prop_out, int32_t* status_out) {
@@ -1367,19 +1394,8 @@ int rmhmc_transition(rmhmc_ctx* ctx, double* w, const double* z, const double* u
       launch_iter_end(ctx, run, g, ib);
     }
   }
-  std::vector<long long> acc(ctx->n);
-  RC(download_vec(ctx, w, ctx->batch.ch.cur.w));
-  RC(download(ctx, acc.data(), ctx->batch.ch.accepted, ctx->n));
-  if (nsteps_out) RC(download(ctx, nsteps_out, ctx->batch.ch.nsteps_last, ctx->n));
-  if (H_cur_out) RC(download(ctx, H_cur_out, ctx->batch.ch.Hcur, ctx->n));
-  if (H_prop_out) RC(download(ctx, H_prop_out, ctx->batch.ch.Hprop, ctx->n));
-  if (w_prop_out) RC(download_vec(ctx, w_prop_out, ctx->batch.ch.trj.w));
-  if (p_prop_out) RC(download_vec(ctx, p_prop_out, ctx->batch.ch.p));
   if (half_logdet_prop_out) RC(download(ctx, half_logdet_prop_out, ctx->batch.ch.trj.hld, ctx->n));
-  if (status_out) RC(download(ctx, status_out, ctx->batch.ch.status, ctx->n));
-  RC(sync(ctx));
-  if (accepted_out) for (int64_t c = 0; c < ctx->n; ++c) accepted_out[c] = (int32_t)acc[c];
-  return RMHMC_OK;
+  return transition_out(ctx, w, accepted_out, nsteps_out, H_cur_out, H_prop_out, w_prop_out, p_prop_out, status_out);
 }
 
 // ---- bulk entry points --------------------------------------------------------------------------
@@ -1873,19 +1889,8 @@ static int hmc_transition_body(rmhmc_ctx* ctx, Sampler sampler, double* w, const
   RC(upload(ctx, ctx->d_uacc, u_acc, ctx->n));
   const IterBase ib{1, 0, 0, nullptr, true, false};
   for (int s = 0; s < L; ++s) launch_global_step(ctx, run, ctx->batch, ib);
-  std::vector<long long> acc(ctx->n);
-  RC(download_vec(ctx, w, ctx->batch.ch.cur.w));
-  RC(download(ctx, acc.data(), ctx->batch.ch.accepted, ctx->n));
-  if (nsteps_out) RC(download(ctx, nsteps_out, ctx->batch.ch.nsteps_last, ctx->n));
-  if (H_cur_out) RC(download(ctx, H_cur_out, ctx->batch.ch.Hcur, ctx->n));
-  if (H_prop_out) RC(download(ctx, H_prop_out, ctx->batch.ch.Hprop, ctx->n));
-  if (w_prop_out) RC(download_vec(ctx, w_prop_out, ctx->batch.ch.trj.w));
-  if (p_prop_out) RC(download_vec(ctx, p_prop_out, ctx->batch.ch.p));
-  if (status_out) RC(download(ctx, status_out, ctx->batch.ch.status, ctx->n));
   if (loglik_out && sampler == TPHMC) RC(download(ctx, loglik_out, ctx->d_ais_ll, ctx->n));
-  RC(sync(ctx));
-  if (accepted_out) for (int64_t c = 0; c < ctx->n; ++c) accepted_out[c] = (int32_t)acc[c];
-  return RMHMC_OK;
+  return transition_out(ctx, w, accepted_out, nsteps_out, H_cur_out, H_prop_out, w_prop_out, p_prop_out, status_out);
 }
 
 int rmhmc_hmc_transition(rmhmc_ctx* ctx, double* w, const double* z, const double* u_len, const double* u_acc, int32_t L, double eps,
@@ -2108,14 +2113,7 @@ int rmhmc_mmala_transition(rmhmc_ctx* ctx, double* w, const double* z, const dou
   RC(upload(ctx, ctx->d_uacc, u_acc, ctx->n));
   const IterBase ib{1, 0, 0, nullptr, true, false};
   launch_mmala_step(ctx, run, ctx->batch, ib);
-  std::vector<long long> acc(ctx->n);
-  RC(download_vec(ctx, w, ctx->batch.ch.cur.w));
-  RC(download(ctx, acc.data(), ctx->batch.ch.accepted, ctx->n));
-  if (ratio_out) RC(download(ctx, ratio_out, ctx->batch.ch.Hprop, ctx->n));
-  if (w_prop_out) RC(download_vec(ctx, w_prop_out, ctx->batch.ch.trj.w));
-  RC(sync(ctx));
-  if (accepted_out) for (int64_t c = 0; c < ctx->n; ++c) accepted_out[c] = (int32_t)acc[c];
-  return RMHMC_OK;
+  return transition_out(ctx, w, accepted_out, nullptr, nullptr, ratio_out /* Hprop */, w_prop_out, nullptr, nullptr);
 }
 
 // Runs the simplified mMALA sampler; the saved states go to the device buffer d_samples ([n][S][D]), the accepted proposals stay in
@@ -2191,8 +2189,7 @@ static int chains_state_impl(rmhmc_ctx* ctx, double* w_out, int64_t* iters_out, 
   NEED_DATA(ctx);
   if (!ctx->chains_ready) return fail(ctx, RMHMC_ERR_INVALID, "chains_state: rmhmc_chains_init has not been called");
   const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  if (w_out)  // strip the padding: [n][DP] -> [n][D]
-    HIPCK(hipMemcpy2DAsync(w_out, ctx->D * sizeof(double), ctx->batch.ch.cur.w, ctx->DP * sizeof(double), ctx->D * sizeof(double), ctx->n, kind, ctx->stream));
+  if (w_out) RC(copy_rows(ctx, w_out, ctx->D, ctx->batch.ch.cur.w, ctx->DP, ctx->D, ctx->n, kind));  // strip the padding: [n][DP] -> [n][D]
   static_assert(sizeof(long long) == sizeof(int64_t), "int64");
   if (iters_out) HIPCK(hipMemcpyAsync(iters_out, ctx->batch.ch.iter, sizeof(int64_t) * ctx->n, kind, ctx->stream));
   if (accept_out) HIPCK(hipMemcpyAsync(accept_out, ctx->batch.ch.accepted, sizeof(int64_t) * ctx->n, kind, ctx->stream));
@@ -2338,9 +2335,7 @@ int amh_sample_body(rmhmc_ctx* ctx, const char* who, int64_t n_iter, int64_t bur
     p.samples = d_samples; p.seed = seed; p.chain_offset = chain_offset; p.n_iter = n_iter; p.burn_in = burn_in;
     RC(amh_run(ctx, p, theta0, seconds_out));
     RC(counter_out(ctx, out, accepted_out, ctx->batch.ch.accepted));
-    if (sd_out)  // [n][DP] -> [n][D]
-      HIPCK(hipMemcpy2DAsync(sd_out, ctx->D * sizeof(double), ctx->batch.ch.PM, ctx->DP * sizeof(double), ctx->D * sizeof(double), ctx->n,
-                             out_kind(out), ctx->stream));
+    if (sd_out) RC(copy_rows(ctx, sd_out, ctx->D, ctx->batch.ch.PM, ctx->DP, ctx->D, ctx->n, out_kind(out)));  // [n][DP] -> [n][D]
     return RMHMC_OK;
   });
 }
@@ -2370,22 +2365,19 @@ int rmhmc_amh_replay(rmhmc_ctx* ctx, int64_t n_iter, int64_t burn_in, const doub
     return fail(ctx, RMHMC_ERR_INVALID, "amh_replay: need z, u, w_out, ljl_out, decisions_out and 0 <= burn_in < n_iter < 2^32");
   ctx->chains_ready = false;
   const size_t n = ctx->n, D = ctx->D, T = (size_t)n_iter, vec = n * T * D;
+  CallMem mem(ctx);
   double *d_z = nullptr, *d_u = nullptr, *d_w = nullptr, *d_l = nullptr;
   int8_t* d_dec = nullptr;
-  int rc = [&]() -> int {
-    HIPCK(hipMalloc((void**)&d_z, sizeof(double) * vec)); HIPCK(hipMalloc((void**)&d_u, sizeof(double) * vec));
-    HIPCK(hipMalloc((void**)&d_w, sizeof(double) * vec)); HIPCK(hipMalloc((void**)&d_l, sizeof(double) * n * T));
-    HIPCK(hipMalloc((void**)&d_dec, vec));
-    RC(upload(ctx, d_z, z, vec)); RC(upload(ctx, d_u, u, vec));
-    AmhParams p{};
-    p.z_in = d_z; p.u_in = d_u; p.w_out = d_w; p.ljl_out = d_l; p.dec_out = d_dec; p.n_iter = n_iter; p.burn_in = burn_in;
-    RC(amh_run(ctx, p, theta0, nullptr));
-    RC(download(ctx, w_out, d_w, vec)); RC(download(ctx, ljl_out, d_l, n * T)); RC(download(ctx, decisions_out, d_dec, vec));
-    if (sd_out) RC(download_vec(ctx, sd_out, ctx->batch.ch.PM));
-    return sync(ctx);
-  }();
-  for (void* q : {(void*)d_z, (void*)d_u, (void*)d_w, (void*)d_l, (void*)d_dec}) if (q) (void)hipFree(q);
-  return rc;
+  RC(mem.alloc(&d_z, sizeof(double) * vec)); RC(mem.alloc(&d_u, sizeof(double) * vec));
+  RC(mem.alloc(&d_w, sizeof(double) * vec)); RC(mem.alloc(&d_l, sizeof(double) * n * T));
+  RC(mem.alloc(&d_dec, vec));
+  RC(upload(ctx, d_z, z, vec)); RC(upload(ctx, d_u, u, vec));
+  AmhParams p{};
+  p.z_in = d_z; p.u_in = d_u; p.w_out = d_w; p.ljl_out = d_l; p.dec_out = d_dec; p.n_iter = n_iter; p.burn_in = burn_in;
+  RC(amh_run(ctx, p, theta0, nullptr));
+  RC(download(ctx, w_out, d_w, vec)); RC(download(ctx, ljl_out, d_l, n * T)); RC(download(ctx, decisions_out, d_dec, vec));
+  if (sd_out) RC(download_vec(ctx, sd_out, ctx->batch.ch.PM));
+  return sync(ctx);
 }
 
 }  // extern "C"
@@ -2395,28 +2387,42 @@ namespace {
 
 const char* const kIwlsDMsg = "iwls: D > 64 is not supported (64 < D <= 256 needs a blocked factorisation of G^-1 + 1e-6 I)";
 
-// device state of one IWLS call: l() of cur / trj ([2][n]), the saturated flag and count, m(cur.w)
-struct IwlsState {
-  double* lq = nullptr;
-  int* sat = nullptr;
-  long long* nsat = nullptr;
-  double* mcur = nullptr;
-};
-
-int iwls_alloc(rmhmc_ctx* ctx, IwlsState& s, IwlsParams& p, int32_t compat) {
-  const size_t n = ctx->n;
-  HIPCK(hipMalloc((void**)&s.lq, sizeof(double) * 2 * n));
-  HIPCK(hipMalloc((void**)&s.sat, sizeof(int) * n));
-  HIPCK(hipMalloc((void**)&s.nsat, sizeof(long long) * n));
-  HIPCK(hipMalloc((void**)&s.mcur, sizeof(double) * n * ctx->DP));
-  HIPCK(hipMemsetAsync(s.lq, 0, sizeof(double) * 2 * n, ctx->stream));
-  HIPCK(hipMemsetAsync(s.nsat, 0, sizeof(long long) * n, ctx->stream));
-  p.compat = compat ? 1 : 0;
-  p.lq_cur = s.lq; p.lq_trj = s.lq + n; p.sat = s.sat; p.nsat = s.nsat; p.mcur = s.mcur;
+// The iteration loop of IWLS and Gibbs.  Sampling: before iterations i % every == 0 and burn_in, report(i) does what the sampler's
+// reference prints there (it synchronises if it has to); before iteration burn_in the stream is drained and the timer restarts.
+// step(i) queues the launches of iteration i.
+template <typename Report, typename Step>
+int timed_iterations(rmhmc_ctx* ctx, long long n_iter, long long burn_in, bool sampling, long long every, double* seconds_out, Report report,
+                     Step step) {
+  auto t0 = std::chrono::steady_clock::now();
+  for (long long i = 0; i < n_iter; ++i) {
+    if (sampling && (i % every == 0 || i == burn_in)) {
+      RC(report(i));
+      if (i == burn_in) {
+        RC(sync(ctx));
+        t0 = std::chrono::steady_clock::now();
+      }
+    }
+    step(i);
+    HIPCK(hipGetLastError());
+    flow_tick(ctx);
+  }
+  RC(sync(ctx));
+  if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return RMHMC_OK;
 }
-void iwls_free(IwlsState& s) {
-  for (void* q : {(void*)s.lq, (void*)s.sat, (void*)s.nsat, (void*)s.mcur}) if (q) (void)hipFree(q);
+
+// device state of one IWLS call, taken from mem into p: l() of cur / trj ([2][n]), the saturated flag and count, m(cur.w)
+int iwls_alloc(rmhmc_ctx* ctx, CallMem& mem, IwlsParams& p, int32_t compat) {
+  const size_t n = ctx->n;
+  RC(mem.alloc(&p.lq_cur, sizeof(double) * 2 * n));
+  RC(mem.alloc(&p.sat, sizeof(int) * n));
+  RC(mem.alloc(&p.nsat, sizeof(long long) * n));
+  RC(mem.alloc(&p.mcur, sizeof(double) * n * ctx->DP));
+  HIPCK(hipMemsetAsync(p.lq_cur, 0, sizeof(double) * 2 * n, ctx->stream));
+  HIPCK(hipMemsetAsync(p.nsat, 0, sizeof(long long) * n, ctx->stream));
+  p.compat = compat ? 1 : 0;
+  p.lq_trj = p.lq_cur + n;
+  return RMHMC_OK;
 }
 
 void launch_iwls_ljit(rmhmc_ctx* ctx, Group& g, const double* Ginv, double* out) {
@@ -2448,31 +2454,21 @@ int iwls_run(rmhmc_ctx* ctx, IwlsParams p, long long n_iter, bool sampling, cons
   RC(mmala_init(ctx, theta0, false));
   if (p.compat) launch_iwls_ljit(ctx, g, g.ch.cur.Ginv, p.lq_cur);
   std::vector<long long> acc;
-  auto t0 = std::chrono::steady_clock::now();
-  for (long long i = 0; i < n_iter; ++i) {
-    if (sampling && (i % 1000 == 0 || i == p.burn_in)) {
-      if (ctx->progress_fn) {
-        acc.resize(ctx->n);
-        RC(download(ctx, acc.data(), ctx->batch.ch.accepted, ctx->n));
-        RC(sync(ctx));
-        long long a = 0;
-        for (long long x : acc) a += x;
-        if (i % 1000 == 0) ctx->progress_fn(RMHMC_EV_PROGRESS, i, a, i * ctx->n, ctx->progress_user);
-        if (i == p.burn_in) ctx->progress_fn(RMHMC_EV_BURNIN_DONE, i, a, i * ctx->n, ctx->progress_user);
-      }
-      if (i == p.burn_in) {
-        RC(sync(ctx));
-        t0 = std::chrono::steady_clock::now();
-      }
-    }
+  const auto report = [&](long long i) -> int {
+    if (!ctx->progress_fn) return RMHMC_OK;
+    acc.resize(ctx->n);
+    RC(download(ctx, acc.data(), ctx->batch.ch.accepted, ctx->n));
+    RC(sync(ctx));
+    long long a = 0;
+    for (long long x : acc) a += x;
+    if (i % 1000 == 0) ctx->progress_fn(RMHMC_EV_PROGRESS, i, a, i * ctx->n, ctx->progress_user);
+    if (i == p.burn_in) ctx->progress_fn(RMHMC_EV_BURNIN_DONE, i, a, i * ctx->n, ctx->progress_user);
+    return RMHMC_OK;
+  };
+  return timed_iterations(ctx, n_iter, p.burn_in, sampling, 1000, seconds_out, report, [&](long long i) {
     p.it = i;
     launch_iwls_iter(ctx, g, p);
-    HIPCK(hipGetLastError());
-    flow_tick(ctx);
-  }
-  RC(sync(ctx));
-  if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  return RMHMC_OK;
+  });
 }
 
 int iwls_sample_body(rmhmc_ctx* ctx, const char* who, int64_t n_iter, int64_t burn_in, int32_t compat, uint64_t seed, int64_t chain_offset,
@@ -2483,17 +2479,15 @@ int iwls_sample_body(rmhmc_ctx* ctx, const char* who, int64_t n_iter, int64_t bu
   if (ctx->D > 64) return fail(ctx, RMHMC_ERR_UNSUPPORTED, kIwlsDMsg);
   ctx->chains_ready = false;
   const int64_t S = n_iter - burn_in;
-  IwlsState s;
-  const int rc = sample_to(ctx, S, out, [&](double* d_samples) -> int {
+  CallMem mem(ctx);  // (outside the core: the copy of nsat that counter_out queues is drained by write_out)
+  return sample_to(ctx, S, out, [&](double* d_samples) -> int {
     IwlsParams p{};
-    RC(iwls_alloc(ctx, s, p, compat));
+    RC(iwls_alloc(ctx, mem, p, compat));
     p.seed = seed; p.chain_offset = chain_offset; p.burn_in = burn_in; p.S = S; p.samples = d_samples; p.T = n_iter;
     RC(iwls_run(ctx, p, n_iter, true, theta0, seconds_out));
     RC(counter_out(ctx, out, accepted_out, ctx->batch.ch.accepted));
-    return counter_out(ctx, out, saturated_out, s.nsat);
+    return counter_out(ctx, out, saturated_out, p.nsat);
   });
-  iwls_free(s);
-  return rc;
 }
 
 }  // namespace
@@ -2523,29 +2517,24 @@ int rmhmc_iwls_replay(rmhmc_ctx* ctx, int64_t n_iter, int32_t compat, const doub
   if (ctx->D > 64) return fail(ctx, RMHMC_ERR_UNSUPPORTED, kIwlsDMsg);
   ctx->chains_ready = false;
   const size_t n = ctx->n, D = ctx->D, T = (size_t)n_iter, vec = n * T * D;
+  CallMem mem(ctx);
   double *d_wp = nullptr, *d_u = nullptr, *d_w = nullptr, *d_m = nullptr, *d_l = nullptr, *d_r = nullptr;
   int8_t* d_dec = nullptr;
-  IwlsState s;
-  int rc = [&]() -> int {
-    HIPCK(hipMalloc((void**)&d_wp, sizeof(double) * vec)); HIPCK(hipMalloc((void**)&d_u, sizeof(double) * n * T));
-    HIPCK(hipMalloc((void**)&d_w, sizeof(double) * vec)); HIPCK(hipMalloc((void**)&d_m, sizeof(double) * vec));
-    HIPCK(hipMalloc((void**)&d_l, sizeof(double) * n * T)); HIPCK(hipMalloc((void**)&d_r, sizeof(double) * n * T));
-    HIPCK(hipMalloc((void**)&d_dec, n * T));
-    RC(upload(ctx, d_wp, w_prop, vec)); RC(upload(ctx, d_u, u, n * T));
-    IwlsParams p{};
-    RC(iwls_alloc(ctx, s, p, compat));
-    p.T = n_iter; p.w_prop = d_wp; p.u_in = d_u; p.w_out = d_w; p.mean_out = d_m; p.ljl_out = d_l; p.ratio_out = d_r; p.dec_out = d_dec;
-    RC(iwls_run(ctx, p, n_iter, false, theta0, nullptr));
-    RC(download(ctx, w_out, d_w, vec));
-    if (mean_out) RC(download(ctx, mean_out, d_m, vec));
-    if (ljl_out) RC(download(ctx, ljl_out, d_l, n * T));
-    if (ratio_out) RC(download(ctx, ratio_out, d_r, n * T));
-    if (decisions_out) RC(download(ctx, decisions_out, d_dec, n * T));
-    return sync(ctx);
-  }();
-  for (void* q : {(void*)d_wp, (void*)d_u, (void*)d_w, (void*)d_m, (void*)d_l, (void*)d_r, (void*)d_dec}) if (q) (void)hipFree(q);
-  iwls_free(s);
-  return rc;
+  RC(mem.alloc(&d_wp, sizeof(double) * vec)); RC(mem.alloc(&d_u, sizeof(double) * n * T));
+  RC(mem.alloc(&d_w, sizeof(double) * vec)); RC(mem.alloc(&d_m, sizeof(double) * vec));
+  RC(mem.alloc(&d_l, sizeof(double) * n * T)); RC(mem.alloc(&d_r, sizeof(double) * n * T));
+  RC(mem.alloc(&d_dec, n * T));
+  RC(upload(ctx, d_wp, w_prop, vec)); RC(upload(ctx, d_u, u, n * T));
+  IwlsParams p{};
+  RC(iwls_alloc(ctx, mem, p, compat));
+  p.T = n_iter; p.w_prop = d_wp; p.u_in = d_u; p.w_out = d_w; p.mean_out = d_m; p.ljl_out = d_l; p.ratio_out = d_r; p.dec_out = d_dec;
+  RC(iwls_run(ctx, p, n_iter, false, theta0, nullptr));
+  RC(download(ctx, w_out, d_w, vec));
+  if (mean_out) RC(download(ctx, mean_out, d_m, vec));
+  if (ljl_out) RC(download(ctx, ljl_out, d_l, n * T));
+  if (ratio_out) RC(download(ctx, ratio_out, d_r, n * T));
+  if (decisions_out) RC(download(ctx, decisions_out, d_dec, n * T));
+  return sync(ctx);
 }
 
 }  // extern "C"
@@ -2555,28 +2544,18 @@ namespace {
 
 const char* const kGibbsDMsg = "gibbs: D > 64 is not supported (64 < D <= 256 needs a blocked inverse and sweep)";
 
-// device state of one Gibbs call (GibbsParams); G, V and Lt are the context's Gq, trj.Ginv and trj.L
-struct GibbsState {
-  double *Z = nullptr, *lam = nullptr, *ilam = nullptr, *B = nullptr, *beta = nullptr;
-  long long *capped = nullptr, *dead = nullptr;
-  int* stop = nullptr;
-};
-
-int gibbs_alloc(rmhmc_ctx* ctx, GibbsState& s, GibbsParams& p) {
+// device state of one Gibbs call, taken from mem into p; G, V and Lt are the context's Gq, trj.Ginv and trj.L
+int gibbs_alloc(rmhmc_ctx* ctx, CallMem& mem, GibbsParams& p) {
   const size_t n = ctx->n, Mp = ctx->Mp, DP = ctx->DP;
-  HIPCK(hipMalloc((void**)&s.Z, sizeof(double) * n * Mp)); HIPCK(hipMalloc((void**)&s.lam, sizeof(double) * n * Mp));
-  HIPCK(hipMalloc((void**)&s.ilam, sizeof(double) * n * Mp));
-  HIPCK(hipMalloc((void**)&s.B, sizeof(double) * n * DP)); HIPCK(hipMalloc((void**)&s.beta, sizeof(double) * n * DP));
-  HIPCK(hipMalloc((void**)&s.capped, sizeof(long long) * n)); HIPCK(hipMalloc((void**)&s.stop, sizeof(int) * n));
-  HIPCK(hipMalloc((void**)&s.dead, sizeof(long long) * n));
-  HIPCK(hipMemsetAsync(s.B, 0, sizeof(double) * n * DP, ctx->stream));
-  HIPCK(hipMemsetAsync(s.beta, 0, sizeof(double) * n * DP, ctx->stream));
-  p.Z = s.Z; p.lam = s.lam; p.ilam = s.ilam; p.B = s.B; p.beta = s.beta; p.capped = s.capped; p.stop = s.stop; p.dead = s.dead;
+  RC(mem.alloc(&p.Z, sizeof(double) * n * Mp)); RC(mem.alloc(&p.lam, sizeof(double) * n * Mp));
+  RC(mem.alloc(&p.ilam, sizeof(double) * n * Mp));
+  RC(mem.alloc(&p.B, sizeof(double) * n * DP)); RC(mem.alloc(&p.beta, sizeof(double) * n * DP));
+  RC(mem.alloc(&p.capped, sizeof(long long) * n)); RC(mem.alloc(&p.stop, sizeof(int) * n));
+  RC(mem.alloc(&p.dead, sizeof(long long) * n));
+  HIPCK(hipMemsetAsync(p.B, 0, sizeof(double) * n * DP, ctx->stream));
+  HIPCK(hipMemsetAsync(p.beta, 0, sizeof(double) * n * DP, ctx->stream));
   p.G = ctx->batch.ch.Gq; p.V = ctx->batch.ch.trj.Ginv; p.Lt = ctx->batch.ch.trj.L;
   return RMHMC_OK;
-}
-void gibbs_free(GibbsState& s) {
-  for (void* q : {(void*)s.Z, (void*)s.lam, (void*)s.ilam, (void*)s.B, (void*)s.beta, (void*)s.capped, (void*)s.stop, (void*)s.dead}) if (q) (void)hipFree(q);
 }
 
 // one iteration of every chain
@@ -2606,26 +2585,16 @@ int gibbs_run_body(rmhmc_ctx* ctx, GibbsParams p, long long n_iter, bool samplin
   fill_int(ctx, ctx->batch.ch.phase, 1, ctx->n);
   hipLaunchKernelGGL(k_gibbs_init, dim3((unsigned)ctx->n, (unsigned)((ctx->Mp + 255) / 256)), dim3(256), 0, ctx->stream, ctx->dd, p);
   HIPCK(hipGetLastError());
-  auto t0 = std::chrono::steady_clock::now();
-  for (long long i = 0; i < n_iter; ++i) {
-    if (sampling && (i % 100 == 0 || i == p.burn_in)) {
-      if (i % 100 == 0 && ctx->progress_fn) {
-        RC(sync(ctx));
-        ctx->progress_fn(RMHMC_EV_PROGRESS, i, 0, i * ctx->n, ctx->progress_user);
-      }
-      if (i == p.burn_in) {
-        RC(sync(ctx));
-        t0 = std::chrono::steady_clock::now();
-      }
-    }
+  const auto report = [&](long long i) -> int {
+    if (i % 100 != 0 || !ctx->progress_fn) return RMHMC_OK;
+    RC(sync(ctx));
+    ctx->progress_fn(RMHMC_EV_PROGRESS, i, 0, i * ctx->n, ctx->progress_user);
+    return RMHMC_OK;
+  };
+  return timed_iterations(ctx, n_iter, p.burn_in, sampling, 100, seconds_out, report, [&](long long i) {
     p.it = i;
     launch_gibbs_iter(ctx, p);
-    HIPCK(hipGetLastError());
-    flow_tick(ctx);
-  }
-  RC(sync(ctx));
-  if (seconds_out) *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  return RMHMC_OK;
+  });
 }
 int gibbs_run(rmhmc_ctx* ctx, const GibbsParams& p, long long n_iter, bool sampling, double* seconds_out) {
   const int rc = gibbs_run_body(ctx, p, n_iter, sampling, seconds_out);
@@ -2643,21 +2612,19 @@ int gibbs_sample_body(rmhmc_ctx* ctx, const char* who, int64_t n_iter, int64_t b
   if (ctx->D > 64) return fail(ctx, RMHMC_ERR_UNSUPPORTED, kGibbsDMsg);
   ctx->chains_ready = false;
   const int64_t S = n_iter - burn_in;
-  GibbsState s;
-  const int rc = sample_to(ctx, S, out, [&](double* d_samples) -> int {
+  CallMem mem(ctx);  // (outside the core: the copies that it queues from the state of the call are drained by write_out)
+  return sample_to(ctx, S, out, [&](double* d_samples) -> int {
     HIPCK(hipMemsetAsync(d_samples, 0xff, sizeof(double) * (size_t)ctx->n * (size_t)S * ctx->D, ctx->stream));  // NaN: the rows a stopped chain never writes
     GibbsParams p{};
-    RC(gibbs_alloc(ctx, s, p));
+    RC(gibbs_alloc(ctx, mem, p));
     p.seed = seed; p.chain_offset = chain_offset; p.burn_in = burn_in; p.S = S; p.samples = d_samples; p.T = n_iter;
     RC(gibbs_run(ctx, p, n_iter, true, seconds_out));
     const size_t n = ctx->n, N = ctx->M, Mp = ctx->Mp;  // [n][Mp] -> [n][N]
-    if (Z_host) HIPCK(hipMemcpy2DAsync(Z_host, N * sizeof(double), s.Z, Mp * sizeof(double), N * sizeof(double), n, hipMemcpyDeviceToHost, ctx->stream));
-    if (lam_host) HIPCK(hipMemcpy2DAsync(lam_host, N * sizeof(double), s.lam, Mp * sizeof(double), N * sizeof(double), n, hipMemcpyDeviceToHost, ctx->stream));
-    RC(counter_out(ctx, out, capped_out, s.capped));
-    return counter_out(ctx, out, stopped_out, s.dead);
+    if (Z_host) RC(copy_rows(ctx, Z_host, N, p.Z, Mp, N, n, hipMemcpyDeviceToHost));
+    if (lam_host) RC(copy_rows(ctx, lam_host, N, p.lam, Mp, N, n, hipMemcpyDeviceToHost));
+    RC(counter_out(ctx, out, capped_out, p.capped));
+    return counter_out(ctx, out, stopped_out, p.dead);
   });
-  gibbs_free(s);
-  return rc;
 }
 
 }  // namespace
@@ -2696,45 +2663,40 @@ int rmhmc_gibbs_replay(rmhmc_ctx* ctx, int64_t n_iter, const double* u_init, con
     }
   HIPCK(hipSetDevice(ctx->device));
   ctx->chains_ready = false;
+  CallMem mem(ctx);
   double *d_ui = nullptr, *d_us = nullptr, *d_T = nullptr, *d_ks = nullptr, *d_beta = nullptr, *d_B = nullptr;
   long long* d_off = nullptr;
   int* d_att = nullptr;
-  GibbsState s;
-  int rc = [&]() -> int {
-    const size_t nks = n * (size_t)std::max<int64_t>(ks_total, 1) * 3;
-    HIPCK(hipMalloc((void**)&d_ui, sizeof(double) * n * N)); HIPCK(hipMalloc((void**)&d_us, sizeof(double) * n * Tn * N));
-    HIPCK(hipMalloc((void**)&d_T, sizeof(double) * n * Tn * D)); HIPCK(hipMalloc((void**)&d_ks, sizeof(double) * nks));
-    HIPCK(hipMalloc((void**)&d_off, sizeof(long long) * n * Tn * (N + 1)));
-    HIPCK(hipMalloc((void**)&d_beta, sizeof(double) * n * Tn * D)); HIPCK(hipMalloc((void**)&d_B, sizeof(double) * n * Tn * D));
-    HIPCK(hipMalloc((void**)&d_att, sizeof(int) * n * Tn * N));
-    HIPCK(hipMemsetAsync(d_beta, 0, sizeof(double) * n * Tn * D, ctx->stream)); HIPCK(hipMemsetAsync(d_B, 0, sizeof(double) * n * Tn * D, ctx->stream));
-    HIPCK(hipMemsetAsync(d_att, 0, sizeof(int) * n * Tn * N, ctx->stream));
-    RC(upload(ctx, d_ui, u_init, n * N)); RC(upload(ctx, d_us, u_sweep, n * Tn * N)); RC(upload(ctx, d_T, T, n * Tn * D));
-    if (ks_total) RC(upload(ctx, d_ks, ks_draws, n * (size_t)ks_total * 3));
-    static_assert(sizeof(long long) == sizeof(int64_t), "int64");
-    RC(upload(ctx, d_off, (const long long*)ks_offset, n * Tn * (N + 1)));
-    GibbsParams p{};
-    RC(gibbs_alloc(ctx, s, p));
-    p.T = n_iter; p.u_init = d_ui; p.u_sweep = d_us; p.T_in = d_T; p.ks = d_ks; p.ks_off = d_off; p.ks_total = ks_total;
-    p.beta_out = d_beta; p.B_out = d_B; p.att_out = d_att; p.burn_in = n_iter;
-    RC(gibbs_run(ctx, p, n_iter, false, nullptr));
-    RC(download(ctx, beta_out, d_beta, n * Tn * D)); RC(download(ctx, B_out, d_B, n * Tn * D));
-    RC(download(ctx, (int*)attempts_out, d_att, n * Tn * N));
-    if (Z_out) HIPCK(hipMemcpy2DAsync(Z_out, N * sizeof(double), s.Z, Mp * sizeof(double), N * sizeof(double), n, hipMemcpyDeviceToHost, ctx->stream));
-    if (lam_out) HIPCK(hipMemcpy2DAsync(lam_out, N * sizeof(double), s.lam, Mp * sizeof(double), N * sizeof(double), n, hipMemcpyDeviceToHost, ctx->stream));
-    std::vector<long long> cp(n);
-    std::vector<int> sp(n);
-    RC(download(ctx, cp.data(), s.capped, n)); RC(download(ctx, sp.data(), s.stop, n));
-    RC(sync(ctx));
-    for (size_t c = 0; c < n; ++c) {
-      if (capped_out) capped_out[c] = cp[c];
-      if (status_out) status_out[c] = sp[c];
-    }
-    return RMHMC_OK;
-  }();
-  for (void* q : {(void*)d_ui, (void*)d_us, (void*)d_T, (void*)d_ks, (void*)d_off, (void*)d_beta, (void*)d_B, (void*)d_att}) if (q) (void)hipFree(q);
-  gibbs_free(s);
-  return rc;
+  const size_t nks = n * (size_t)std::max<int64_t>(ks_total, 1) * 3;
+  RC(mem.alloc(&d_ui, sizeof(double) * n * N)); RC(mem.alloc(&d_us, sizeof(double) * n * Tn * N));
+  RC(mem.alloc(&d_T, sizeof(double) * n * Tn * D)); RC(mem.alloc(&d_ks, sizeof(double) * nks));
+  RC(mem.alloc(&d_off, sizeof(long long) * n * Tn * (N + 1)));
+  RC(mem.alloc(&d_beta, sizeof(double) * n * Tn * D)); RC(mem.alloc(&d_B, sizeof(double) * n * Tn * D));
+  RC(mem.alloc(&d_att, sizeof(int) * n * Tn * N));
+  HIPCK(hipMemsetAsync(d_beta, 0, sizeof(double) * n * Tn * D, ctx->stream)); HIPCK(hipMemsetAsync(d_B, 0, sizeof(double) * n * Tn * D, ctx->stream));
+  HIPCK(hipMemsetAsync(d_att, 0, sizeof(int) * n * Tn * N, ctx->stream));
+  RC(upload(ctx, d_ui, u_init, n * N)); RC(upload(ctx, d_us, u_sweep, n * Tn * N)); RC(upload(ctx, d_T, T, n * Tn * D));
+  if (ks_total) RC(upload(ctx, d_ks, ks_draws, n * (size_t)ks_total * 3));
+  static_assert(sizeof(long long) == sizeof(int64_t), "int64");
+  RC(upload(ctx, d_off, (const long long*)ks_offset, n * Tn * (N + 1)));
+  GibbsParams p{};
+  RC(gibbs_alloc(ctx, mem, p));
+  p.T = n_iter; p.u_init = d_ui; p.u_sweep = d_us; p.T_in = d_T; p.ks = d_ks; p.ks_off = d_off; p.ks_total = ks_total;
+  p.beta_out = d_beta; p.B_out = d_B; p.att_out = d_att; p.burn_in = n_iter;
+  RC(gibbs_run(ctx, p, n_iter, false, nullptr));
+  RC(download(ctx, beta_out, d_beta, n * Tn * D)); RC(download(ctx, B_out, d_B, n * Tn * D));
+  RC(download(ctx, (int*)attempts_out, d_att, n * Tn * N));
+  if (Z_out) RC(copy_rows(ctx, Z_out, N, p.Z, Mp, N, n, hipMemcpyDeviceToHost));
+  if (lam_out) RC(copy_rows(ctx, lam_out, N, p.lam, Mp, N, n, hipMemcpyDeviceToHost));
+  std::vector<long long> cp(n);
+  std::vector<int> sp(n);
+  RC(download(ctx, cp.data(), p.capped, n)); RC(download(ctx, sp.data(), p.stop, n));
+  RC(sync(ctx));
+  for (size_t c = 0; c < n; ++c) {
+    if (capped_out) capped_out[c] = cp[c];
+    if (status_out) status_out[c] = sp[c];
+  }
+  return RMHMC_OK;
 }
 
 }  // extern "C"
@@ -2796,9 +2758,7 @@ int rmhmc_diag_partial_dev(rmhmc_ctx* ctx, const double* samples_dev, int64_t n,
   const int64_t T = (max_lag ? max_lag : H - 1) + 1;
   HIPCK(hipSetDevice(ctx->device));
   CallMem mem(ctx);
-  const int rc = launch_diag(ctx, samples_dev, n, S, P, T, partial_dev, mem);
-  const int rs = sync(ctx);
-  return rc != RMHMC_OK ? rc : rs;
+  return sync_after(ctx, launch_diag(ctx, samples_dev, n, S, P, T, partial_dev, mem));
 }
 
 int rmhmc_diag_finish(const double* const* partials, int32_t k, int64_t H, int64_t T, int32_t P, double* merged, double* rhat, double* ess,
@@ -2881,9 +2841,7 @@ int rmhmc_quant_hist_dev(rmhmc_ctx* ctx, const double* samples_dev, int64_t n, i
   if ((int64_t)K * P > INT32_MAX / QUANT_BINS) return fail(ctx, RMHMC_ERR_UNSUPPORTED, "quant_hist_dev: K * P * 256 must fit 31 bits");
   HIPCK(hipSetDevice(ctx->device));
   CallMem mem(ctx);
-  const int rc = launch_quant_hist(ctx, samples_dev, n * S, P, round, prefix, K, hist_dev, mem);
-  const int rs = sync(ctx);
-  return rc != RMHMC_OK ? rc : rs;
+  return sync_after(ctx, launch_quant_hist(ctx, samples_dev, n * S, P, round, prefix, K, hist_dev, mem));
 }
 
 int rmhmc_quant_plan(const int64_t* m, const double* probs, int32_t Q, int32_t P, int64_t* rank, double* frac) {
@@ -2928,8 +2886,7 @@ int rmhmc_quant_dev(rmhmc_ctx* ctx, const double* samples_dev, int64_t n, int64_
         hipError_t e = hipMemcpyAsync(hist.data(), d_hist, sizeof(double) * len, hipMemcpyDeviceToHost, ctx->stream);
         if (e != hipSuccess) rc = fail(ctx, RMHMC_ERR_RUNTIME, std::string(hipGetErrorString(e)) + " in quant_dev");
       }
-      const int rs = sync(ctx);
-      if (rc == RMHMC_OK) rc = rs;
+      rc = sync_after(ctx, rc);
     }
     RC(rc);
     if (round == 0) {
@@ -2977,9 +2934,7 @@ int launch_cov(rmhmc_ctx* ctx, const double* d_x, size_t N, int P, double* d_par
 
 int cov_partial(rmhmc_ctx* ctx, const double* d_x, size_t N, int P, double* d_partial) {
   CallMem mem(ctx);
-  const int rc = launch_cov(ctx, d_x, N, P, d_partial, mem);
-  const int rs = sync(ctx);
-  return rc != RMHMC_OK ? rc : rs;
+  return sync_after(ctx, launch_cov(ctx, d_x, N, P, d_partial, mem));
 }
 
 }  // namespace
@@ -3312,8 +3267,7 @@ int pred_partial(rmhmc_ctx* ctx, const double* d_w, size_t N, int D, const doubl
     HIPCK(hipGetLastError());
     return RMHMC_OK;
   }();
-  const int rs = sync(ctx);
-  return rc != RMHMC_OK ? rc : rs;
+  return sync_after(ctx, rc);
 }
 
 }  // namespace

@@ -37,6 +37,7 @@ CERT_PATHS = {
     "large_int8": (6000, 100, 4, I8(6) | _capi.FLAG_INT8_CERTIFY, 38),
 }
 ESS_S = 200
+REPLAY_T = 3            # iterations of the replay calls
 
 
 def assert_path(ctx, path, certify_active=True, paths=None):
@@ -89,6 +90,16 @@ def make_inputs(spec):
     inp["wm"] = 0.1 * rs.randn(n, D); inp["zm"] = rs.randn(n, D); inp["uam"] = rs.rand(n)
     inp["ess_x"] = np.cumsum(rs.randn(3, ESS_S, D), axis=1) * 0.05 + rs.randn(3, ESS_S, D)
     inp["eps_lf"] = 0.3 if D > 64 else 0.5
+    # the tapes of the three replays (a stream of their own: the inputs above are the ones they always were)
+    rr = np.random.RandomState(2000 + seed)
+    T = REPLAY_T
+    inp["amh_z"] = rr.randn(n, T, D); inp["amh_u"] = rr.rand(n, T, D)
+    inp["iwls_wp"] = 0.1 * rr.randn(n, T, D); inp["iwls_u"] = rr.rand(n, T)
+    # Gibbs: two attempts per row and iteration (the same ranges in every iteration), the second with the acceptance uniform 0, which
+    # every proposal passes (gibbs_sampler.py:21,41: a positive partial sum exceeds it): no chain's tape runs out, status stays 0
+    ks = np.stack([rr.randn(n, 2 * M), rr.rand(n, 2 * M), rr.rand(n, 2 * M)], axis=2); ks[:, 1::2, 2] = 0.0
+    off = np.ascontiguousarray(np.broadcast_to(2 * np.arange(M + 1, dtype=np.int64), (n, T, M + 1)))
+    inp["gibbs_tapes"] = (rr.rand(n, M), rr.rand(n, T, M), rr.randn(n, T, D), ks, off)
     return inp
 
 
@@ -172,17 +183,32 @@ def _gibbs_sample(ctx, i):
     return r
 
 
+def _amh_replay(ctx, i):
+    return ctx.amh_replay(REPLAY_T, 1, i["amh_z"], i["amh_u"])
+
+
+def _iwls_replay(ctx, i):
+    return ctx.iwls_replay(i["iwls_wp"], i["iwls_u"])
+
+
+def _gibbs_replay(ctx, i):
+    r = ctx.gibbs_replay(*i["gibbs_tapes"])
+    assert not r["status"].any(), r["status"]          # (no chain stopped: the records below are those of every iteration)
+    return r
+
+
 CALLS = [("log_posterior", _log_posterior), ("metric", _metric), ("metric_terms", _metric_terms), ("leapfrog", _leapfrog),
          ("transition", _transition), ("sample", _sample), ("sample_stats", _sample_stats), ("chains", _chains),
          ("hmc_transition", _hmc_transition), ("hmc_sample", _hmc_sample), ("mmala_transition", _mmala_transition),
          ("mmala_sample", _mmala_sample), ("ess", _ess), ("amh_sample", _amh_sample), ("iwls_sample", _iwls_sample),
-         ("gibbs_sample", _gibbs_sample)]
+         ("gibbs_sample", _gibbs_sample), ("amh_replay", _amh_replay), ("iwls_replay", _iwls_replay), ("gibbs_replay", _gibbs_replay)]
 
 
 def calls_for(ctx):
     """the calls of the battery this library and shape support"""
     # (IWLS and Gibbs: D <= 64, RMHMC_ERR_UNSUPPORTED above)
-    have = {"amh_sample": ctx.rl.has_amh, "iwls_sample": ctx.rl.has_iwls and ctx.D <= 64, "gibbs_sample": ctx.rl.has_gibbs and ctx.D <= 64}
+    amh, iwls, gibbs = ctx.rl.has_amh, ctx.rl.has_iwls and ctx.D <= 64, ctx.rl.has_gibbs and ctx.D <= 64
+    have = {"amh_sample": amh, "iwls_sample": iwls, "gibbs_sample": gibbs, "amh_replay": amh, "iwls_replay": iwls, "gibbs_replay": gibbs}
     return [(name, fn) for name, fn in CALLS if have.get(name, True)]
 
 
