@@ -256,6 +256,22 @@ QUANT_THREADS, QUANT_KEYS, QUANT_MAX_TILE = 256, 64, 64               # the kern
 QUANT_KEYS_OUT = ("quantiles", "quantile_draws")                      # what quantiles=probs adds to a sample_to result
 
 
+# include/rmhmc_loo.h: PSIS leave-one-out cross-validation and WAIC from draws on the device, HIP library only as well
+LOO_SIGNATURES = {
+    "rmhmc_loo_loglik_dev": (C.c_int, [C.c_void_p, _vp, C.c_int64, C.c_int64, C.c_int32, _dp, _dp, C.c_int32, _vp]),
+    "rmhmc_loo_moments_dev": (C.c_int, [C.c_void_p, _vp, C.c_int64, C.c_int64, C.c_int32, _vp]),
+    "rmhmc_loo_plan": (C.c_int, [_lp, C.c_int32, _lp, _lp]),
+    "rmhmc_loo_split_dev": (C.c_int, [C.c_void_p, _vp, C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _lp, C.c_int64, _vp, _vp, _vp]),
+    "rmhmc_loo_fit_dev": (C.c_int, [C.c_void_p, _vp, _vp, _dp, _dp, _lp, C.c_int64, C.c_int32, _vp]),
+    "rmhmc_loo_finish": (C.c_int, [_dpp, C.c_int32, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _lp, _lp]),
+    "rmhmc_loo_dev": (C.c_int, [C.c_void_p, _vp, C.c_int64, C.c_int64, C.c_int32, _dp, _dp, C.c_int64, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp,
+                                _dp, _dp, _dp, _dp, _lp, _lp]),
+}
+LOO_MAX_COLS, LOO_MAX_TAIL, LOO_MAX_D = 64, 16384, 256     # RMHMC_LOO_MAX_COLS, RMHMC_LOO_MAX_TAIL; widest draw
+LOO_POINTWISE = ("elpd_loo", "p_loo", "pareto_k", "lppd", "p_waic", "elpd_waic")           # the [C] outputs of loo_finish, in its order
+LOO_TOTALS = ("elpd_loo", "se_elpd_loo", "p_loo", "elpd_waic", "se_elpd_waic", "p_waic")   # its totals [6]
+
+
 def quant_tile(P):
     """(column tile, rows of a workgroup's row block) of the histogram kernel at P columns: quant_tile_width and quant_block_rows of
     csrc/quant.h"""
@@ -287,6 +303,7 @@ FEATURES = {
     "pred": (PRED_SIGNATURES, "the posterior predictive probabilities (include/rmhmc_pred.h)"),
     "smc": (SMC_SIGNATURES, "adaptive sequential Monte Carlo (include/rmhmc_smc.h)"),
     "quant": (QUANT_SIGNATURES, "the posterior quantiles (include/rmhmc_quant.h)"),
+    "loo": (LOO_SIGNATURES, "leave-one-out cross-validation (include/rmhmc_loo.h)"),
 }
 
 
@@ -939,6 +956,96 @@ class Context:
         res["partial"] = part
         return res
 
+    # ---- leave-one-out cross-validation (include/rmhmc_loo.h) -----------
+    @staticmethod
+    def _loo_rows(who, x, t, D):
+        x = _f64(x)
+        if x.ndim != 2 or x.shape[1] != D or x.shape[0] < 1:
+            raise ValueError("%s: x must be (C, D) with the D of the samples" % who)
+        t = _f64(t).reshape(-1)
+        if t.shape[0] != x.shape[0]:
+            raise ValueError("%s: t must have one entry per row of x" % who)
+        return x, t
+
+    def _loo_cut(self, who, cut, lmin, tail_len, C):
+        cut, lmin = _f64(cut).reshape(-1), _f64(lmin).reshape(-1)
+        tl = np.ascontiguousarray(tail_len, dtype=np.int64).reshape(-1)
+        if not cut.size == lmin.size == tl.size == C:
+            raise ValueError("%s: cut, lmin and tail_len must have one entry per column" % who)
+        return cut, lmin, tl
+
+    def loo_loglik(self, samples, x, t):
+        """The log-likelihood matrix ll [n][S][C] (include/rmhmc_loo.h) of the C <= 64 data rows x [C][D], t [C] (host, 0 or 1) under the
+        draws of a float64 torch tensor [n][S][D] already on the context's GPU, a tensor there.  torch's current stream is synchronised
+        first, as in ess_dev."""
+        import torch
+        self.rl.need("loo")
+        w = self._dev_tensor("loo_loglik", samples, " [n][S][D]", 3)
+        n, S, D = w.shape
+        x, t = self._loo_rows("loo_loglik", x, t, D)
+        ll = torch.empty((n, S, x.shape[0]), dtype=torch.float64, device=w.device)
+        self._ck(self.lib.rmhmc_loo_loglik_dev(self._h, w.data_ptr(), n, S, D, _ptr(x), _ptr(t), x.shape[0], ll.data_ptr()))
+        return ll
+
+    def loo_moments(self, ll):
+        """The mergeable moments partial [5, C] = (m, mean, M2, SQ, lmin) of ll [n][S][C] on the context's GPU, a tensor there"""
+        import torch
+        self.rl.need("loo")
+        ll = self._dev_tensor("loo_moments", ll, " [n][S][C]", 3)
+        n, S, Cc = ll.shape
+        part = torch.empty((5, Cc), dtype=torch.float64, device=ll.device)
+        self._ck(self.lib.rmhmc_loo_moments_dev(self._h, ll.data_ptr(), n, S, Cc, part.data_ptr()))
+        return part
+
+    def loo_split(self, ll, cut, lmin, tail_len, stride=None):
+        """The split of ll [n][S][C] at the cutoffs cut [C] (host; lmin [C], tail_len [C] of loo_plan): dict(tail [C][stride] (the first
+        n_lt slots of a row hold the values below the cutoff, in no order), counts int64 [2, C] = (n_lt, n_gt), body [2, C] = (A_body,
+        B_body)), tensors on the context's GPU.  stride: max(1, the longest tail) unless given."""
+        import torch
+        self.rl.need("loo")
+        ll = self._dev_tensor("loo_split", ll, " [n][S][C]", 3)
+        n, S, Cc = ll.shape
+        cut, lmin, tl = self._loo_cut("loo_split", cut, lmin, tail_len, Cc)
+        stride = max(1, int(tl.max())) if stride is None else int(stride)
+        tail = torch.empty((Cc, max(stride, 1)), dtype=torch.float64, device=ll.device)
+        counts = torch.empty((2, Cc), dtype=torch.int64, device=ll.device)
+        body = torch.empty((2, Cc), dtype=torch.float64, device=ll.device)
+        self._ck(self.lib.rmhmc_loo_split_dev(self._h, ll.data_ptr(), n, S, Cc, _ptr(cut), _ptr(lmin), _ptr(tl, _lp), stride, tail.data_ptr(),
+                                              counts.data_ptr(), body.data_ptr()))
+        return dict(tail=tail, counts=counts, body=body)
+
+    def loo_fit(self, tail, counts, cut, lmin, tail_len):
+        """The generalised Pareto fit of every column's tail (tail [C][stride], counts [2, C] of loo_split): fit [4, C] = (khat, sigma,
+        A_tail, B_tail), a tensor on the context's GPU"""
+        import torch
+        self.rl.need("loo")
+        tail = self._dev_tensor("loo_fit", tail, " [C][stride]", 2)
+        counts = self._dev_tensor("loo_fit", counts, " [2][C]", 2, torch.int64)
+        Cc, stride = tail.shape
+        if tuple(counts.shape) != (2, Cc):
+            raise ValueError("loo_fit: counts must be [2][C]")
+        cut, lmin, tl = self._loo_cut("loo_fit", cut, lmin, tail_len, Cc)
+        fit = torch.empty((4, Cc), dtype=torch.float64, device=tail.device)
+        self._ck(self.lib.rmhmc_loo_fit_dev(self._h, tail.data_ptr(), counts.data_ptr(), _ptr(cut), _ptr(lmin), _ptr(tl, _lp), stride, Cc,
+                                            fit.data_ptr()))
+        return fit
+
+    def loo(self, samples, x, t, cols_per_block=0):
+        """PSIS-LOO and WAIC of the rows x [R][D], t [R] (host) under the draws samples [n][S][D] on the context's GPU (rmhmc_loo_dev), in
+        blocks of cols_per_block columns (0: the library chooses).  Returns what loo_finish returns, with partial [5, R], fit [4, R] and
+        body [2, R] (host) in place of merged."""
+        self.rl.need("loo")
+        w = self._dev_tensor("loo", samples, " [n][S][D]", 3)
+        n, S, D = w.shape
+        x, t = self._loo_rows("loo", x, t, D)
+        R = x.shape[0]
+        part = np.empty((5, R)); fit = np.empty((4, R)); body = np.empty((2, R))
+        pw = [np.empty(R) for _ in LOO_POINTWISE]
+        totals = np.empty(6); kc = np.zeros(2, dtype=np.int64); used = np.zeros(R, dtype=np.int64)
+        self._ck(self.lib.rmhmc_loo_dev(self._h, w.data_ptr(), n, S, D, _ptr(x), _ptr(t), R, int(cols_per_block), _ptr(part), _ptr(fit), _ptr(body),
+                                        *[_ptr(a) for a in pw], _ptr(totals), _ptr(kc, _lp), _ptr(used, _lp)))
+        return _loo_result(pw, totals, kc, used, partial=part, fit=fit, body=body)
+
     # ---- adaptive Metropolis (code/metropolis.py, include/rmhmc_amh.h) -----------
     def amh_sample(self, n_iter, burn_in, seed=0, chain_offset=0, theta0=None):
         """returns (samples [n][n_iter-burn_in][D], accepted proposals [n], final ProposalSD [n][D], seconds after burn-in)"""
@@ -1545,6 +1652,48 @@ def pred_finish(partials, lib=None):
 def pred_identity(R):
     """the partial of no draws at all (an empty shard): the identity of the merge"""
     return np.zeros((4, int(R)))
+
+
+def loo_identity(C):
+    """the moments partial of no draws at all (an empty shard): the identity of the merge, lmin = +inf"""
+    p = np.zeros((5, int(C)))
+    p[4] = np.inf
+    return p
+
+
+def loo_plan(m, lib=None):
+    """rmhmc_loo_plan (include/rmhmc_loo.h): m [C] finite values per column (int64) -> (tail_len int64 [C], rank int64 [C]: the 0-based
+    rank of the cutoff, -1 where the tail is shorter than 5).  RmhmcError -4 for a tail longer than LOO_MAX_TAIL."""
+    lib = _lib_with(lib, "loo")
+    m = np.ascontiguousarray(m, dtype=np.int64).reshape(-1)
+    tl = np.zeros(m.size, dtype=np.int64); rank = np.zeros(m.size, dtype=np.int64)
+    lib.ck(lib.lib.rmhmc_loo_plan(_ptr(m, _lp), m.size, _ptr(tl, _lp), _ptr(rank, _lp)))
+    return tl, rank
+
+
+def _loo_result(pointwise, totals, k_counts, used, **more):
+    out = dict(zip(LOO_POINTWISE, pointwise))
+    out["totals"] = dict(zip(LOO_TOTALS, (float(v) for v in totals)))
+    out.update(k_mid=int(k_counts[0]), k_high=int(k_counts[1]), draws_used=used)
+    out.update(more)
+    return out
+
+
+def loo_finish(partials, fit=None, body=None, lib=None):
+    """rmhmc_loo_finish (include/rmhmc_loo.h): the moments partials ([5, C] each: torch tensors on any device or NumPy arrays) merged in
+    the order given and finished on the host with fit [4, C] and body [2, C] (both None: WAIC alone).  Returns dict(elpd_loo, p_loo,
+    pareto_k, lppd, p_waic, elpd_waic [C]; totals: a dict of LOO_TOTALS; k_mid, k_high: the khat in (0.5, 0.7] and above 0.7;
+    draws_used int64 [C]; merged [5, C])."""
+    shape, call = _finish_call("rmhmc_loo_finish", "loo", partials, lib, lambda p: p.ndim == 2 and p.shape[0] == 5,
+                               "loo_finish: partials of one shape [5, C] required")
+    Cc = shape[1]
+    host = [None if a is None else _f64(a if isinstance(a, np.ndarray) else a.detach().cpu().numpy()) for a in (fit, body)]
+    if (host[0] is None) != (host[1] is None) or (host[0] is not None and (host[0].shape != (4, Cc) or host[1].shape != (2, Cc))):
+        raise ValueError("loo_finish: fit [4, C] and body [2, C] together, or neither")
+    merged = np.empty((5, Cc)); pw = [np.empty(Cc) for _ in LOO_POINTWISE]
+    totals = np.empty(6); kc = np.zeros(2, dtype=np.int64); used = np.zeros(Cc, dtype=np.int64)
+    call(Cc, _ptr(host[0]), _ptr(host[1]), _ptr(merged), *[_ptr(a) for a in pw], _ptr(totals), _ptr(kc, _lp), _ptr(used, _lp))
+    return _loo_result(pw, totals, kc, used, merged=merged)
 
 
 _hip = None

@@ -17,6 +17,7 @@
 #include "../../include/rmhmc_pred.h"
 #include "../../include/rmhmc_smc.h"
 #include "../../include/rmhmc_quant.h"
+#include "../../include/rmhmc_loo.h"
 #include "plan.h"
 #include "mass.h"
 #include "kernels.hip.h"
@@ -35,6 +36,7 @@
 #include "pred.hip.h"
 #include "smc.hip.h"
 #include "quant.hip.h"
+#include "loo.hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -2783,15 +2785,18 @@ int launch_quant_tw(rmhmc_ctx* ctx, dim3 grid, const double* d_samples, long lon
 
 // samples [N][P] -> the histogram partial [Kh][P][256] of `round`, all in device memory; queued on the stream, its buffers taken from mem,
 // which the caller keeps until the stream is idle.  prefix: host [K][P], unused in round 0
+// (pre: buffers of the caller's for the counters [Kh][P][256], the prefixes and the representatives [K][P] in place of mem's)
+struct QuantScratch { unsigned long long* cnt; unsigned long long* prefix; signed char* rep; };
 int launch_quant_hist(rmhmc_ctx* ctx, const double* d_samples, long long N, int P, int round, const uint64_t* prefix, int K, double* d_hist,
-                      CallMem& mem) {
+                      CallMem& mem, const QuantScratch* pre = nullptr) {
   const int tw = quant_tile_width(P), Kh = round ? K : 1;
   const long long nblocks = (N + quant_block_rows(tw) - 1) / quant_block_rows(tw), ntiles = ((long long)P + tw - 1) / tw;
   if (nblocks > 0x7fffffffLL || ntiles > 65535) return fail(ctx, RMHMC_ERR_UNSUPPORTED, "quant: too many rows or columns for one launch");
   const size_t targets = (size_t)Kh * P, total = targets * QUANT_BINS;
   unsigned long long *d_cnt = nullptr, *d_prefix = nullptr;
   signed char* d_rep = nullptr;
-  RC(mem.alloc(&d_cnt, sizeof(unsigned long long) * total));
+  if (pre) d_cnt = pre->cnt;
+  else RC(mem.alloc(&d_cnt, sizeof(unsigned long long) * total));
   HIPCK(hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * total, ctx->stream));
   if (round) {
     // a target whose top 8 round bits repeat those of an earlier target of its column is not counted again (k_quant_out copies)
@@ -2802,8 +2807,11 @@ int launch_quant_hist(rmhmc_ctx* ctx, const double* d_samples, long long N, int 
         while (!quant_match(prefix[(size_t)first * P + d], prefix[(size_t)k * P + d], round)) ++first;
         rep[(size_t)k * P + d] = (signed char)first;
       }
-    RC(mem.alloc(&d_prefix, sizeof(uint64_t) * targets));
-    RC(mem.alloc(&d_rep, targets));
+    if (pre) { d_prefix = pre->prefix; d_rep = pre->rep; }
+    else {
+      RC(mem.alloc(&d_prefix, sizeof(uint64_t) * targets));
+      RC(mem.alloc(&d_rep, targets));
+    }
     HIPCK(hipMemcpyAsync(d_prefix, prefix, sizeof(uint64_t) * targets, hipMemcpyHostToDevice, ctx->stream));
     HIPCK(hipMemcpyAsync(d_rep, rep.data(), targets, hipMemcpyHostToDevice, ctx->stream));
     HIPCK(hipStreamSynchronize(ctx->stream));  // rep goes out of scope, and the caller's prefix is its own again
@@ -3289,6 +3297,273 @@ int rmhmc_pred_finish(const double* const* partials, int32_t k, int64_t R, doubl
                       double* lpd_total, int64_t* draws_used) {
   const int rc = pred_finish(partials, k, R, merged, prob, pvar, lpd, lpd_total, draws_used);
   return rc == RMHMC_OK ? rc : fail(nullptr, rc, rc == RMHMC_ERR_NOMEM ? "pred_finish: out of memory" : "pred_finish: need k >= 1, R >= 1 and no NULL partial");
+}
+
+}  // extern "C"
+
+// ---- leave-one-out cross-validation: PSIS-LOO and WAIC (include/rmhmc_loo.h, loo.h, loo.hip.h) ---------------------------------------------
+namespace {
+
+// The device buffers of one block of C <= 64 columns over N draws, carved out of one allocation (base nullptr: sizes only).
+// which: 1 the log-likelihood, 2 a reduction, 4 the split, 8 the fit, 16 the select, 32 ll itself
+struct LooBufs {
+  double *x = nullptr, *t = nullptr, *vcnt = nullptr, *rec = nullptr, *partial = nullptr, *cut = nullptr, *lmin = nullptr, *tail = nullptr,
+         *sorted = nullptr, *body = nullptr, *fit = nullptr, *hist = nullptr, *ll = nullptr;
+  long long *tail_len = nullptr, *counts = nullptr;
+  unsigned long long *fill = nullptr;
+  QuantScratch q{nullptr, nullptr, nullptr};
+  unsigned char* valid = nullptr;
+  size_t bytes = 0;
+  template <typename T>
+  void take(char* base, T*& p, size_t count) {
+    bytes = (bytes + 15) & ~(size_t)15;
+    p = base ? (T*)(base + bytes) : nullptr;
+    bytes += count * sizeof(T);
+  }
+  void carve(char* base, int which, size_t N, int D, int C, size_t stride, const loo_plan_t& pl) {
+    bytes = 0;
+    const size_t c = (size_t)C;
+    if (which & 32) take(base, ll, N * c);
+    if (which & 1) { take(base, x, c * (size_t)D); take(base, t, c); take(base, vcnt, (size_t)pl.vblocks); take(base, valid, N); }
+    if (which & 2) { take(base, rec, (size_t)pl.rblocks * LOO_REC * LOO_MAX_COLS); take(base, partial, 5 * c); }
+    if (which & (4 | 8)) { take(base, cut, c); take(base, lmin, c); take(base, tail_len, c); take(base, counts, 2 * c); }
+    if (which & 4) { take(base, fill, c); take(base, body, 2 * c); }
+    if (which & 32) take(base, tail, c * stride);  // (the single calls take the caller's)
+    if (which & 8) { take(base, sorted, c * stride); take(base, fit, 4 * c); }
+    if (which & 16) { take(base, hist, c * QUANT_BINS); take(base, q.cnt, c * QUANT_BINS); take(base, q.prefix, c); take(base, q.rep, c); }
+  }
+  int alloc(rmhmc_ctx*, CallMem& mem, int which, size_t N, int D, int C, size_t stride, const loo_plan_t& pl) {
+    carve(nullptr, which, N, D, C, stride, pl);
+    char* base = nullptr;
+    RC(mem.alloc(&base, bytes));
+    carve(base, which, N, D, C, stride, pl);
+    return RMHMC_OK;
+  }
+};
+
+// draws [N][D] (device), x [C][D] and t [C] (host, checked) -> ll [N][C] (device); queued
+int loo_loglik(rmhmc_ctx* ctx, const double* d_w, size_t N, int D, const double* x, const double* t, int C, const loo_plan_t& pl, LooBufs& b,
+               double* d_ll) {
+  RC(upload(ctx, b.x, x, (size_t)C * (size_t)D));
+  RC(upload(ctx, b.t, t, (size_t)C));
+  launch(ctx, "loo_loglik", [&](hipStream_t st) {
+    hipLaunchKernelGGL(k_pred_valid, dim3((unsigned)pl.vblocks), dim3(256), 0, st, d_w, N, D, (size_t)pl.draws_per_vblock, b.valid, b.vcnt);
+    switch (pl.ksteps) {
+#define LOO_CASE(KS_) case KS_: hipLaunchKernelGGL(k_loo_loglik<KS_>, dim3((unsigned)pl.lblocks), dim3(256), 0, st, d_w, N, D, b.valid, b.x, b.t, C, d_ll); break
+      LOO_CASE(4); LOO_CASE(8); LOO_CASE(16); LOO_CASE(24); LOO_CASE(32); LOO_CASE(40); LOO_CASE(48); LOO_CASE(56);
+      default: static_assert(LOO_MAX_D == 256, "the cases above end at 64 steps"); LOO_CASE(64);
+#undef LOO_CASE
+    }
+  });
+  HIPCK(hipGetLastError());
+  return RMHMC_OK;
+}
+
+// ll [N][C] -> the moments partial [5][C], both device; queued
+int loo_moments(rmhmc_ctx* ctx, const double* d_ll, size_t N, int C, const loo_plan_t& pl, LooBufs& b, double* d_partial) {
+  launch(ctx, "loo_moments", [&](hipStream_t st) {
+    const dim3 grid((unsigned)pl.rblocks);
+    const loo_split_args none{};
+    hipLaunchKernelGGL(k_loo_reduce<0>, grid, dim3(256), 0, st, d_ll, N, C, (size_t)pl.rows_per_block, (const double*)nullptr, none, b.rec);
+    hipLaunchKernelGGL(k_loo_fin<0>, dim3(1), dim3(64), 0, st, b.rec, (size_t)pl.rblocks, C, d_partial, none, (long long*)nullptr, (double*)nullptr);
+    hipLaunchKernelGGL(k_loo_reduce<1>, grid, dim3(256), 0, st, d_ll, N, C, (size_t)pl.rows_per_block, (const double*)(d_partial + C), none, b.rec);
+    hipLaunchKernelGGL(k_loo_fin<1>, dim3(1), dim3(64), 0, st, b.rec, (size_t)pl.rblocks, C, d_partial, none, (long long*)nullptr, (double*)nullptr);
+  });
+  HIPCK(hipGetLastError());
+  return RMHMC_OK;
+}
+
+// cut, lmin, tail_len [C] (host) to the device; the caller keeps them until the stream is idle
+int loo_upload_cut(rmhmc_ctx* ctx, const double* cut, const double* lmin, const int64_t* tail_len, int C, LooBufs& b) {
+  RC(upload(ctx, b.cut, cut, (size_t)C));
+  RC(upload(ctx, b.lmin, lmin, (size_t)C));
+  RC(upload(ctx, (int64_t*)b.tail_len, tail_len, (size_t)C));
+  return RMHMC_OK;
+}
+
+// ll [N][C] and the uploaded cut -> tail [C][stride], counts [2][C], body [2][C], all device; queued
+int loo_split(rmhmc_ctx* ctx, const double* d_ll, size_t N, int C, size_t stride, const loo_plan_t& pl, LooBufs& b, double* d_tail,
+              long long* d_counts, double* d_body) {
+  HIPCK(hipMemsetAsync(b.fill, 0, sizeof(unsigned long long) * (size_t)C, ctx->stream));
+  launch(ctx, "loo_split", [&](hipStream_t st) {
+    const loo_split_args sp{b.cut, b.lmin, b.tail_len, d_tail, (long long)stride, b.fill};
+    hipLaunchKernelGGL(k_loo_reduce<2>, dim3((unsigned)pl.rblocks), dim3(256), 0, st, d_ll, N, C, (size_t)pl.rows_per_block, (const double*)nullptr,
+                       sp, b.rec);
+    hipLaunchKernelGGL(k_loo_fin<2>, dim3(1), dim3(64), 0, st, b.rec, (size_t)pl.rblocks, C, (double*)nullptr, sp, d_counts, d_body);
+  });
+  HIPCK(hipGetLastError());
+  return RMHMC_OK;
+}
+
+// tail [C][stride], counts [2][C] and the uploaded cut -> fit [4][C], all device; queued
+int loo_fit(rmhmc_ctx* ctx, const double* d_tail, const long long* d_counts, size_t stride, int C, LooBufs& b, double* d_fit) {
+  RC(raise_lds(ctx, k_loo_fit, MAX_LDS));  // per device: set where it is used
+  launch(ctx, "loo_fit", [&](hipStream_t st) {
+    hipLaunchKernelGGL(k_loo_fit, dim3((unsigned)C), dim3(LOO_FIT_THREADS), LOO_FIT_LDS_BYTES, st, d_tail, d_counts, b.cut, b.lmin, b.tail_len,
+                       (long long)stride, C, b.sorted, d_fit);
+  });
+  HIPCK(hipGetLastError());
+  return RMHMC_OK;
+}
+
+const char* loo_ll_refusal(const rmhmc_ctx* ctx, const void* ll, int64_t n, int64_t S, int32_t C) {
+  if (!ctx || !ll || n < 1 || S < 1 || C < 1 || C > LOO_MAX_COLS || n > INT64_MAX / S || n * S > INT64_MAX / 8 / LOO_MAX_COLS)
+    return "need a context, ll, n >= 1, S >= 1 and 1 <= C <= 64";
+  return nullptr;
+}
+
+// one block of columns of rmhmc_loo_dev: x [C][D], t [C] -> the block's partial [5][C], fit [4][C], body [2][C] on the host
+int loo_block(rmhmc_ctx* ctx, const double* d_w, size_t N, int D, const double* x, const double* t, int C, size_t stride, const loo_plan_t& pl,
+              LooBufs& b, CallMem& mem, double* partial, double* fit, double* body) {
+  const size_t c = (size_t)C;
+  RC(sync_after(ctx, [&]() -> int {
+    RC(loo_loglik(ctx, d_w, N, D, x, t, C, pl, b, b.ll));
+    RC(loo_moments(ctx, b.ll, N, C, pl, b, b.partial));
+    return download(ctx, partial, b.partial, 5 * c);
+  }()));
+  std::vector<int64_t> m(c), tl(c), rank(c);
+  for (size_t i = 0; i < c; ++i) m[i] = (int64_t)partial[i];
+  const int rp = loo_plan(m.data(), C, tl.data(), rank.data());
+  if (rp != RMHMC_OK) return fail(ctx, rp, "loo_dev: a column's tail is longer than 16384 draws (more than 29 826 161 finite draws)");
+  std::vector<uint64_t> prefix(c, 0);
+  std::vector<double> hist(c * QUANT_BINS), cut(c, NAN);
+  bool any = false;
+  for (size_t i = 0; i < c; ++i) any = any || rank[i] >= 0;
+  for (int round = 0; any && round < 8; ++round) {
+    RC(sync_after(ctx, [&]() -> int {
+      RC(launch_quant_hist(ctx, b.ll, (long long)N, C, round, prefix.data(), 1, b.hist, mem, &b.q));
+      return download(ctx, hist.data(), b.hist, hist.size());
+    }()));
+    const double* one = hist.data();
+    const int rs = quant_step(&one, 1, C, 1, round, prefix.data(), rank.data());
+    if (rs != RMHMC_OK) return fail(ctx, rs, "loo_dev: a round's histogram does not continue the previous round");
+  }
+  for (size_t i = 0; i < c; ++i)
+    if (tl[i] >= 5) cut[i] = quant_unkey(prefix[i]);
+  return sync_after(ctx, [&]() -> int {
+    RC(loo_upload_cut(ctx, cut.data(), partial + 4 * c, tl.data(), C, b));
+    RC(loo_split(ctx, b.ll, N, C, stride, pl, b, b.tail, b.counts, b.body));
+    RC(loo_fit(ctx, b.tail, b.counts, stride, C, b, b.fit));
+    RC(download(ctx, body, b.body, 2 * c));
+    return download(ctx, fit, b.fit, 4 * c);
+  }());
+}
+
+}  // namespace
+
+extern "C" {
+
+int rmhmc_loo_loglik_dev(rmhmc_ctx* ctx, const double* samples_dev, int64_t n, int64_t S, int32_t D, const double* x, const double* t, int32_t C,
+                         double* ll_dev) {
+  if (!samples_dev || !x || !t || D < 1) return fail(ctx, RMHMC_ERR_INVALID, "loo_loglik_dev: need samples, x, t and D >= 1");
+  if (const char* why = loo_ll_refusal(ctx, ll_dev, n, S, C)) return fail(ctx, RMHMC_ERR_INVALID, std::string("loo_loglik_dev: ") + why);
+  if (D > LOO_MAX_D) return fail(ctx, RMHMC_ERR_UNSUPPORTED, "loo_loglik_dev: D <= 256");
+  if (const char* why = loo_check_rows(x, t, C, D)) return fail(ctx, RMHMC_ERR_INVALID, std::string("loo_loglik_dev: ") + why);
+  const size_t N = (size_t)n * (size_t)S;
+  const loo_plan_t pl = loo_kernel_plan((int64_t)N, D);
+  if (pl.lblocks > 0x7fffffffLL) return fail(ctx, RMHMC_ERR_UNSUPPORTED, "loo_loglik_dev: too many draws for one launch");
+  HIPCK(hipSetDevice(ctx->device));
+  CallMem mem(ctx);
+  LooBufs b;
+  RC(b.alloc(ctx, mem, 1, N, D, C, 1, pl));
+  return sync_after(ctx, loo_loglik(ctx, samples_dev, N, D, x, t, C, pl, b, ll_dev));
+}
+
+int rmhmc_loo_moments_dev(rmhmc_ctx* ctx, const double* ll_dev, int64_t n, int64_t S, int32_t C, double* partial_dev) {
+  if (const char* why = loo_ll_refusal(ctx, ll_dev, n, S, C)) return fail(ctx, RMHMC_ERR_INVALID, std::string("loo_moments_dev: ") + why);
+  if (!partial_dev) return fail(ctx, RMHMC_ERR_INVALID, "loo_moments_dev: need a partial");
+  const size_t N = (size_t)n * (size_t)S;
+  const loo_plan_t pl = loo_kernel_plan((int64_t)N, 1);
+  HIPCK(hipSetDevice(ctx->device));
+  CallMem mem(ctx);
+  LooBufs b;
+  RC(b.alloc(ctx, mem, 2, N, 1, C, 1, pl));
+  return sync_after(ctx, loo_moments(ctx, ll_dev, N, C, pl, b, partial_dev));
+}
+
+int rmhmc_loo_plan(const int64_t* m, int32_t C, int64_t* tail_len, int64_t* rank) {
+  const int rc = loo_plan(m, C, tail_len, rank);
+  return rc == RMHMC_OK ? rc : fail(nullptr, rc, rc == RMHMC_ERR_UNSUPPORTED ? "loo_plan: a tail longer than 16384 draws (m above 29 826 161)"
+                                                                              : "loo_plan: need m >= 0, C >= 1 and no NULL pointer");
+}
+
+int rmhmc_loo_split_dev(rmhmc_ctx* ctx, const double* ll_dev, int64_t n, int64_t S, int32_t C, const double* cut, const double* lmin,
+                        const int64_t* tail_len, int64_t stride, double* tail_dev, int64_t* counts_dev, double* body_dev) {
+  if (const char* why = loo_ll_refusal(ctx, ll_dev, n, S, C)) return fail(ctx, RMHMC_ERR_INVALID, std::string("loo_split_dev: ") + why);
+  if (!cut || !lmin || !tail_len || !tail_dev || !counts_dev || !body_dev) return fail(ctx, RMHMC_ERR_INVALID, "loo_split_dev: a NULL pointer");
+  if (const char* why = loo_check_tails(tail_len, C, stride)) return fail(ctx, RMHMC_ERR_INVALID, std::string("loo_split_dev: ") + why);
+  const size_t N = (size_t)n * (size_t)S;
+  const loo_plan_t pl = loo_kernel_plan((int64_t)N, 1);
+  HIPCK(hipSetDevice(ctx->device));
+  CallMem mem(ctx);
+  LooBufs b;
+  RC(b.alloc(ctx, mem, 2 | 4, N, 1, C, 0, pl));
+  return sync_after(ctx, [&]() -> int {
+    RC(loo_upload_cut(ctx, cut, lmin, tail_len, C, b));
+    return loo_split(ctx, ll_dev, N, C, (size_t)stride, pl, b, tail_dev, (long long*)counts_dev, body_dev);
+  }());
+}
+
+int rmhmc_loo_fit_dev(rmhmc_ctx* ctx, const double* tail_dev, const int64_t* counts_dev, const double* cut, const double* lmin,
+                      const int64_t* tail_len, int64_t stride, int32_t C, double* fit_dev) {
+  if (!ctx || !tail_dev || !counts_dev || !cut || !lmin || !tail_len || !fit_dev || C < 1 || C > LOO_MAX_COLS)
+    return fail(ctx, RMHMC_ERR_INVALID, "loo_fit_dev: need a context, 1 <= C <= 64 and no NULL pointer");
+  if (const char* why = loo_check_tails(tail_len, C, stride)) return fail(ctx, RMHMC_ERR_INVALID, std::string("loo_fit_dev: ") + why);
+  const loo_plan_t pl = loo_kernel_plan(1, 1);
+  HIPCK(hipSetDevice(ctx->device));
+  CallMem mem(ctx);
+  LooBufs b;
+  RC(b.alloc(ctx, mem, 8, 1, 1, C, (size_t)stride, pl));
+  return sync_after(ctx, [&]() -> int {
+    RC(loo_upload_cut(ctx, cut, lmin, tail_len, C, b));
+    return loo_fit(ctx, tail_dev, (const long long*)counts_dev, (size_t)stride, C, b, fit_dev);
+  }());
+}
+
+int rmhmc_loo_finish(const double* const* partials, int32_t k, int64_t C, const double* fit, const double* body, double* merged, double* elpd_loo,
+                     double* p_loo, double* pareto_k, double* lppd, double* p_waic, double* elpd_waic, double* totals, int64_t* k_counts,
+                     int64_t* draws_used) {
+  const int rc = loo_finish(partials, k, C, fit, body, merged, elpd_loo, p_loo, pareto_k, lppd, p_waic, elpd_waic, totals, k_counts, draws_used);
+  return rc == RMHMC_OK ? rc : fail(nullptr, rc, rc == RMHMC_ERR_NOMEM ? "loo_finish: out of memory"
+                                                                       : "loo_finish: need k >= 1, C >= 1, no NULL partial, and fit and body together");
+}
+
+int rmhmc_loo_dev(rmhmc_ctx* ctx, const double* samples_dev, int64_t n, int64_t S, int32_t D, const double* x, const double* t, int64_t R,
+                  int32_t cols_per_block, double* partial, double* fit, double* body, double* elpd_loo, double* p_loo, double* pareto_k, double* lppd,
+                  double* p_waic, double* elpd_waic, double* totals, int64_t* k_counts, int64_t* draws_used) {
+  if (!ctx || !samples_dev || !x || !t || n < 1 || S < 1 || D < 1 || R < 1 || n > INT64_MAX / S || n * S > INT64_MAX / 8 / LOO_MAX_COLS ||
+      R > INT64_MAX / 8 / (D > LOO_MAX_D ? D : LOO_MAX_D) || cols_per_block < 0 || cols_per_block > LOO_MAX_COLS)
+    return fail(ctx, RMHMC_ERR_INVALID, "loo_dev: need samples, x, t, n >= 1, S >= 1, D >= 1, R >= 1 and 0 <= cols_per_block <= 64");
+  if (D > LOO_MAX_D) return fail(ctx, RMHMC_ERR_UNSUPPORTED, "loo_dev: D <= 256");
+  if (const char* why = loo_check_rows(x, t, R, D)) return fail(ctx, RMHMC_ERR_INVALID, std::string("loo_dev: ") + why);
+  const size_t N = (size_t)n * (size_t)S, r = (size_t)R;
+  const loo_plan_t pl = loo_kernel_plan((int64_t)N, D);
+  if (pl.lblocks > 0x7fffffffLL) return fail(ctx, RMHMC_ERR_UNSUPPORTED, "loo_dev: too many draws for one launch");
+  int cb = cols_per_block ? cols_per_block : loo_cols_per_block((int64_t)N);
+  if ((size_t)cb > r) cb = (int)r;
+  int64_t bound = loo_tail_len((int64_t)N);  // no column's tail is longer: the tail length grows with m <= N
+  const size_t stride = (size_t)(bound < 1 ? 1 : bound > LOO_MAX_TAIL ? LOO_MAX_TAIL : bound);
+  HIPCK(hipSetDevice(ctx->device));
+  CallMem mem(ctx);
+  LooBufs b;
+  RC(b.alloc(ctx, mem, 63, N, D, cb, stride, pl));
+  std::vector<double> P(5 * r), F(4 * r), B(2 * r), p((size_t)5 * cb), f((size_t)4 * cb), bd((size_t)2 * cb);
+  for (size_t c0 = 0; c0 < r; c0 += (size_t)cb) {
+    const int C = (int)std::min<size_t>((size_t)cb, r - c0);
+    RC(loo_block(ctx, samples_dev, N, D, x + c0 * (size_t)D, t + c0, C, stride, pl, b, mem, p.data(), f.data(), bd.data()));
+    for (int q = 0; q < 5; ++q)
+      for (int c = 0; c < C; ++c) {
+        P[(size_t)q * r + c0 + c] = p[(size_t)q * C + c];
+        if (q < 4) F[(size_t)q * r + c0 + c] = f[(size_t)q * C + c];
+        if (q < 2) B[(size_t)q * r + c0 + c] = bd[(size_t)q * C + c];
+      }
+  }
+  const double* one = P.data();
+  RC(rmhmc_loo_finish(&one, 1, R, F.data(), B.data(), nullptr, elpd_loo, p_loo, pareto_k, lppd, p_waic, elpd_waic, totals, k_counts, draws_used));
+  if (partial) std::copy(P.begin(), P.end(), partial);
+  if (fit) std::copy(F.begin(), F.end(), fit);
+  if (body) std::copy(B.begin(), B.end(), body);
+  return RMHMC_OK;
 }
 
 }  // extern "C"
