@@ -3,10 +3,10 @@
 //
 // Two passes, four kernels, no atomics; every sum has a fixed order that depends on (N, P) alone, so a call repeats bit for bit.
 //   k_cov_sums    grid: row blocks of cov_plan_sums x 256 threads.  A wavefront takes the rows wv, wv + 4, ... of its block, lane l the
-//                 columns l, l + 64, ...: a row with a non-finite entry (ballot) is flagged in valid[] and skipped, the others are
-//                 added to the lane's column sums, kept as an unevaluated pair (sum, error) by Knuth's two-sum.  The four wavefronts
-//                 meet in LDS in the order 0..3.  Output: blk [nblocks][3][P], rows (sum, error, rows used in entry 0).
-//   k_cov_mean    one workgroup: the blocks added in block order (two-sum again); rows 0 and 1 of the partial, and the centre as a pair
+//                 columns l, l + 64, ...: a row with a non-finite entry (wave_row_finite) is flagged in valid[] and skipped, the
+//                 others are added to the lane's column sums, each a sum_pair of sums.hip.h.  The four wavefronts meet in LDS in the
+//                 order 0..3.  Output: blk [nblocks][3][P], rows (sum, error, rows used in entry 0).
+//   k_cov_mean    one workgroup: the blocks added in block order (pairs again); rows 0 and 1 of the partial, and the centre as a pair
 //                 (hi = row 1, lo) with hi + lo the mean to about twice the precision of a double.
 //   k_cov_xtx     grid: (pairs I <= J of 16-column tiles, row blocks of cov_plan) x one wavefront.  Xc' Xc of the block's rows on
 //                 v_mfma_f64_16x16x4_f64, four sample rows per instruction: lane l holds A[i = l & 15][k = l >> 4] = xc[r0 + k][16 I + i]
@@ -23,61 +23,39 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "adapt.h"  // COV_MAX_P, the row blocks
+#include "adapt.h"     // COV_MAX_P, the row blocks
+#include "sums.hip.h"  // sum_pair, sum_finite, block_rows, wave_row_finite, d4
 
-typedef double cov_d4 __attribute__((ext_vector_type(4)));
-
-// (s, e) <- (s, e) + x with the rounding error of the sum kept in e (Knuth)
-__device__ __forceinline__ void cov_two_sum(double& s, double& e, double x) {
-  const double t = s + x;
-  const double bp = t - s;
-  e += (s - (t - bp)) + (x - bp);
-  s = t;
-}
+static_assert(COV_MAX_P == 256, "wave_row_finite checks 256 columns");
 
 __global__ __launch_bounds__(256) void k_cov_sums(const double* __restrict__ x, size_t N, int P, size_t rows_per_block,
                                                   unsigned char* __restrict__ valid, double* __restrict__ blk) {
-  __shared__ double red_s[4][COV_MAX_P], red_e[4][COV_MAX_P];
+  __shared__ sum_pair red[4][COV_MAX_P];
   __shared__ double red_m[4];
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-  const size_t r_begin = (size_t)blockIdx.x * rows_per_block;
-  const size_t r_end = r_begin + rows_per_block < N ? r_begin + rows_per_block : N;
-  double s[4] = {0.0, 0.0, 0.0, 0.0}, e[4] = {0.0, 0.0, 0.0, 0.0};
+  const block_range rows = block_rows(blockIdx.x, rows_per_block, N);
+  sum_pair sum[4] = {};
   double used = 0.0;
-  for (size_t r = r_begin + wv; r < r_end; r += 4) {
-    const double* __restrict__ row = x + r * (size_t)P;
+  for (size_t r = rows.begin + wv; r < rows.end; r += 4) {
     double v[4];
-    int bad = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int c = lane + 64 * q;
-      v[q] = c < P ? row[c] : 0.0;
-      bad |= !(fabs(v[q]) <= 1.7976931348623157e308);
-    }
-    const bool ok = __ballot(bad) == 0ULL;
+    const bool ok = wave_row_finite(x + r * (size_t)P, P, lane, v);
     if (lane == 0) valid[r] = ok ? 1 : 0;
     if (ok) {
       used += 1.0;
 #pragma unroll
-      for (int q = 0; q < 4; ++q) cov_two_sum(s[q], e[q], v[q]);
+      for (int q = 0; q < 4; ++q) sum[q].add(v[q]);
     }
   }
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    red_s[wv][lane + 64 * q] = s[q];
-    red_e[wv][lane + 64 * q] = e[q];
-  }
+  for (int q = 0; q < 4; ++q) red[wv][lane + 64 * q] = sum[q];
   if (lane == 0) red_m[wv] = used;
   __syncthreads();
   if (tid < P) {
-    double ts = red_s[0][tid], te = red_e[0][tid];
-    for (int w = 1; w < 4; ++w) {
-      cov_two_sum(ts, te, red_s[w][tid]);
-      te += red_e[w][tid];
-    }
+    sum_pair t = red[0][tid];
+    for (int w = 1; w < 4; ++w) t.add(red[w][tid]);
     double* out = blk + (size_t)blockIdx.x * 3 * (size_t)P;
-    out[tid] = ts;
-    out[P + tid] = te;
+    out[tid] = t.s;
+    out[P + tid] = t.e;
     if (tid == 0) out[2 * (size_t)P] = ((red_m[0] + red_m[1]) + red_m[2]) + red_m[3];
   }
 }
@@ -88,19 +66,19 @@ __global__ __launch_bounds__(256) void k_cov_mean(const double* __restrict__ blk
   const int c = threadIdx.x;
   if (c >= P) return;
   const size_t p = (size_t)P;
-  double s = 0.0, e = 0.0, m = 0.0;
+  sum_pair t = {};
+  double m = 0.0;
   for (size_t b = 0; b < nblocks; ++b) {
     const double* in = blk + b * 3 * p;
-    cov_two_sum(s, e, in[c]);
-    e += in[p + c];
+    t.add(sum_pair{in[c], in[p + c]});
     m += in[2 * p];
   }
   double hi = 0.0, lo = 0.0;
   if (m > 0.0) {
-    const double sh = s + e, sl = e - (sh - s);  // (|e| <= |s| ulp-wise: fast two-sum)
+    const double sh = t.value(), sl = t.e - (sh - t.s);  // (|e| <= |s| ulp-wise: fast two-sum)
     hi = sh / m;
     lo = (fma(-hi, m, sh) + sl) / m;
-    if (!(fabs(hi) <= 1.7976931348623157e308) || !(fabs(lo) <= 1.7976931348623157e308)) lo = 0.0;  // (the sum has overflowed: hi says so)
+    if (!sum_finite(hi) || !sum_finite(lo)) lo = 0.0;  // (the sum has overflowed: hi says so)
   }
   partial[c] = m;
   partial[p + c] = hi;
@@ -121,9 +99,9 @@ __global__ __launch_bounds__(64) void k_cov_xtx(const double* __restrict__ x, si
   const size_t p = (size_t)P;
   const double hia = in_a ? ctr[ca] : 0.0, loa = in_a ? ctr[p + ca] : 0.0;
   const double hib = in_b ? ctr[cb] : 0.0, lob = in_b ? ctr[p + cb] : 0.0;
-  const size_t r_begin = (size_t)blockIdx.y * rows_per_block;  // (a multiple of 4)
-  const size_t r_end = r_begin + rows_per_block < N ? r_begin + rows_per_block : N;
-  cov_d4 acc = (cov_d4){0.0, 0.0, 0.0, 0.0};
+  const block_range rows = block_rows(blockIdx.y, rows_per_block, N);  // (begin a multiple of 4)
+  const size_t r_begin = rows.begin, r_end = rows.end;
+  d4 acc = (d4){0.0, 0.0, 0.0, 0.0};
   const long long nsteps = r_end > r_begin ? (long long)((r_end - r_begin + 3) / 4) : 0;
   // (branch-free, so that the loads of several steps are in flight: a lane without an operand reads row r_end - 1 or column 0 of
   // the block, which exist, and selects zero)

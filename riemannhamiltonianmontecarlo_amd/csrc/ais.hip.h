@@ -21,15 +21,15 @@
 //   k_ais_max   grid: blocks of ais_plan x 256 threads.  NaN entries are counted and left out; the block's maximum of the others, the
 //               counts of used and NaN entries -> blk [nblocks][3]
 //   k_ais_sums  the same grid.  Every block first takes the global maximum a from blk (the same value in each); thread t adds
-//               exp(lw - a) and exp(2 (lw - a)) of its entries t, t + 256, ... into (sum, error) pairs by Knuth's two-sum; thread 0
+//               exp(lw - a) and exp(2 (lw - a)) of its entries t, t + 256, ... into the sum_pairs of sums.hip.h; thread 0
 //               adds the 256 pairs in thread order -> sums [nblocks][4]
 //   k_ais_fin   one thread: the blocks in block order -> partial [5]
 // a = -inf (every used entry -inf, or none used) makes every term 0 without reading anything else; no index depends on the data.
 #pragma once
 #include "../../include/rmhmc_ais.h"  // RMHMC_AIS_PRIOR_ITER
 #include "phmc.hip.h"
-#include "adapt.hip.h"  // cov_two_sum
-#include "ais.h"        // ais_plan
+#include "sums.hip.h"  // sum_pair, block_rows, SUM_NEG_INF
+#include "ais.h"       // ais_plan
 
 #pragma clang fp contract(off)
 
@@ -154,15 +154,12 @@ __global__ __launch_bounds__(64) void k_ais_prior(int D, unsigned long long seed
   for (int d = lane; d < D; d += 64) out[(size_t)c * ld + d] = sqrt_alpha * zs[d];
 }
 
-#define AIS_NEG_INF (-__builtin_huge_val())
-
 __global__ __launch_bounds__(256) void k_ais_max(const double* __restrict__ lw, size_t n, size_t per_block, double* __restrict__ blk) {
   __shared__ double r_a[256], r_m[256], r_n[256];
   const int tid = threadIdx.x;
-  const size_t begin = (size_t)blockIdx.x * per_block;
-  const size_t end = begin + per_block < n ? begin + per_block : n;
-  double a = AIS_NEG_INF, m = 0.0, nn = 0.0;
-  for (size_t i = begin + tid; i < end; i += 256) {
+  const block_range rg = block_rows(blockIdx.x, per_block, n);
+  double a = SUM_NEG_INF, m = 0.0, nn = 0.0;
+  for (size_t i = rg.begin + tid; i < rg.end; i += 256) {
     const double x = lw[i];
     if (x != x) { nn += 1.0; continue; }
     m += 1.0;
@@ -184,56 +181,53 @@ __global__ __launch_bounds__(256) void k_ais_max(const double* __restrict__ lw, 
 
 __global__ __launch_bounds__(256) void k_ais_sums(const double* __restrict__ lw, size_t n, size_t per_block, const double* __restrict__ blk,
                                                   int nblocks, double* __restrict__ sums) {
-  __shared__ double r[4][256];
+  __shared__ sum_pair r[2][256];  // (r[0][].s first carries the threads' maxima)
   const int tid = threadIdx.x;
-  double a = AIS_NEG_INF;
+  double a = SUM_NEG_INF;
   for (int b = tid; b < nblocks; b += 256) a = blk[3 * (size_t)b] > a ? blk[3 * (size_t)b] : a;
-  r[0][tid] = a;
+  r[0][tid].s = a;
   __syncthreads();
-  for (int t = 0; t < 256; ++t) a = r[0][t] > a ? r[0][t] : a;  // (a maximum: any order gives the same value)
+  for (int t = 0; t < 256; ++t) a = r[0][t].s > a ? r[0][t].s : a;  // (a maximum: any order gives the same value)
   __syncthreads();
-  const size_t begin = (size_t)blockIdx.x * per_block;
-  const size_t end = begin + per_block < n ? begin + per_block : n;
-  double s1 = 0.0, e1 = 0.0, s2 = 0.0, e2 = 0.0;
-  if (a > AIS_NEG_INF) {
-    for (size_t i = begin + tid; i < end; i += 256) {
+  const block_range rg = block_rows(blockIdx.x, per_block, n);
+  sum_pair s1 = {}, s2 = {};
+  if (a > SUM_NEG_INF) {
+    for (size_t i = rg.begin + tid; i < rg.end; i += 256) {
       const double x = lw[i];
       if (x != x) continue;
       const double dx = x - a;
-      cov_two_sum(s1, e1, exp(dx));
-      cov_two_sum(s2, e2, exp(2.0 * dx));
+      s1.add(exp(dx));
+      s2.add(exp(2.0 * dx));
     }
   }
-  r[0][tid] = s1; r[1][tid] = e1; r[2][tid] = s2; r[3][tid] = e2;
+  r[0][tid] = s1; r[1][tid] = s2;
   __syncthreads();
   if (tid == 0) {
     for (int t = 1; t < 256; ++t) {
-      cov_two_sum(s1, e1, r[0][t]);
-      e1 += r[1][t];
-      cov_two_sum(s2, e2, r[2][t]);
-      e2 += r[3][t];
+      s1.add(r[0][t]);
+      s2.add(r[1][t]);
     }
     double* out = sums + 4 * (size_t)blockIdx.x;
-    out[0] = s1; out[1] = e1; out[2] = s2; out[3] = e2;
+    out[0] = s1.s; out[1] = s1.e; out[2] = s2.s; out[3] = s2.e;
   }
 }
 
 __global__ __launch_bounds__(64) void k_ais_fin(const double* __restrict__ blk, const double* __restrict__ sums, int nblocks,
                                                 double* __restrict__ partial) {
   if (threadIdx.x != 0) return;
-  double a = AIS_NEG_INF, m = 0.0, nn = 0.0, s1 = 0.0, e1 = 0.0, s2 = 0.0, e2 = 0.0;
+  double a = SUM_NEG_INF, m = 0.0, nn = 0.0;
+  sum_pair s1 = {}, s2 = {};
   for (int b = 0; b < nblocks; ++b) {
+    const double* in = sums + 4 * (size_t)b;
     a = blk[3 * (size_t)b] > a ? blk[3 * (size_t)b] : a;
     m += blk[3 * (size_t)b + 1];
     nn += blk[3 * (size_t)b + 2];
-    cov_two_sum(s1, e1, sums[4 * (size_t)b]);
-    e1 += sums[4 * (size_t)b + 1];
-    cov_two_sum(s2, e2, sums[4 * (size_t)b + 2]);
-    e2 += sums[4 * (size_t)b + 3];
+    s1.add(sum_pair{in[0], in[1]});
+    s2.add(sum_pair{in[2], in[3]});
   }
   partial[0] = m;
   partial[1] = nn;
   partial[2] = a;
-  partial[3] = s1 + e1;
-  partial[4] = s2 + e2;
+  partial[3] = s1.value();
+  partial[4] = s2.value();
 }

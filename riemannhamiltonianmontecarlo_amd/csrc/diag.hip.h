@@ -2,7 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "diag.h"  // DIAG_CHAINS, DIAG_THREADS, DIAG_R, the LDS image
+#include "diag.h"      // DIAG_CHAINS, DIAG_THREADS, DIAG_R, the LDS image
+#include "sums.hip.h"  // sum_finite
 
 // Every chain gives two series per dimension: its first H = S / 2 rows and its last H rows.  k_diag_acov sums, over the series of a
 // block of DIAG_CHAINS chains, the raw lag products sum_s x_s x_{s+t} of the centred series for t < T, and counts the series it used.
@@ -62,7 +63,7 @@ __global__ __launch_bounds__(DIAG_THREADS, 2) void k_diag_acov(const double* __r
           const double v = x[(size_t)r * P];
           tile[(r + (r >> 4)) * TW + dl] = v;
           s += v;
-          nonfinite |= !(fabs(v) <= 1.7976931348623157e308);
+          nonfinite |= !sum_finite(v);
         }
       }
       red[tid] = s;
@@ -75,7 +76,7 @@ __global__ __launch_bounds__(DIAG_THREADS, 2) void k_diag_acov(const double* __r
         anybad |= bad[k * TW + dl];
       }
       const double mu = tot / (double)H;
-      const bool used = dvalid && !anybad && fabs(mu) <= 1.7976931348623157e308;
+      const bool used = dvalid && !anybad && sum_finite(mu);
       if (dvalid)
         for (int r = g; r < H; r += G) {
           const int i = (r + (r >> 4)) * TW + dl;

@@ -12,9 +12,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "plan.h"  // RM_LD
-
-typedef double d4 __attribute__((ext_vector_type(4)));
+#include "plan.h"      // RM_LD
+#include "sums.hip.h"  // d4
 
 #define RM_PI2 6.283185307179586476925286766559
 // Packed form of the same LDS image (PK = true in the routines below): only the lower BLOCK triangle of 16 x 16 blocks is kept - the

@@ -3,15 +3,14 @@
 // itself is the select of quant.hip.h on ll.  Every floating-point sum has a fixed order that depends on N alone (not on C, so a column
 // gives the same bits whichever block of columns it is computed in); the one atomic is the integer slot counter of the gather.
 //
-//   k_loo_loglik   grid: blocks of LOO_DRAWS draws x 4 wavefronts: the scheme of k_pred_main.  A wavefront owns 16 columns (data rows) as
-//                  the A operand of v_mfma_f64_16x16x4_f64, KS doubles per lane in registers, and walks the draws of the block 16 at a
-//                  time, B read straight from global memory, no branch in the product.  Exact zeros for k >= D and columns >= C (in A) and
-//                  for draws past the end or flagged by k_pred_valid (in B).  The MFMA steps of an (x, w) pair are the same whichever
+//   k_loo_loglik   grid: blocks of LOO_DRAWS draws x 4 wavefronts.  A wavefront owns 16 columns (data rows) as the A operand of the
+//                  DrawProduct of pred.hip.h and walks the draws of the block 16 at a time: exact zeros for k >= D and columns >= C (in
+//                  A) and for draws past the end or flagged by k_pred_valid (in B).  The MFMA steps of an (x, w) pair are the same whichever
 //                  lane holds them, so l does not depend on the position of the draw or the column.  Epilogue: l of include/rmhmc_loo.h;
 //                  result element e of lane l is column (l >> 4) + 4 e and draw l & 15; a flagged draw writes NaN, a draw past the end
 //                  nothing.
 //   k_loo_reduce   grid: the row blocks of loo_kernel_plan x 256 threads = LOO_ROW_LANES row lanes (one wavefront each) x 64 columns:
-//                  thread (g, c) walks rows g, g + 4, .. of its block with (sum, error) pairs (Knuth's two-sum); the four lanes of a
+//                  thread (g, c) walks rows g, g + 4, .. of its block with the sum_pairs of sums.hip.h; the four lanes of a
 //                  column meet in LDS in lane order and leave one record rec [block][LOO_REC][64].  MODE 0: count, sum l, sum exp(l),
 //                  min l.  MODE 1: sum (l - mean)^2.  MODE 2: n_lt, n_gt, n_eq and sum over l > cut of exp(lmin - l); a value below the
 //                  cutoff takes the next slot of its column's tail.
@@ -22,66 +21,33 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "adapt.hip.h"  // cov_two_sum
 #include "loo.h"
-
-typedef double loo_d4 __attribute__((ext_vector_type(4)));
+#include "pred.hip.h"  // DrawProduct, k_pred_valid
+#include "sums.hip.h"  // sum_pair, sum_finite, block_rows
 
 #define LOO_FIT_LDS_DOUBLES (LOO_MAX_TAIL + 2 * LOO_MAX_G + 2 * LOO_FIT_THREADS + 8)
 #define LOO_FIT_LDS_BYTES (LOO_FIT_LDS_DOUBLES * 8)
-
-__device__ __forceinline__ bool loo_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }
 
 template <int KS>
 __global__ __launch_bounds__(256) void k_loo_loglik(const double* __restrict__ w, size_t N, int D, const unsigned char* __restrict__ valid,
                                                     const double* __restrict__ x, const double* __restrict__ t, int C,
                                                     double* __restrict__ ll) {
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, a = lane & 15, k = lane >> 4;
-  const size_t d = (size_t)D;
   const int col0 = wv * 16;
   if (col0 >= C) return;  // (the whole wavefront)
-  constexpr int TAIL = KS < 8 ? KS : 8;  // the steps that may reach past column D, as in k_pred_main
-  double xa[KS];
-  {
-    const int ca = col0 + a;
-    const size_t cc = (size_t)(ca < C ? ca : C - 1);
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const int c = 4 * s + k;
-      const double v = x[cc * d + (size_t)(c < D ? c : D - 1)];
-      xa[s] = (ca < C && c < D) ? v : 0.0;
-    }
-  }
-  unsigned toff[TAIL];
-#pragma unroll
-  for (int u = 0; u < TAIL; ++u) {
-    const int c = 4 * (KS - TAIL + u) + k;
-    toff[u] = (unsigned)(c < D ? c : D - 1);
-  }
-  bool one[4];
-#pragma unroll
-  for (int el = 0; el < 4; ++el) {
-    const int cc = col0 + k + 4 * el;
-    one[el] = cc < C && t[cc] == 1.0;
-  }
-  const size_t j_begin = (size_t)blockIdx.x * LOO_DRAWS;
-  const size_t j_end = j_begin + LOO_DRAWS < N ? j_begin + LOO_DRAWS : N;
-  for (size_t j0 = j_begin; j0 < j_end; j0 += 16) {
+  DrawProduct<KS> xw;
+  xw.load(x, t, (size_t)col0, (size_t)C, D, lane);
+  const block_range draws = block_rows(blockIdx.x, LOO_DRAWS, N);
+  for (size_t j0 = draws.begin; j0 < draws.end; j0 += 16) {
     const size_t j = j0 + (size_t)a;
-    const size_t jc = j < j_end ? j : j_end - 1;
-    const bool ok = j < j_end && valid[jc] != 0;
-    const double* __restrict__ wr = w + jc * d;
-    loo_d4 acc = (loo_d4){0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int s = 0; s < KS - TAIL; ++s) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[s], ok ? wr[4 * s + k] : 0.0, acc, 0, 0, 0);
-#pragma unroll
-    for (int u = 0; u < TAIL; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[KS - TAIL + u], ok ? wr[toff[u]] : 0.0, acc, 0, 0, 0);
-    if (j < j_end) {
+    bool ok;
+    const d4 acc = xw.times(w, valid, D, j, draws.end, ok);
+    if (j < draws.end) {
 #pragma unroll
       for (int el = 0; el < 4; ++el) {
         const int cc = col0 + k + 4 * el;
         const double f = acc[el];
-        const double s = one[el] ? f : -f;
+        const double s = xw.one[el] ? f : -f;
         const double ex = exp(-fabs(f));
         double l = (s < 0.0 ? s : 0.0) - log1p(ex) + 0.0;  // (+ 0.0: a -0.0 becomes +0.0)
         if (!ok || f != f) l = __builtin_nan("");
@@ -104,61 +70,56 @@ struct loo_split_args {
 template <int MODE>
 __global__ __launch_bounds__(256) void k_loo_reduce(const double* __restrict__ ll, size_t N, int C, size_t rows_per_block,
                                                     const double* __restrict__ mean, loo_split_args sp, double* __restrict__ rec) {
-  __shared__ double red[LOO_ROW_LANES][2 * LOO_REC][LOO_MAX_COLS];
+  __shared__ sum_pair red[LOO_ROW_LANES][LOO_REC][LOO_MAX_COLS];
   const int tid = threadIdx.x, c = tid & 63, g = tid >> 6;
   const bool mine = c < C;
-  const size_t r_begin = (size_t)blockIdx.x * rows_per_block;
-  const size_t r_end = r_begin + rows_per_block < N ? r_begin + rows_per_block : N;
-  double s[LOO_REC] = {0.0, 0.0, 0.0, 0.0}, e[LOO_REC] = {0.0, 0.0, 0.0, 0.0};
-  if (MODE == 0) s[3] = __builtin_inf();
+  const block_range rows = block_rows(blockIdx.x, rows_per_block, N);
+  sum_pair s[LOO_REC] = {};  // (a count or the minimum lives in .s alone)
+  if (MODE == 0) s[3].s = __builtin_inf();
   double mu = 0.0, cut = 0.0, lmin = 0.0;
   long long tl = 0;
   if (mine && MODE == 1) mu = mean[c];
   if (mine && MODE == 2) { cut = sp.cut[c]; lmin = sp.lmin[c]; tl = sp.tail_len[c]; }
   const bool smoothed = tl >= 5;
   if (mine) {
-    for (size_t r = r_begin + (size_t)g; r < r_end; r += LOO_ROW_LANES) {
+    for (size_t r = rows.begin + (size_t)g; r < rows.end; r += LOO_ROW_LANES) {
       const double l = ll[r * (size_t)C + (size_t)c];
-      if (!loo_finite(l)) continue;
+      if (!sum_finite(l)) continue;
       if (MODE == 0) {
-        s[0] += 1.0;
-        cov_two_sum(s[1], e[1], l);
-        cov_two_sum(s[2], e[2], exp(l));
-        s[3] = l < s[3] ? l : s[3];
+        s[0].s += 1.0;
+        s[1].add(l);
+        s[2].add(exp(l));
+        s[3].s = l < s[3].s ? l : s[3].s;
       } else if (MODE == 1) {
         const double dl = l - mu;
-        cov_two_sum(s[0], e[0], dl * dl);
+        s[0].add(dl * dl);
       } else {
         if (smoothed && l < cut) {
-          s[0] += 1.0;
+          s[0].s += 1.0;
           const unsigned long long slot = atomicAdd(&sp.fill[c], 1ull);
           if (slot < (unsigned long long)tl) sp.tail[(size_t)c * (size_t)sp.stride + (size_t)slot] = l;  // (tl <= stride: checked on the host)
         } else if (smoothed && !(l > cut)) {
-          s[2] += 1.0;
+          s[2].s += 1.0;
         } else {
-          s[1] += 1.0;
-          cov_two_sum(s[3], e[3], exp(lmin - l));
+          s[1].s += 1.0;
+          s[3].add(exp(lmin - l));
         }
       }
     }
   }
 #pragma unroll
-  for (int q = 0; q < LOO_REC; ++q) {
-    red[g][q][c] = s[q];
-    red[g][LOO_REC + q][c] = e[q];
-  }
+  for (int q = 0; q < LOO_REC; ++q) red[g][q][c] = s[q];
   __syncthreads();
   if (g == 0 && mine) {
     double* out = rec + (size_t)blockIdx.x * LOO_REC * LOO_MAX_COLS + c;
 #pragma unroll
     for (int q = 0; q < LOO_REC; ++q) {
-      double ts = red[0][q][c], te = red[0][LOO_REC + q][c];
+      sum_pair t = red[0][q][c];
       for (int l = 1; l < LOO_ROW_LANES; ++l) {
-        if (MODE == 0 && q == 3) { ts = red[l][q][c] < ts ? red[l][q][c] : ts; continue; }
-        cov_two_sum(ts, te, red[l][q][c]);
-        te += red[l][LOO_REC + q][c];
+        if (MODE == 0 && q == 3) { t.s = red[l][q][c].s < t.s ? red[l][q][c].s : t.s; continue; }
+        t.add(red[l][q][c]);
       }
-      out[q * LOO_MAX_COLS] = ts + te;
+      out[q * LOO_MAX_COLS] = t.value();
     }
   }
 }
@@ -169,35 +130,35 @@ __global__ __launch_bounds__(64) void k_loo_fin(const double* __restrict__ rec, 
                                                 loo_split_args sp, long long* __restrict__ counts, double* __restrict__ body) {
   const int c = threadIdx.x;
   if (c >= C) return;
-  double s[LOO_REC] = {0.0, 0.0, 0.0, 0.0}, e[LOO_REC] = {0.0, 0.0, 0.0, 0.0};
-  if (MODE == 0) s[3] = __builtin_inf();
+  sum_pair s[LOO_REC] = {};
+  if (MODE == 0) s[3].s = __builtin_inf();
   for (size_t b = 0; b < nblocks; ++b) {
     const double* in = rec + b * LOO_REC * LOO_MAX_COLS + c;
 #pragma unroll
     for (int q = 0; q < LOO_REC; ++q) {
       const double v = in[q * LOO_MAX_COLS];
-      if (MODE == 0 && q == 3) s[3] = v < s[3] ? v : s[3];
-      else cov_two_sum(s[q], e[q], v);
+      if (MODE == 0 && q == 3) s[3].s = v < s[3].s ? v : s[3].s;
+      else s[q].add(v);
     }
   }
   const size_t n = (size_t)C;
   if (MODE == 0) {
-    const double m = s[0];
+    const double m = s[0].s;
     partial[c] = m;
-    partial[n + c] = m > 0.0 ? (s[1] + e[1]) / m : 0.0;
-    partial[3 * n + c] = s[2] + e[2];
-    partial[4 * n + c] = s[3];
+    partial[n + c] = m > 0.0 ? s[1].value() / m : 0.0;
+    partial[3 * n + c] = s[2].value();
+    partial[4 * n + c] = s[3].s;
   } else if (MODE == 1) {
-    partial[2 * n + c] = s[0] + e[0];
+    partial[2 * n + c] = s[0].value();
   } else {
-    const double n_lt = s[0], n_gt = s[1], n_eq = s[2];
+    const double n_lt = s[0].s, n_gt = s[1].s, n_eq = s[2].s;
     const double lmin = sp.lmin[c];
     double A = 0.0, B = 0.0;
     if (n_lt + n_gt + n_eq > 0.0) {
       double rest = n_eq;  // the copies of the cutoff that stay in the body: n_eq - r, r = M - n_lt
       if (sp.tail_len[c] >= 5) rest = n_eq - ((double)sp.tail_len[c] - n_lt);
-      if (rest > 0.0) cov_two_sum(s[3], e[3], rest * exp(lmin - sp.cut[c]));
-      A = s[3] + e[3];
+      if (rest > 0.0) s[3].add(rest * exp(lmin - sp.cut[c]));
+      A = s[3].value();
       B = (n_gt + rest) * exp(lmin);
     }
     counts[c] = (long long)n_lt;
@@ -207,23 +168,20 @@ __global__ __launch_bounds__(64) void k_loo_fin(const double* __restrict__ rec, 
   }
 }
 
-// the sum of the threads' (s, e) pairs in a fixed tree; every thread of the workgroup calls it and gets the sum
-__device__ __forceinline__ double loo_block_sum(double s, double e, double* red_s, double* red_e, int tid) {
+// the sum of the threads' pairs in a fixed tree; every thread of the workgroup calls it and gets the sum
+__device__ __forceinline__ double loo_block_sum(sum_pair v, sum_pair* red, int tid) {
   __syncthreads();  // (whoever still reads the last sum is done)
-  red_s[tid] = s;
-  red_e[tid] = e;
+  red[tid] = v;
   __syncthreads();
   for (int h = LOO_FIT_THREADS / 2; h >= 1; h >>= 1) {
     if (tid < h) {
-      double a = red_s[tid], b = red_e[tid];
-      cov_two_sum(a, b, red_s[tid + h]);
-      b += red_e[tid + h];
-      red_s[tid] = a;
-      red_e[tid] = b;
+      sum_pair a = red[tid];
+      a.add(red[tid + h]);
+      red[tid] = a;
     }
     __syncthreads();
   }
-  return red_s[0] + red_e[0];
+  return red[0].value();
 }
 
 // tail [C][stride], counts [2][C], cut, lmin, tail_len [C], sorted [C][stride] (scratch) -> fit [4][C]
@@ -235,9 +193,8 @@ __global__ __launch_bounds__(LOO_FIT_THREADS) void k_loo_fit(const double* __res
   double* y = loo_lds;                          // the tail: l, then y, by ascending l
   double* theta = loo_lds + LOO_MAX_TAIL;       // [LOO_MAX_G]
   double* Lv = theta + LOO_MAX_G;               // [LOO_MAX_G]
-  double* red_s = Lv + LOO_MAX_G;               // [LOO_FIT_THREADS]
-  double* red_e = red_s + LOO_FIT_THREADS;      // [LOO_FIT_THREADS]
-  double* scal = red_e + LOO_FIT_THREADS;       // [8]
+  sum_pair* red = (sum_pair*)(Lv + LOO_MAX_G);  // [LOO_FIT_THREADS]
+  double* scal = Lv + LOO_MAX_G + 2 * LOO_FIT_THREADS;  // [8]
   const int tid = threadIdx.x, c = blockIdx.x;
   const size_t n = (size_t)C;
   long long Ml = tail_len[c];
@@ -284,9 +241,9 @@ __global__ __launch_bounds__(LOO_FIT_THREADS) void k_loo_fit(const double* __res
     while ((long long)(G - 30 + 1) * (G - 30 + 1) <= (long long)M) ++G;  // 30 + floor(sqrt(M))
     for (int i = 1; i <= G; ++i) {
       const double th = 1.0 / yM + (1.0 - sqrt((double)G / ((double)i - 0.5))) / (3.0 * yq);
-      double s = 0.0, e = 0.0;
-      for (int j = tid; j < M; j += LOO_FIT_THREADS) cov_two_sum(s, e, log1p(-th * y[j]));
-      const double kappa = loo_block_sum(s, e, red_s, red_e, tid) / (double)M;
+      sum_pair s = {};
+      for (int j = tid; j < M; j += LOO_FIT_THREADS) s.add(log1p(-th * y[j]));
+      const double kappa = loo_block_sum(s, red, tid) / (double)M;
       if (tid == 0) {
         theta[i - 1] = th;
         Lv[i - 1] = (double)M * (log(-th / kappa) - kappa - 1.0);
@@ -306,18 +263,18 @@ __global__ __launch_bounds__(LOO_FIT_THREADS) void k_loo_fit(const double* __res
     }
     __syncthreads();
     const double th = scal[0];
-    double s = 0.0, e = 0.0;
-    for (int j = tid; j < M; j += LOO_FIT_THREADS) cov_two_sum(s, e, log1p(-th * y[j]));
-    const double kk = loo_block_sum(s, e, red_s, red_e, tid) / (double)M;
+    sum_pair s = {};
+    for (int j = tid; j < M; j += LOO_FIT_THREADS) s.add(log1p(-th * y[j]));
+    const double kk = loo_block_sum(s, red, tid) / (double)M;
     sigma = -kk / th;
     khat = (kk * (double)M + 5.0) / ((double)M + 10.0);
-    if (!loo_finite(khat) || !loo_finite(sigma)) {
+    if (!sum_finite(khat) || !sum_finite(sigma)) {
       smooth = false;
       khat = __builtin_inf();
     }
   }
   const double lw_cut = lmin - cut;
-  double sa = 0.0, ea = 0.0, sb = 0.0, eb = 0.0;
+  sum_pair sa = {}, sb = {};
   for (int j = 1 + tid; j <= M; j += LOO_FIT_THREADS) {
     const double l = srow[M - j];
     double lw = lmin - l;
@@ -327,10 +284,10 @@ __global__ __launch_bounds__(LOO_FIT_THREADS) void k_loo_fit(const double* __res
       lw = lw_cut + log1p(qj);
       lw = lw < 0.0 ? lw : 0.0;
     }
-    cov_two_sum(sa, ea, exp(lw));
-    cov_two_sum(sb, eb, exp(lw + l));
+    sa.add(exp(lw));
+    sb.add(exp(lw + l));
   }
-  const double A = loo_block_sum(sa, ea, red_s, red_e, tid);
-  const double B = loo_block_sum(sb, eb, red_s, red_e, tid);
+  const double A = loo_block_sum(sa, red, tid);
+  const double B = loo_block_sum(sb, red, tid);
   if (tid == 0) { fit[c] = khat; fit[n + c] = sigma; fit[2 * n + c] = A; fit[3 * n + c] = B; }
 }

@@ -260,6 +260,34 @@ void flow_tick(rmhmc_ctx* ctx, long long steps = 1) {
     default: { constexpr int NB_ = 4; __VA_ARGS__; } break;               \
   }
 
+// the steps of four columns of a DrawProduct (pred_ksteps, loo's ksteps)
+static_assert(PRED_MAX_D == 256 && LOO_MAX_D == 256, "the cases of KS_SWITCH end at 64 steps");
+#define KS_SWITCH(ksteps, ...)                                            \
+  switch (ksteps) {                                                       \
+    case 4: { constexpr int KS_ = 4; __VA_ARGS__; } break;                \
+    case 8: { constexpr int KS_ = 8; __VA_ARGS__; } break;                \
+    case 16: { constexpr int KS_ = 16; __VA_ARGS__; } break;              \
+    case 24: { constexpr int KS_ = 24; __VA_ARGS__; } break;              \
+    case 32: { constexpr int KS_ = 32; __VA_ARGS__; } break;              \
+    case 40: { constexpr int KS_ = 40; __VA_ARGS__; } break;              \
+    case 48: { constexpr int KS_ = 48; __VA_ARGS__; } break;              \
+    case 56: { constexpr int KS_ = 56; __VA_ARGS__; } break;              \
+    default: { constexpr int KS_ = 64; __VA_ARGS__; } break;              \
+  }
+
+// the tile widths of diag_tile_width and quant_tile_width; `otherwise` runs for any other
+#define TW_SWITCH(tw, otherwise, ...)                                     \
+  switch (tw) {                                                           \
+    case 1: { constexpr int TW_ = 1; __VA_ARGS__; } break;                \
+    case 2: { constexpr int TW_ = 2; __VA_ARGS__; } break;                \
+    case 4: { constexpr int TW_ = 4; __VA_ARGS__; } break;                \
+    case 8: { constexpr int TW_ = 8; __VA_ARGS__; } break;                \
+    case 16: { constexpr int TW_ = 16; __VA_ARGS__; } break;              \
+    case 32: { constexpr int TW_ = 32; __VA_ARGS__; } break;              \
+    case 64: { constexpr int TW_ = 64; __VA_ARGS__; } break;              \
+    default: { otherwise; } break;                                        \
+  }
+
 #define I8_SWITCH(ctx, ...) I8_SWITCH_S((ctx)->i8S, __VA_ARGS__)
 #define I8_SWITCH_S(sval, ...)                                                                       \
   switch (sval) {                                                                                    \
@@ -2732,16 +2760,9 @@ int launch_diag(rmhmc_ctx* ctx, const double* d_samples, long long n, long long 
   const dim3 grid((unsigned)ntiles, (unsigned)nblocks);
   const size_t lds = (size_t)diag_lds_bytes(H, tw);
   const int rows = (int)diag_lds_rows(H);
-#define DIAG_CASE(TW)                                                                                                      \
-  case TW:                                                                                                                 \
-    if (nq == 1) RC((launch_diag_acov<TW, 1>(ctx, grid, lds, d_samples, n, S, P, (int)H, (int)T, rows, d_blk, d_means)));     \
-    else RC((launch_diag_acov<TW, DIAG_NQ>(ctx, grid, lds, d_samples, n, S, P, (int)H, (int)T, rows, d_blk, d_means)));       \
-    break
-  switch (tw) {
-    DIAG_CASE(1); DIAG_CASE(2); DIAG_CASE(4); DIAG_CASE(8); DIAG_CASE(16); DIAG_CASE(32); DIAG_CASE(64);
-    default: return fail(ctx, RMHMC_ERR_RUNTIME, "diag: no kernel for this tile width");
-  }
-#undef DIAG_CASE
+  TW_SWITCH(tw, return fail(ctx, RMHMC_ERR_RUNTIME, "diag: no kernel for this tile width"),
+            if (nq == 1) RC((launch_diag_acov<TW_, 1>(ctx, grid, lds, d_samples, n, S, P, (int)H, (int)T, rows, d_blk, d_means)));
+            else RC((launch_diag_acov<TW_, DIAG_NQ>(ctx, grid, lds, d_samples, n, S, P, (int)H, (int)T, rows, d_blk, d_means))));
   hipLaunchKernelGGL(k_diag_reduce, dim3((unsigned)((rowlen + 255) / 256)), dim3(256), 0, ctx->stream, d_blk, nblocks, P, (int)H, (int)T, d_partial);
   hipLaunchKernelGGL(k_diag_m2, dim3((unsigned)((P + 15) / 16)), dim3(1024), 0, ctx->stream, d_means, 2 * n, P, d_partial);
   HIPCK(hipGetLastError());
@@ -2819,12 +2840,8 @@ int launch_quant_hist(rmhmc_ctx* ctx, const double* d_samples, long long N, int 
   const dim3 grid((unsigned)nblocks, (unsigned)ntiles);
   int rc = RMHMC_OK;
   launch(ctx, "quant_hist", [&](hipStream_t) {
-#define QUANT_CASE(TW) case TW: rc = launch_quant_tw<TW>(ctx, grid, d_samples, N, P, round, Kh, d_prefix, d_rep, d_cnt); break
-    switch (tw) {
-      QUANT_CASE(1); QUANT_CASE(2); QUANT_CASE(4); QUANT_CASE(8); QUANT_CASE(16); QUANT_CASE(32); QUANT_CASE(64);
-      default: rc = fail(ctx, RMHMC_ERR_RUNTIME, "quant: no kernel for this tile width");
-    }
-#undef QUANT_CASE
+    TW_SWITCH(tw, rc = fail(ctx, RMHMC_ERR_RUNTIME, "quant: no kernel for this tile width"),
+              rc = launch_quant_tw<TW_>(ctx, grid, d_samples, N, P, round, Kh, d_prefix, d_rep, d_cnt));
   });
   RC(rc);
   hipLaunchKernelGGL(k_quant_out, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, d_cnt, d_rep, P, total, d_hist);
@@ -3263,12 +3280,8 @@ int pred_partial(rmhmc_ctx* ctx, const double* d_w, size_t N, int D, const doubl
     const double* t_arg = tnew ? d_t : nullptr;
     launch(ctx, "pred", [&](hipStream_t st) {
       hipLaunchKernelGGL(k_pred_valid, dim3((unsigned)pl.vblocks), dim3(256), 0, st, d_w, N, D, (size_t)pl.draws_per_vblock, valid, cnt);
-      switch (pl.ksteps) {
-#define PRED_CASE(KS_) case KS_: hipLaunchKernelGGL(k_pred_main<KS_>, grid, dim3(64 * PRED_WAVES), 0, st, d_w, N, D, (size_t)pl.draws_per_block, valid, d_x, t_arg, R, rec); break
-        PRED_CASE(4); PRED_CASE(8); PRED_CASE(16); PRED_CASE(24); PRED_CASE(32); PRED_CASE(40); PRED_CASE(48); PRED_CASE(56);
-        default: static_assert(PRED_MAX_D == 256, "the cases above end at 64 steps"); PRED_CASE(64);
-#undef PRED_CASE
-      }
+      KS_SWITCH(pl.ksteps, hipLaunchKernelGGL(k_pred_main<KS_>, grid, dim3(64 * PRED_WAVES), 0, st, d_w, N, D, (size_t)pl.draws_per_block, valid, d_x,
+                                              t_arg, R, rec));
       hipLaunchKernelGGL(k_pred_fin, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, rec, (size_t)pl.nblocks, cnt, (size_t)pl.vblocks, R,
                          tnew ? 1 : 0, d_partial);
     });
@@ -3348,12 +3361,7 @@ int loo_loglik(rmhmc_ctx* ctx, const double* d_w, size_t N, int D, const double*
   RC(upload(ctx, b.t, t, (size_t)C));
   launch(ctx, "loo_loglik", [&](hipStream_t st) {
     hipLaunchKernelGGL(k_pred_valid, dim3((unsigned)pl.vblocks), dim3(256), 0, st, d_w, N, D, (size_t)pl.draws_per_vblock, b.valid, b.vcnt);
-    switch (pl.ksteps) {
-#define LOO_CASE(KS_) case KS_: hipLaunchKernelGGL(k_loo_loglik<KS_>, dim3((unsigned)pl.lblocks), dim3(256), 0, st, d_w, N, D, b.valid, b.x, b.t, C, d_ll); break
-      LOO_CASE(4); LOO_CASE(8); LOO_CASE(16); LOO_CASE(24); LOO_CASE(32); LOO_CASE(40); LOO_CASE(48); LOO_CASE(56);
-      default: static_assert(LOO_MAX_D == 256, "the cases above end at 64 steps"); LOO_CASE(64);
-#undef LOO_CASE
-    }
+    KS_SWITCH(pl.ksteps, hipLaunchKernelGGL(k_loo_loglik<KS_>, dim3((unsigned)pl.lblocks), dim3(256), 0, st, d_w, N, D, b.valid, b.x, b.t, C, d_ll));
   });
   HIPCK(hipGetLastError());
   return RMHMC_OK;

@@ -2,13 +2,13 @@
 // that of ais.hip.h, unchanged; what is here is small next to it: the conditional ESS of candidate steps, the reweighting, and systematic
 // resampling on integers.
 //
-// Conditional ESS (the partial of include/rmhmc_smc.h), three kernels in the shape of k_ais_max / k_ais_sums / k_ais_fin, no atomics, every
-// order fixed by n alone.  JT is the number of candidates the instantiation carries (the caller pads its J with copies of the last);
-// NQ = 1 + 2 JT quantities, numbered 0: lw, 1 + 2 j: lw + t_j, 2 + 2 j: lw + 2 t_j, which is the order of the pairs of the partial.
+// Conditional ESS (the partial of include/rmhmc_smc.h), three kernels (maxima, sums, finish: as the weights of ais.hip.h, but every
+// quantity is scaled by its own maximum), no atomics, every order fixed by n alone.  JT is the number of candidates
+// the instantiation carries (the caller pads its J with copies of the last); NQ = 1 + 2 JT quantities, numbered 0: lw, 1 + 2 j: lw + t_j, 2 + 2 j: lw + 2 t_j, which is the order of the pairs of the partial.
 //   k_smc_cess_max<JT>   grid: blocks of ais_plan x 256 threads.  One read of lw and l per entry; the block's maximum of every quantity
 //                        -> blk [nblocks][NQ]
 //   k_smc_cess_sums<JT>  the same grid.  Every block first takes the global maxima from blk (the same values in each); thread t adds the
-//                        NQ terms exp(x - a) of its entries t, t + 256, ... into (sum, error) pairs held in registers; the pairs of the
+//                        NQ terms exp(x - a) of its entries t, t + 256, ... into sum_pairs (sums.hip.h) held in registers; the pairs of the
 //                        256 threads are added in thread order, eight quantities at a time through LDS -> sums [nblocks][NQ][2]
 //   k_smc_cess_fin       thread q: quantity q over the blocks in block order -> partial [2 + 4 J]
 // A quantity whose maximum is -inf has every term 0 and is not evaluated; no index depends on the data.
@@ -18,8 +18,10 @@
 // (k_smc_scan_offsets, one block), exact in uint64 whatever the order; k_smc_ancestors is one binary search per offspring on
 // C_i (n 2^32) > (j 2^32 + U) Q, both sides as (hi, lo) pairs of 64-bit words; k_smc_gather copies the positions.
 #pragma once
-#include "ais.hip.h"
+#include <hip/hip_runtime.h>
+
 #include "smc.h"
+#include "sums.hip.h"  // sum_pair, block_rows, SUM_NEG_INF
 
 #pragma clang fp contract(off)
 
@@ -40,12 +42,11 @@ __global__ __launch_bounds__(256) void k_smc_cess_max(const double* __restrict__
   constexpr int NQ = 1 + 2 * JT;
   __shared__ double r[4][NQ];
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-  const size_t begin = (size_t)blockIdx.x * per_block;
-  const size_t end = begin + per_block < n ? begin + per_block : n;
+  const block_range rg = block_rows(blockIdx.x, per_block, n);
   double a[NQ];
 #pragma unroll
-  for (int q = 0; q < NQ; ++q) a[q] = AIS_NEG_INF;
-  for (size_t i = begin + tid; i < end; i += 256) {
+  for (int q = 0; q < NQ; ++q) a[q] = SUM_NEG_INF;
+  for (size_t i = rg.begin + tid; i < rg.end; i += 256) {
     const double x = lw[i];
     if (x != x) continue;
     const double l = ll[i];
@@ -81,45 +82,39 @@ __global__ __launch_bounds__(256) void k_smc_cess_sums(const double* __restrict_
   __shared__ double r_s[SMC_CESS_CHUNK][257], r_e[SMC_CESS_CHUNK][257];  // (257: the summing threads read one column each)
   const int tid = threadIdx.x;
   if (tid < NQ) {
-    double m = AIS_NEG_INF;
+    double m = SUM_NEG_INF;
     for (int b = 0; b < nblocks; ++b) m = blk[(size_t)b * NQ + tid] > m ? blk[(size_t)b * NQ + tid] : m;
     amax[tid] = m;
   }
   __syncthreads();
-  const size_t begin = (size_t)blockIdx.x * per_block;
-  const size_t end = begin + per_block < n ? begin + per_block : n;
-  double S[NQ], E[NQ];
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) { S[q] = 0.0; E[q] = 0.0; }
-  for (size_t i = begin + tid; i < end; i += 256) {
+  const block_range rg = block_rows(blockIdx.x, per_block, n);
+  sum_pair S[NQ] = {};
+  for (size_t i = rg.begin + tid; i < rg.end; i += 256) {
     const double x = lw[i];
     if (x != x) continue;
     const double l = ll[i];
-    if (amax[0] > AIS_NEG_INF) cov_two_sum(S[0], E[0], exp(x - amax[0]));
+    if (amax[0] > SUM_NEG_INF) S[0].add(exp(x - amax[0]));
     if (!isfinite(l)) continue;
 #pragma unroll
     for (int j = 0; j < JT; ++j) {
       const double t = dl.d[j] * l;
       const double x1 = x + t, x2 = x + 2.0 * t;
       const double a1 = amax[1 + 2 * j], a2 = amax[2 + 2 * j];
-      if (a1 > AIS_NEG_INF) cov_two_sum(S[1 + 2 * j], E[1 + 2 * j], exp(x1 - a1));
-      if (a2 > AIS_NEG_INF) cov_two_sum(S[2 + 2 * j], E[2 + 2 * j], exp(x2 - a2));
+      if (a1 > SUM_NEG_INF) S[1 + 2 * j].add(exp(x1 - a1));
+      if (a2 > SUM_NEG_INF) S[2 + 2 * j].add(exp(x2 - a2));
     }
   }
 #pragma unroll
   for (int q0 = 0; q0 < NQ; q0 += SMC_CESS_CHUNK) {
 #pragma unroll
     for (int u = 0; u < SMC_CESS_CHUNK; ++u)
-      if (q0 + u < NQ) { r_s[u][tid] = S[q0 + u]; r_e[u][tid] = E[q0 + u]; }
+      if (q0 + u < NQ) { r_s[u][tid] = S[q0 + u].s; r_e[u][tid] = S[q0 + u].e; }
     __syncthreads();
     if (tid < SMC_CESS_CHUNK && q0 + tid < NQ) {
-      double s = r_s[tid][0], e = r_e[tid][0];
-      for (int t = 1; t < 256; ++t) {
-        cov_two_sum(s, e, r_s[tid][t]);
-        e += r_e[tid][t];
-      }
+      sum_pair s = {r_s[tid][0], r_e[tid][0]};
+      for (int t = 1; t < 256; ++t) s.add(sum_pair{r_s[tid][t], r_e[tid][t]});
       double* out = sums + 2 * ((size_t)blockIdx.x * NQ + q0 + tid);
-      out[0] = s; out[1] = e;
+      out[0] = s.s; out[1] = s.e;
     }
     __syncthreads();
   }
@@ -130,15 +125,16 @@ __global__ __launch_bounds__(128) void k_smc_cess_fin(const double* __restrict__
                                                       double* __restrict__ partial) {
   const int q = threadIdx.x;
   if (q >= nq_out) return;
-  double a = AIS_NEG_INF, s = 0.0, e = 0.0;
+  double a = SUM_NEG_INF;
+  sum_pair s = {};
   for (int b = 0; b < nblocks; ++b) {
     const double m = blk[(size_t)b * nq + q];
     a = m > a ? m : a;
-    cov_two_sum(s, e, sums[2 * ((size_t)b * nq + q)]);
-    e += sums[2 * ((size_t)b * nq + q) + 1];
+    const double* in = sums + 2 * ((size_t)b * nq + q);
+    s.add(sum_pair{in[0], in[1]});
   }
   partial[2 * q] = a;
-  partial[2 * q + 1] = s + e;
+  partial[2 * q + 1] = s.value();
 }
 
 __global__ __launch_bounds__(256) void k_smc_reweight(double* __restrict__ lw, const double* __restrict__ ll, size_t n, double delta) {
@@ -146,7 +142,7 @@ __global__ __launch_bounds__(256) void k_smc_reweight(double* __restrict__ lw, c
   if (i >= n) return;
   const double x = lw[i], l = ll[i];
   if (x != x) return;  // (NaN stays)
-  lw[i] = isfinite(l) ? x + delta * l : AIS_NEG_INF;
+  lw[i] = isfinite(l) ? x + delta * l : SUM_NEG_INF;
 }
 
 __global__ __launch_bounds__(256) void k_smc_quantise(const double* __restrict__ lw, size_t n, double a, unsigned long long* __restrict__ q) {
@@ -154,7 +150,7 @@ __global__ __launch_bounds__(256) void k_smc_quantise(const double* __restrict__
   if (i >= n) return;
   const double x = lw[i];
   unsigned long long v = 0ull;
-  if (x == x && x > AIS_NEG_INF) {
+  if (x == x && x > SUM_NEG_INF) {
     const double dx = x - a;  // (a = -inf with a finite x: +inf, and the weight is the full one)
     v = (unsigned long long)floor(0x1p40 * exp(dx < 0.0 ? dx : 0.0));
   }

@@ -36,6 +36,18 @@ SHAPES = {
     "two_tiles": (8, 5, 60, 65, 29),              # P beyond one wavefront: a second dimension tile of one column
     "lag_sets": (10, 2, 133, 33, 65),             # 66 lags: more than the 64 that one set of 16 per thread covers at this tile width
     "lds_limit": (9, 2, 20000, 2, 7),             # H = 10000: one dimension per tile, 86 KB of LDS, without the quadratic cost
+    # the other tile widths with one lag set ...
+    "width_2": (11, 3, 40, 2, 7),
+    "width_4": (12, 3, 40, 3, 7),
+    "width_16": (13, 3, 40, 9, 7),
+    "width_32": (14, 3, 40, 17, 7),
+    # ... and every width below 64 with four: every lag of a half series longer than the 4096 / width lags of one set
+    "width_32_lag_sets": (15, 1, 300, 17, 149),
+    "width_16_lag_sets": (16, 1, 600, 9, 299),
+    "width_8_lag_sets": (17, 1, 1100, 5, 549),
+    "width_4_lag_sets": (18, 1, 2100, 3, 1049),
+    "width_2_lag_sets": (19, 1, 4200, 2, 2099),
+    "width_1_lag_sets": (20, 1, 8400, 1, 4199),
 }
 _inputs = {}
 

@@ -186,7 +186,7 @@ def test_column_edges(ctx, Cn):
     run_all(ctx, w, x, t, "C = %d" % Cn)
 
 
-@pytest.mark.parametrize("D", [1, 3, 4, 5, 63, 64, 65, 130, 256])
+@pytest.mark.parametrize("D", [1, 3, 4, 5, 17, 63, 64, 65, 128, 130, 192, 224, 256])     # every step count of the product
 def test_dimension_edges(ctx, D):
     w, x, t = draws(3, 11, D, 5)
     run_all(ctx, w, x, t, "D = %d" % D)

@@ -161,7 +161,7 @@ def ctx(hip):
 
 # ---- 1. shape edges ------------------------------------------------------------------------------------------------------------------------
 RS = [1, 15, 16, 17, 33, TILE - 1, TILE, TILE + 1]
-DS = [1, 3, 4, 5, 63, 64, 65, 130, 256]
+DS = [1, 3, 4, 5, 17, 63, 64, 65, 128, 130, 192, 224, 256]     # every step count of the product: 4, 8, 16, 24, .., 64
 NS = [1, 15, 16, 17, BLOCK - 1, BLOCK, BLOCK + 1, 2 * BLOCK + 3]
 
 

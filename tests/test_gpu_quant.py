@@ -43,6 +43,8 @@ SHAPES = {
     "narrow_tile": (7, 2, ROWS_16 // 2 + 3, 15),                 # the australian width: 4 lanes of a wavefront share a column
     "narrow_tile_ragged": (8, 1, 2 * ROWS_16 + 1, 17),           # 17 of 32 columns
     "two_columns": (9, 5, 1000, 2),
+    "three_columns": (11, 2, 500, 3),                            # a tile of 4
+    "seven_columns": (12, 2, 500, 7),                            # a tile of 8
     "ar1": (10, 40, 300, 33),                                    # an AR(1) posterior-like tensor, 396 000 values
 }
 _inputs = {}

@@ -82,7 +82,7 @@ def check_cess(got, want, EL, what):
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, 257, 1000, 70001])
 def test_conditional_ess(hip, n):
     rs = np.random.RandomState(n)
-    deltas = {1: np.array([3e-5]), 16: S.grid(0, 1.0, 0.0, 1.0), 32: np.geomspace(1e-7, 1.0, 32)}
+    deltas = {1: np.array([3e-5]), 4: np.geomspace(1e-5, 1.0, 4), 16: S.grid(0, 1.0, 0.0, 1.0), 32: np.geomspace(1e-7, 1.0, 32)}
     worst = (0.0, 0.0)
     with hip.context(10, 2, 1) as ctx:
         for name, (lw, ll) in cess_inputs(n, rs).items():
