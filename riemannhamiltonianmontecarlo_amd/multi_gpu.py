@@ -4,11 +4,26 @@ Chains never interact (the reference has exactly one chain, ``rmhmc.py:37-191``)
 partitions by chain index: rank r runs chains ``[start_r, end_r)`` on its own GPU with X, t replicated by
 its own ``rmhmc_set_data`` (ranks that are not handed the data get it from rank 0 by one broadcast before the
 run) and **no collective inside the sampling loop**.  The Philox counters use the
-global chain id (``chain_offset``), so the samples do not depend on the number of ranks.  The single
+global chain id (``chain_offset``), so every chain draws the same random numbers whatever the number of ranks, and the
+arithmetic class - fixed-point or fp64 metric - is chosen from the JOB (``shard_flags``), never from the shard.  What the
+samples then depend on is the plan of the context a chain runs in (csrc/plan.h), see "What sharding leaves unchanged"
+below.  The single
 exchange is the gather at write-out (``torch.distributed``: RCCL over xGMI for the ``nccl`` backend, gloo
 in the CPU tests), fed from device memory: the sampler writes its outputs through the ``_dev`` entry points of
 include/rmhmc.h into torch tensors in HBM and those tensors are what RCCL sends.  One process per GPU, launched by ``torch.distributed.run``.
 The other five samplers shard the same way through the output descriptor of include/rmhmc_out.h (``sampler=``).
+
+What sharding leaves unchanged (tests/test_gpu_batch_invariance.py).  Under one plan a chain's samples and
+counters are a function of (data, seed, global chain id, run arguments): bit-identical whatever the size of its batch, its slot and
+its neighbours.  The plan of a context follows its own chain count, so a sharded job equals the one-rank job BIT FOR BIT when
+every shard's plan equals the one-rank plan in the fields that order a sum or pick a kernel: the stepping path (``fused``,
+``medium``, ``hmc_traj``), the row splits ``nsplit`` and ``fsplit``, the int8 k pieces ``ksplit_a`` / ``ksplit_l``, and the
+variant of the adaptive Metropolis kernel (``amh_shape``: 1024 chains).  With the default options these move with the chain
+count (512 chains for the one-launch step and, with more than 1024 data rows, for ``k_hmc_traj``; 1024 chains for the row ranges
+of the fp64 assembly; ``nsplit`` with every 16 chains); the create options ``nsplit_max``, ``fsplit``, ``medium`` and
+``hmc_traj_maxn`` pin them.  Otherwise the shards agree with one rank to summation-order rounding per transition (the bounds
+the paths hold against each other and against the oracle), and a discrete decision - an accept, a trajectory length - can
+differ only where a uniform draw falls within that rounding of its threshold, after which that chain's path is another one.
 """
 import os
 
@@ -21,6 +36,16 @@ from .experiment import SAMPLERS
 _SHARDED = {"RMHMC": ("rmhmc", True), "HMC": ("hmc", False), "mMALA": ("mmala", True), "AMH": ("amh", False), "IWLS": ("iwls", True),
             "Gibbs": ("gibbs", False)}
 assert set(_SHARDED) == set(SAMPLERS)
+
+
+def shard_flags(sampler, D, n_chains, N, compat=False):
+    """The context flags of EVERY shard of a job of ``n_chains`` chains of ``sampler`` (a key of experiment.SAMPLERS) on N x D data:
+    the reference's guards for RMHMC with ``compat``, and the int8 metric assembly where the sampler assembles a metric and the JOB
+    is large enough for it to pay (_capi.auto_metric_flags).  A function of the job alone: fixed-point or fp64 metric is an accuracy
+    class, and it must not change with the number of ranks the job happens to run on."""
+    has_metric = _SHARDED[sampler][1]
+    flags = _capi.COMPAT if (compat and sampler == "RMHMC") else 0
+    return flags | (_capi.auto_metric_flags(D, n_chains, M=N) if has_metric else 0)
 
 
 def shard_range(n_total, world, rank):
@@ -96,6 +121,11 @@ def sample_sharded(XX, t, n_chains, NumOfIterations=6000, BurnIn=1000, NumOfLeap
                    sampler="RMHMC", sampler_args=None, diagnostics=False, max_lag=None, quantiles=None):
     """Run ``n_chains`` chains sharded over the ranks of the initialised process group.
 
+    The samples and counters are those of one rank bit for bit when every shard's plan equals the one-rank plan in the stepping path,
+    ``nsplit``, ``fsplit``, the int8 k pieces and ``amh_shape`` (module docstring; the create options in ``options`` can pin them), and
+    agree with one rank to summation-order rounding per transition otherwise.  The context flags - the int8 or the fp64 metric among
+    them - are those of the whole job on every rank (``shard_flags``).
+
     gather="samples": rank 0 returns (samples [n_chains,S,D], seconds, info); other ranks return None.
     gather="summary": only per-chain posterior mean / variance / min-ESS travel (config 4 at S=5000 would be
     168 GB of raw samples); rank 0 returns (summary dict, seconds, info).  min_ess of a chain whose ESS is NaN in
@@ -107,17 +137,20 @@ def sample_sharded(XX, t, n_chains, NumOfIterations=6000, BurnIn=1000, NumOfLeap
     iterations through its *_sample_to entry point (include/rmhmc_out.h; HIP library only); NumOfLeapFrogSteps, StepSize,
     NumOfNewtonSteps and ``compat`` are RMHMC's and do not apply: ``sampler_args`` carries the sampler's own run arguments as
     _capi.Context.sample_to takes them (L, eps for HMC; eps for mMALA; compat for IWLS), its defaults otherwise.  ``info`` then holds the
-    sampler's own counters.  The int8 metric assembly is chosen as for RMHMC where the sampler assembles a metric (mMALA, IWLS).
+    sampler's own counters.  The int8 metric assembly is chosen as for RMHMC, from the job's chain count, where the sampler assembles a
+    metric (mMALA, IWLS).
     ``diagnostics=True`` (every sampler, both gather modes; HIP library only): ``info`` gains rhat, ess_pooled, pairs and chains_used (D,),
     the split R-hat and the pooled ESS across ALL n_chains chains (include/rmhmc_diag.h; ``max_lag`` as there).  Every rank reduces the
     samples of its shard to a partial on its GPU - an empty shard contributes the identity - and the partials, a few KB each, are
     gathered to rank 0 and merged there in rank order.  "RMHMC" then runs through rmhmc_sample_to as the other samplers do, which by the
-    contract of include/rmhmc_out.h gives the same samples and counters.  The result does not depend on the number of ranks beyond
-    rounding (the merge is exact arithmetic only for the counts).
+    contract of include/rmhmc_out.h gives the same samples and counters.  GIVEN the samples, the merged result does not depend on the
+    number of ranks beyond rounding (the merge is exact arithmetic only for the counts); whether the samples themselves do is the
+    statement above.
     ``quantiles=probs`` (every sampler, both gather modes; HIP library only): ``info`` gains quantiles (Q, D) and quantile_draws (D,), the
     exact posterior quantiles over ALL n_chains chains (include/rmhmc_quant.h).  Every rank counts the histogram of a round on its GPU - an
     empty shard contributes the identity without a launch -, one all_reduce(SUM) per round merges them, and every rank takes the same step
-    on the sum; no sample leaves its GPU.  Counts add exactly, so the result is the same to the bit for any number of ranks.
+    on the sum; no sample leaves its GPU.  Counts add exactly, so GIVEN the samples the quantiles are the same to the bit for any number of
+    ranks: a statement about the merge, not about the samples.
     """
     if sampler not in _SHARDED:   # (before any collective: every rank raises on its own)
         raise ValueError("unknown sampler %r: one of %s" % (sampler, sorted(_SHARDED)))
@@ -171,12 +204,10 @@ def sample_sharded(XX, t, n_chains, NumOfIterations=6000, BurnIn=1000, NumOfLeap
     if diagnostics or quantiles is not None:   # the same run through rmhmc_sample_to: its samples stay where the partial is computed
         args = dict(L=NumOfLeapFrogSteps, eps=StepSize, K=NumOfNewtonSteps)
         return _sharded_to(sampler, args, XX, t, n_chains, NumOfIterations, BurnIn, seed, theta0, alpha, gather, lib, options, gpu, odev,
-                           cdev, start, end, counts, diagnostics=diagnostics, max_lag=max_lag, flags=_capi.COMPAT if compat else 0,
-                           quantiles=quantiles)
+                           cdev, start, end, counts, diagnostics=diagnostics, max_lag=max_lag, compat=compat, quantiles=quantiles)
     if n_local > 0:
         th = None if theta0 is None else np.broadcast_to(theta0, (n_chains, D))[start:end]
-        with lib.context(N, D, n_local, flags=(_capi.COMPAT if compat else 0) | _capi.auto_metric_flags(D, n_local, M=N), device=gpu,
-                         options=options) as ctx:
+        with lib.context(N, D, n_local, flags=shard_flags(sampler, D, n_chains, N, compat), device=gpu, options=options) as ctx:
             ctx.set_data(XX, t, alpha)
             # device-resident write-out (rmhmc_sample_dev / rmhmc_sample_stats_dev): the outputs stay in this rank's HBM
             if gather == "samples":
@@ -213,22 +244,21 @@ def sample_sharded(XX, t, n_chains, NumOfIterations=6000, BurnIn=1000, NumOfLeap
 
 
 def _sharded_to(sampler, args, XX, t, n_chains, n_iter, burn_in, seed, theta0, alpha, gather, lib, options, gpu, odev, cdev, start, end,
-                counts, diagnostics=False, max_lag=None, flags=0, quantiles=None):
+                counts, diagnostics=False, max_lag=None, compat=False, quantiles=None):
     """sample_sharded for the samplers that run through include/rmhmc_out.h: same shards, same gathers, the sampler's own counters;
     diagnostics: one more gather, of every rank's partial (include/rmhmc_diag.h); quantiles: eight all_reduces of every rank's histogram
-    (include/rmhmc_quant.h), while the shard's samples and its context are there.  flags: context flags besides the metric's"""
+    (include/rmhmc_quant.h), while the shard's samples and its context are there.  compat: RMHMC's guards (shard_flags)"""
     import torch as _t
     dist = _dist()
     rank, world = dist.get_rank(), dist.get_world_size()
-    key, has_metric = _SHARDED[sampler]
+    key = _SHARDED[sampler][0]
     N, D = XX.shape
     n_local, S = end - start, n_iter - burn_in
     counters = _capi.SAMPLERS_TO[key][1]
     if n_local > 0:
         if theta0 is not None:
             args["theta0"] = np.broadcast_to(theta0, (n_chains, D))[start:end]
-        flags |= _capi.auto_metric_flags(D, n_local, M=N) if has_metric else 0
-        with lib.context(N, D, n_local, flags=flags, device=gpu, options=options) as ctx:
+        with lib.context(N, D, n_local, flags=shard_flags(sampler, D, n_chains, N, compat), device=gpu, options=options) as ctx:
             ctx.set_data(XX, t, alpha)
             st = ctx.sample_to(key, n_iter, burn_in, where="device", device=odev, samples=gather == "samples" or quantiles is not None,
                                stats=gather == "summary", seed=seed, chain_offset=start, diagnostics=diagnostics, max_lag=max_lag, **args)
